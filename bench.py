@@ -11,7 +11,16 @@ per GPU (N(0,1) pixels, resident in HBM), gradient averaging across ranks (bucke
 overlapped with backward, ssl4gie_amd.parallel), AdamW(b=(0.9,0.95), wd 0.05) step.  bf16 MFMA
 operands, fp32 accumulate / residual / statistics.  Prints ONE JSON line on rank 0.
 
-Extra objects on the line:
+A plain run sets up, warms up, times the K steps and prints the line; nothing else.
+
+  --dump-outputs DIR  after the timed steps, what the last timed step computed goes to DIR/<name>.npy (float32):
+                      the tensors the step's forward returned (MAE: loss, pred, mask), the parameters after the
+                      optimizer step and their gradients (the model's arena buffers).  An array larger than its
+                      share of 64 MB is a fixed, seeded sample of its flattened elements (the same indices on every
+                      run); the inputs are seeded, so two builds can be compared output for output.
+  --full              also the extra measurements below (runs of their own, after the timed steps).
+
+Extra objects on the --full line:
   roofline      dominant kernel (bf16 NT GEMM, v_mfma_f32_16x16x32_bf16): algorithmic FLOPs (2MNK
                 summed over its launches) / summed launch durations, measured with HIP events on
                 the launch stream by the library's launch profiler over `--prof-steps` further
@@ -270,8 +279,8 @@ def roofline_pass(step, a, workload):
     stream around every launch of the heavy kernel kinds; outside the timed region, every stream folded back so
     that a launch has the chip to itself) -> the `roofline` object of the bench line for the kind with the largest
     summed duration: bound "mfma" (GEMM / attention kinds: algorithmic FLOPs / duration against 2.5 PFLOP/s) or
-    "hbm" (BatchNorm / LayerNorm entry points: algorithmic bytes / duration against 8 TB/s)."""
-    if a.prof_steps <= 0:
+    "hbm" (BatchNorm / LayerNorm entry points: algorithmic bytes / duration against 8 TB/s).  --full only."""
+    if not a.full or a.prof_steps <= 0:
         return None
     from ssl4gie_amd import _lib
     from ssl4gie_amd import engine as _engine
@@ -347,11 +356,43 @@ def roofline_pass(step, a, workload):
             "launches_per_step": per[name]["launches_per_step"], "kernels": per}
 
 
-def timed_steps(step, a, world, dev, ddp=None):
+DUMP_BYTES = 64 << 20   # --dump-outputs: all arrays together stay under this
+
+
+def dump_outputs(a, rank, model, outs):
+    """--dump-outputs DIR (rank 0): `outs` (name -> tensor, what the last timed step's forward returned) plus the
+    model's parameters after the optimizer step and their gradients, as DIR/<name>.npy in float32 (float64 stays
+    float64).  Every array gets an equal share of DUMP_BYTES; a larger one is replaced by a sample of its flattened
+    elements at indices drawn from a fixed seed (identical on every run and build)."""
+    if not a.dump_outputs or rank != 0:
+        return
+    import numpy as np
+    outs = dict(outs)
+    arena = model.arena() if hasattr(model, "arena") else None
+    if arena is not None:
+        outs["params"], outs["grads"] = arena.data, arena.grad
+    else:
+        ps = [p for p in model.parameters()]
+        outs["params"] = torch.cat([p.detach().reshape(-1).float() for p in ps])
+        outs["grads"] = torch.cat([(p.grad if p.grad is not None else torch.zeros_like(p)).detach().reshape(-1).float()
+                                   for p in ps])
+    cap = (DUMP_BYTES - (1 << 20)) // 8 // len(outs)   # elements per array (8 bytes: room for float64)
+    os.makedirs(a.dump_outputs, exist_ok=True)
+    for name, t in outs.items():
+        t = t.detach()
+        if t.numel() > cap:
+            idx = torch.randint(0, t.numel(), (cap,), generator=torch.Generator().manual_seed(20240601)).sort().values
+            t = t.reshape(-1)[idx.to(t.device)]
+        t = t.to(torch.float64 if t.dtype == torch.float64 else torch.float32).cpu().numpy()
+        np.save(os.path.join(a.dump_outputs, f"{name}.npy"), t)
+
+
+def timed_steps(step, a, world, dev, ddp=None, dump=None):
     """the driver's timing contract: W untimed warm-up steps, then exactly K steps bracketed by a
     barrier + torch.cuda.synchronize() on both sides; returns (last loss, MAX over ranks of the
     elapsed seconds, the data-parallel self-check of dp_verify() — None for one rank — taken after the
-    timed region)"""
+    timed region).  `dump` (--dump-outputs) runs right after the timed region, before anything else
+    steps the model again."""
     import torch.distributed as dist
 
     def fence():
@@ -392,6 +433,8 @@ def timed_steps(step, a, world, dev, ddp=None):
     tt = torch.tensor([dt], dtype=torch.float64, device=dev)
     if world > 1:
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
+    if dump is not None:
+        dump()
     snap = None
     if ddp is not None:  # the per-step figures of dp_info() describe the warm-up + timed steps only
         from ssl4gie_amd import resnet_engine
@@ -431,14 +474,19 @@ def bench_depth(a):
     tgt = torch.rand(B, 1, 224, 224, generator=g)
     tgt = torch.where(torch.rand(B, 1, 224, 224, generator=g) < 0.1, torch.zeros(()), tgt).to(dev)
 
+    keep = {} if a.dump_outputs else None
+
     def step():
         opt.zero_grad(set_to_none=True)
-        loss = loss_fn((ddp or model)(imgs), tgt)
+        depth = (ddp or model)(imgs)
+        loss = loss_fn(depth, tgt)
         loss.backward()   # under DataParallel the gradient exchange completes in here
         opt.step()
+        if keep is not None:
+            keep.update(loss=loss, depth=depth)
         return loss
 
-    loss, dt, verify = timed_steps(step, a, world, dev, ddp)
+    loss, dt, verify = timed_steps(step, a, world, dev, ddp, lambda: dump_outputs(a, rank, model, keep))
     roof = roofline_pass(step, a, a.workload)
     if world > 1:
         dist.barrier()
@@ -494,14 +542,18 @@ def bench_moco(a):
     x1 = torch.randn(B, 3, 224, 224, generator=g).to(dev)
     x2 = torch.randn(B, 3, 224, 224, generator=g).to(dev)
 
+    keep = {} if a.dump_outputs else None
+
     def step():
         opt.zero_grad(set_to_none=True)
         loss = (ddp or model)(x1, x2, 0.99)
         loss.backward()   # under DataParallel the gradient exchange completes in here
         opt.step()
+        if keep is not None:
+            keep.update(loss=loss)
         return loss
 
-    loss, dt, verify = timed_steps(step, a, world, dev, ddp)
+    loss, dt, verify = timed_steps(step, a, world, dev, ddp, lambda: dump_outputs(a, rank, model, keep))
     roof = roofline_pass(step, a, a.workload)
     if world > 1:
         dist.barrier()
@@ -549,14 +601,19 @@ def bench_vit(a):
     imgs = torch.randn(B, 3, 224, 224, generator=g).to(dev)
     labels = torch.randint(0, 6, (B,), generator=g).to(dev)
 
+    keep = {} if a.dump_outputs else None
+
     def step():
         opt.zero_grad(set_to_none=True)
-        loss = torch.nn.functional.cross_entropy((ddp or model)(imgs), labels)
+        logits = (ddp or model)(imgs)
+        loss = torch.nn.functional.cross_entropy(logits, labels)
         loss.backward()   # under DataParallel the gradient exchange completes in here
         opt.step()
+        if keep is not None:
+            keep.update(loss=loss, logits=logits)
         return loss
 
-    loss, dt, verify = timed_steps(step, a, world, dev, ddp)
+    loss, dt, verify = timed_steps(step, a, world, dev, ddp, lambda: dump_outputs(a, rank, model, keep))
     roof = roofline_pass(step, a, a.workload)
     if world > 1:
         dist.barrier()
@@ -603,15 +660,19 @@ def bench_det(a):
     g = torch.Generator("cpu").manual_seed(rank)
     imgs = torch.randn(B, 3, 1024, 1024, generator=g).to(dev)
 
+    keep = {} if a.dump_outputs else None
+
     def step():
         opt.zero_grad(set_to_none=True)
         out = (ddp or model)(imgs)
         loss = sum((v * v).mean() for v in out.values())
         loss.backward()   # under DataParallel the gradient exchange completes in here
         opt.step()
+        if keep is not None:
+            keep.update(loss=loss, **{f"out_{k}": v for k, v in out.items()})
         return loss
 
-    loss, dt, verify = timed_steps(step, a, world, dev, ddp)
+    loss, dt, verify = timed_steps(step, a, world, dev, ddp, lambda: dump_outputs(a, rank, model, keep))
     roof = roofline_pass(step, a, a.workload)
     if world > 1:
         dist.barrier()
@@ -675,14 +736,18 @@ def bench_bt(a):
     y1 = torch.randn(B, 3, 224, 224, generator=g).to(dev)
     y2 = (y1.cpu() + 0.5 * torch.randn(B, 3, 224, 224, generator=g)).to(dev)  # correlated views
 
+    keep = {} if a.dump_outputs else None
+
     def step():
         opt.zero_grad(set_to_none=True)
         loss = (ddp or model)(y1, y2)
         loss.backward()   # under DataParallel the gradient exchange completes in here
         opt.step()
+        if keep is not None:
+            keep.update(loss=loss)
         return loss
 
-    loss, dt, verify = timed_steps(step, a, world, dev, ddp)
+    loss, dt, verify = timed_steps(step, a, world, dev, ddp, lambda: dump_outputs(a, rank, model, keep))
     roof = roofline_pass(step, a, a.workload)
     if world > 1:
         dist.barrier()
@@ -714,8 +779,14 @@ def main():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--batch", type=int, default=256, help="images per GPU")
-    ap.add_argument("--prof-steps", type=int, default=3)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--prof-steps", type=int, default=3, help="--full: steps of the roofline pass")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also the roofline pass (`roofline`) and, N = 1 MAE, the CPU "
+                         "oracle's step (`cpu_baseline`); a plain run measures the headline figure only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/<name>.npy (float32, <= 64 MB in all, "
+                         "large arrays as a fixed seeded sample)")
     ap.add_argument("--precision", default="bf16")
     ap.add_argument("--optim", default="arena", choices=["torch", "arena"],
                     help="arena: the optimizer update as kernels over the parameter arena (ssl4gie_amd.optim: "
@@ -730,6 +801,8 @@ def main():
                     help="launch check without a GPU: the ranks meet (gloo), sum their ranks and rank 0 "
                          "prints one JSON line — what tests/test_abi_and_host.py runs through the self-launcher")
     a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
     if a.rendezvous_only:
         import torch.distributed as dist
         from ssl4gie_amd import parallel
@@ -823,14 +896,18 @@ def main():
     g = torch.Generator("cpu").manual_seed(0 if same else rank)
     imgs = torch.randn(a.batch, 3, 224, 224, generator=g).pin_memory().to(dev, non_blocking=True)
 
+    keep = {} if a.dump_outputs else None
+
     def step():
         opt.zero_grad(set_to_none=True)
-        loss, _, _ = (ddp or model)(imgs, mask_ratio=0.75)
+        loss, pred, mask = (ddp or model)(imgs, mask_ratio=0.75)
         loss.backward()   # under DataParallel the gradient exchange completes in here
         opt.step()
+        if keep is not None:
+            keep.update(loss=loss, pred=pred, mask=mask)
         return loss
 
-    loss, dt, verify = timed_steps(step, a, world, dev, ddp)
+    loss, dt, verify = timed_steps(step, a, world, dev, ddp, lambda: dump_outputs(a, rank, model, keep))
     final_loss = float(loss.detach())
 
     roof = roofline_pass(step, a, "mae")
@@ -859,7 +936,7 @@ def main():
         line.update(dp_info(ddp, a.steps + a.warmup, verify))
         if roof is not None:
             line["roofline"] = roof
-        if world == 1 and not a.no_cpu_baseline:
+        if world == 1 and a.full and not a.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline()
         print(json.dumps(line), flush=True)
     if world > 1:

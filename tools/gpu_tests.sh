@@ -21,8 +21,8 @@ for what in "$@"; do
     mae)   run mae 1100 python -m pytest tests/test_gpu_mae.py -m gpu -q --timeout 900 -p no:cacheprovider ;;
     all)   run all 1100 python -m pytest tests -m gpu -q -x --timeout 900 -p no:cacheprovider ;;
     smoke) run smoke 600 python -c "import __graft_entry__ as g; g.smoke()" ;;
-    bench) run bench 900 python bench.py --steps 10 --warmup 3 ;;
-    benchq) run benchq 600 python bench.py --steps 10 --warmup 3 --no-cpu-baseline ;;
+    bench) run bench 900 python bench.py --steps 10 --warmup 3 --full ;;
+    benchq) run benchq 600 python bench.py --steps 10 --warmup 3 --full --no-cpu-baseline ;;
   esac
 done
 echo "=== done" >> gpurun_out/summary.txt
