@@ -14,7 +14,7 @@
  *   - returns 0 on success, SSL4GIE_EARG (1000) for an invalid argument, otherwise a hipError_t;
  *   - callable from any host thread; the only mutable process-wide settings are the execution
  *     options ssl4gie_set_wgrad_stream / ssl4gie_set_compute_cus and the profiler;
- *   - ssl4gie_abi_version() = 7 (6: before ssl4gie_bn_coef_stats / ssl4gie_bn_apply_bits / ssl4gie_bn_bwd_reduce_bits existed — additions only; 5: before SSL4GIE_PROF_KINDS grew from 5 to 7 — the profiler's arrays; 1: before ssl4gie_gemm_desc gained `colsum_a` / `conv`; 2: before
+ *   - ssl4gie_abi_version() = 8 (7: before ssl4gie_stem3x3_{tiles,fwd,wgrad_workspace_bytes,wgrad} existed — additions only; 6: before ssl4gie_bn_coef_stats / ssl4gie_bn_apply_bits / ssl4gie_bn_bwd_reduce_bits existed — additions only; 5: before SSL4GIE_PROF_KINDS grew from 5 to 7 — the profiler's arrays; 1: before ssl4gie_gemm_desc gained `colsum_a` / `conv`; 2: before
  *     ssl4gie_block_bwd's `accumulate` became a flag word and the grouped / deferred weight-gradient
  *     entry points existed; 3: before the direct transport's error word / time-out / all-gather,
  *     ssl4gie_bn_combine_stats and ssl4gie_debug_nt256_stamps existed — additions only; 4: before
@@ -413,6 +413,23 @@ int ssl4gie_stem7x7_fwd(const void* packed, const void* w2s, void* y, float* col
 size_t ssl4gie_stem7x7_wgrad_workspace_bytes(int B, int H, int W);
 int ssl4gie_stem7x7_wgrad(const void* dy, const void* packed, float* dw2s, void* workspace,
                           size_t workspace_bytes, int B, int H, int W, int accumulate, void* stream);
+/* MoCo-v3 ConvStem layer 1 = nn.Conv2d(3, C0, 3, stride 2, pad 1, bias=False) (reference
+ * Models/moco_v3/vits.py:92-96) on the fp32 NCHW image itself: no patch matrix, no packed copy (ABI 8).
+ * C0 % 16 == 0, 16 <= C0 <= 128; H, W >= 2; Ho = (H-1)/2 + 1, Wo likewise.  dtype = type of y / dy:
+ * SSL4GIE_BF16 (image and weight rounded to bf16 on the way in, MFMA) or SSL4GIE_F32 (plain fp32 FMA chains).
+ *   fwd:   img fp32 [B,3,H,W], weight fp32 [C0][3][3][3] (the parameter) -> y [B,Ho,Wo,C0].  colstats
+ *          (optional): fp32 [ssl4gie_stem3x3_tiles(B,H,W)][2][C0], per-tile column sums / sums of squares of
+ *          the STORED y, as ssl4gie_bn_fwd_partials / ssl4gie_bn_coef_partials / ssl4gie_bn_stats_partials take.
+ *   wgrad: dweight fp32 [C0][3][3][3] (+)= sum over output pixels of dy [B,Ho,Wo,C0] x image patch.
+ *          Deterministic: one fp32 partial per workgroup in `workspace` + a fixed-order reduction.
+ * Any other shape returns SSL4GIE_EARG. */
+int ssl4gie_stem3x3_tiles(int B, int H, int W);
+int ssl4gie_stem3x3_fwd(const float* img, const float* weight, void* y, float* colstats, int dtype, int B,
+                        int H, int W, int C0, void* stream);
+size_t ssl4gie_stem3x3_wgrad_workspace_bytes(int dtype, int B, int H, int W, int C0);
+int ssl4gie_stem3x3_wgrad(const void* dy, const float* img, float* dweight, void* workspace,
+                          size_t workspace_bytes, int dtype, int B, int H, int W, int C0, int accumulate,
+                          void* stream);
 /* F.interpolate(scale_factor=2, mode="bilinear", align_corners=True) (:293-295, Interpolate :69-104)
  * x [B,H,W,C] -> y [B,2H,2W,C]; backward in gather form (no atomics) */
 int ssl4gie_bilinear2x_fwd(const void* x, void* y, int dtype, int B, int H, int W, int C,

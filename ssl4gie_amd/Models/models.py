@@ -42,11 +42,11 @@ class _ViTBackbone(EngineModule):
     """Shared trunk: patch-embed -> [cls | tokens] + pos -> blocks (-> taps) -> norm -> readout."""
 
     def _build_trunk(self, embed_dim, depth, num_heads, img_size=224, patch_size=16, in_chans=3,
-                     mlp_ratio=4.0):
+                     mlp_ratio=4.0, embed_layer=None):
         norm_layer = partial(nn.LayerNorm, eps=1e-6)
         self.embed_dim = embed_dim
         self.num_heads = num_heads
-        self.patch_embed = PatchEmbed(img_size, patch_size, in_chans, embed_dim)
+        self.patch_embed = (embed_layer or PatchEmbed)(img_size, patch_size, in_chans, embed_dim)
         n = self.patch_embed.num_patches
         self.cls_token = nn.Parameter(torch.zeros(1, 1, embed_dim))
         self.pos_embed = nn.Parameter(torch.zeros(1, n + 1, embed_dim))
@@ -72,13 +72,40 @@ class _ViTBackbone(EngineModule):
             self.decoder = self.adopt(DPT_decoder(num_classes=num_classes, dense=dense))
         self.out_token = out_token
 
+    def _conv_stem_tokens(self, imgs):
+        """MoCo-v3 ConvStem (reference Models/moco_v3/vits.py:72-112) on the engine: four (3x3 stride-2 convolution ->
+        BatchNorm -> ReLU) stages, channels-last — layer 1 by the 3-channel stem kernels, layers 2-4 by the library's
+        3x3 convolution — the 1x1 projection as a GEMM over the 14 x 14 map, then [cls | tokens] + position table.
+        Every convolution hands the batch statistics of its output to the BatchNorm behind it where it can (bf16)."""
+        from ..dpt_engine import Conv3x3Fn
+        from ..engine import TokensAssembleFn
+        from ..resnet_engine import BatchNormFn, StemConv3x3Fn
+        pe, dt, sink = self.patch_embed, self.dtype_, self.sink()
+        assert isinstance(pe.norm, nn.Identity), "ConvStem with a norm_layer is not built (the reference passes none)"
+        proj = pe.proj
+        fused = dt == torch.bfloat16   # fp32 parity mode: the BatchNorm takes its own statistics pass
+        r = StemConv3x3Fn.apply(imgs, proj[0].weight, dt, sink, fused)
+        x, st = r if fused else (r, None)
+        x = BatchNormFn.apply(x, proj[1].weight, proj[1].bias, None, proj[1], True, sink, st, None)
+        for i in (3, 6, 9):
+            conv, bn = proj[i], proj[i + 1]
+            x, st = Conv3x3Fn.apply(x, conv.weight, None, 2, False, sink, self.lp_cache, True)
+            x = BatchNormFn.apply(x, bn.weight, bn.bias, None, bn, True, sink, st, None)
+        B, _, _, C = x.shape
+        lin = proj[12]
+        y = LinearFn.apply(x.reshape(-1, C), lin.weight, lin.bias, dt, dt, sink, self.lp_cache)
+        return TokensAssembleFn.apply(y, self.cls_token, self.pos_embed, B, dt, sink)
+
     def _trunk(self, imgs, dense):
         self._prepare()
         p = self.patch_embed.patch_size[0]
         assert imgs.shape[2:] == tuple(self.patch_embed.img_size), "input size mismatch"
-        tok = PatchEmbedFn.apply(imgs.float(), self.patch_embed.proj.weight,
-                                 self.patch_embed.proj.bias, self.cls_token, self.pos_embed, None,
-                                 self.patch_embed.num_patches, p, self.dtype_, self.sink(), self._lp)
+        if not isinstance(self.patch_embed, PatchEmbed):   # the MoCo-v3 conv stem (moco_v3/vits.py ConvStem)
+            tok = self._conv_stem_tokens(imgs)
+        else:
+            tok = PatchEmbedFn.apply(imgs.float(), self.patch_embed.proj.weight,
+                                     self.patch_embed.proj.bias, self.cls_token, self.pos_embed, None,
+                                     self.patch_embed.num_patches, p, self.dtype_, self.sink(), self._lp)
         taps = TAP_BLOCKS if dense else ()
         tok, tap_out = self._blocks(self.blocks, tok, self.num_heads, self.norm.eps, taps=taps)
         if dense:

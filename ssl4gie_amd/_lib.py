@@ -21,7 +21,7 @@ if _dbg == "1" or _dbg.startswith("x"):  # "x<tag>": a tools/build_variant.sh ex
 
 # the one copy of the ABI revision on the Python side: build(), the tests and load() compare the
 # library's ssl4gie_abi_version() with it (include/ssl4gie_hip.h documents the history)
-ABI_VERSION = 7
+ABI_VERSION = 8
 
 PROF_KINDS = 7  # SSL4GIE_PROF_KINDS: entries of the launch profiler's arrays
 
@@ -116,6 +116,10 @@ PROTOTYPES = {
     "ssl4gie_stem7x7_fwd": (i32, [vp, vp, vp, vp, i32, i32, i32, vp]),
     "ssl4gie_stem7x7_wgrad_workspace_bytes": (sz, [i32, i32, i32]),
     "ssl4gie_stem7x7_wgrad": (i32, [vp, vp, vp, vp, sz, i32, i32, i32, i32, vp]),
+    "ssl4gie_stem3x3_tiles": (i32, [i32, i32, i32]),
+    "ssl4gie_stem3x3_fwd": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, i32, vp]),
+    "ssl4gie_stem3x3_wgrad_workspace_bytes": (sz, [i32, i32, i32, i32, i32]),
+    "ssl4gie_stem3x3_wgrad": (i32, [vp, vp, vp, vp, sz, i32, i32, i32, i32, i32, i32, vp]),
     "ssl4gie_bilinear2x_fwd": (i32, [vp, vp, i32, i32, i32, i32, i32, vp]),
     "ssl4gie_bilinear2x_bwd": (i32, [vp, vp, i32, i32, i32, i32, i32, vp]),
     "ssl4gie_pixel_shuffle": (i32, [vp, vp, vp, i32, i32, i32, i32, i32, i32, vp]),

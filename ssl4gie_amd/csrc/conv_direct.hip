@@ -28,6 +28,8 @@
 #include "gemm_internal.h"
 #include "ssl4gie_hip.h"
 #include "prof.h"
+#include <map>
+#include <mutex>
 
 typedef __attribute__((ext_vector_type(16))) float f32x16;
 #define MFMA32(a, b, c) __builtin_amdgcn_mfma_f32_32x32x16_bf16((a), (b), (c), 0, 0, 0)
@@ -952,5 +954,545 @@ extern "C" int ssl4gie_stem7x7_wgrad(const void* dy, const void* packed, float* 
         if (rc) return rc;
     }
     return ssl4gie_internal_reduce_partials((const float*)workspace, dw2s, grid, 64 * 7 * 32, (size_t)64 * 7 * 32,
+                                            accumulate, st);
+}
+
+// ------------------------------------------------------------------ 3x3 stride-2 stem, 3 input channels
+// MoCo-v3 ConvStem layer 1 = nn.Conv2d(3, C0, 3, stride 2, pad 1, bias=False) (reference
+// Models/moco_v3/vits.py:92-96) on the fp32 NCHW image, forward and weight gradient, no patch matrix and NO
+// packed copy of the image: the kernels read the three fp32 planes themselves.  A pack pass (as the 7x7 stem
+// has) would cost 12 B read + 8 B written per pixel once and 8 B read per use; the planes read directly cost
+// 12 B per use, their rows are contiguous (coalesced 4-byte loads), and the image is used twice per step and
+// encoder (forward, weight gradient) — so the direct read moves fewer bytes (24 against 36 per pixel) and
+// needs no cache of packed images on the host side.
+//
+// K = 27.  A tile is TH output rows x 64 output columns of one image; its input window (2 TH + 1 rows x 130
+// columns x 3 planes) is rounded to bf16 and staged ONCE in LDS as [row][column][c0 c1 c2 0] (8 B per pixel):
+// every image row is fetched once per tile (the row shared by two vertically adjacent tiles twice).  The window
+// of output column ox starts at the even staged column 2 ox, so four pixels x four channels of one kernel row
+// are one aligned 32-byte run = 16 K-entries; two kernel rows are one v_mfma_f32_16x16x32_bf16 step, the
+// convolution is two steps (K = 64, 27 live: an HBM-bound stream can afford it) per 16 pixels x 16 channels.
+// The weights live in registers for the whole kernel, read from the fp32 parameter itself (8 registers per
+// 16 channels).  Workgroups are persistent and fetch the next tile's window into registers while they compute
+// the current one.
+//  * forward: a wave owns one output row of the tile, 16 pixels at a time.  Pixels are the ROWS of the MFMA
+//    product and channels its columns, so a lane ends up with ONE channel of four pixels per 16-channel block:
+//    its contribution to the BatchNorm statistics is one (sum, sum of squares) pair per block, and the per-tile
+//    reduction is two shuffles per value (the other way round — four channels of one pixel per lane — it was
+//    four shuffles over four times as many values and cost 15-40 % of the kernel).  The bf16 results go through
+//    a wave-private LDS strip and leave as 16-byte pieces of whole 2 C0-byte pixel rows (16 pixels = one
+//    contiguous run of y).  colstats: sums / sums of squares of the rounded values, lanes -> waves -> tile in
+//    a fixed order.  C0 = 48 / 96: 108 / 155 VGPRs, no scratch, 18 / 26 KiB LDS, 4 / 3 workgroups per CU.
+//  * weight gradient: the contraction runs over pixels (32 per MFMA step).  dy^T is the A operand, gathered
+//    from a pixel-major LDS image of the dy tile one 32-bit word (two channels) at a time: the even channels
+//    of a 32-channel group form one 16-row block, the odd ones the next, so one gather feeds two MFMAs.  The
+//    patches are the B operand (27 of 2 x 16 columns live), gathered from the staged window.  Each workgroup
+//    keeps the C0 x 27 block in registers over all its tiles and writes one fp32 partial in the parameter's
+//    own [C0][3][3][3] layout; ssl4gie_internal_reduce_partials sums them in a fixed order (no atomics).
+//    C0 = 48 / 96: 96 + 32 / 128 + 48 registers (VGPR + AGPR), no scratch, 22 / 30 KiB LDS, 4 / 2 workgroups per CU.
+//  * F32 = the exact-fp32 parity path: the same tiles and staging with fp32 values (16 B per staged pixel) and
+//    plain FMA chains in place of the MFMAs; y / dy are fp32.
+#define MFMA16(a, b, c) __builtin_amdgcn_mfma_f32_16x16x32_bf16((a), (b), (c), 0, 0, 0)
+#define S3_TW 64
+#define S3_RW (2 * S3_TW + 2)  // staged columns: image columns 2 ox0 - 1 .. 2 ox0 + 128
+#define S3_FWD_TH 4
+template <int TH> struct S3G {
+    static constexpr int RH = 2 * TH + 1, NPIX = RH * S3_RW, IT = (NPIX + DC_THREADS - 1) / DC_THREADS;
+};
+struct S3Tile {
+    int b, oy0, ox0;
+};
+DEVI S3Tile s3_tile(int t, int tiles_x, int tiles_y, int th) {
+    S3Tile q;
+    q.ox0 = (t % tiles_x) * S3_TW;
+    t /= tiles_x;
+    q.oy0 = (t % tiles_y) * th;
+    q.b = t / tiles_y;
+    return q;
+}
+// the tile's input window -> registers (zeros outside the image)
+template <int TH>
+DEVI void s3_load(float (&v)[S3G<TH>::IT][3], const float* __restrict__ img, const S3Tile tp, int H, int W, int tid) {
+#pragma unroll
+    for (int i = 0; i < S3G<TH>::IT; ++i) {
+        const int idx = tid + i * DC_THREADS, rl = idx / S3_RW, xl = idx % S3_RW;
+        const int gy = 2 * tp.oy0 - 1 + rl, gx = 2 * tp.ox0 - 1 + xl;
+        v[i][0] = v[i][1] = v[i][2] = 0.f;
+        if (idx < S3G<TH>::NPIX && (unsigned)gy < (unsigned)H && (unsigned)gx < (unsigned)W) {
+            const float* p = img + ((size_t)tp.b * 3 * H + gy) * W + gx;
+            v[i][0] = p[0];
+            v[i][1] = p[(size_t)H * W];
+            v[i][2] = p[(size_t)2 * H * W];
+        }
+    }
+}
+template <int TH, bool F32> DEVI void s3_stage(char* Xs, const float (&v)[S3G<TH>::IT][3], int tid) {
+#pragma unroll
+    for (int i = 0; i < S3G<TH>::IT; ++i) {
+        const int idx = tid + i * DC_THREADS;
+        if (idx < S3G<TH>::NPIX) {
+            if constexpr (F32) *(f32x4*)(Xs + idx * 16) = f32x4{v[i][0], v[i][1], v[i][2], 0.f};
+            else *(u32x2*)(Xs + idx * 8) = u32x2{pack_bf2(v[i][0], v[i][1]), pack_bf2(v[i][2], 0.f)};
+        }
+    }
+}
+DEVI void s3_wave_sync() {  // orders a wave's own LDS writes and reads (wave-private strips: no workgroup barrier)
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+template <int NCB, bool F32>
+__global__ __launch_bounds__(DC_THREADS, (NCB <= 6 && !F32) ? 3 : 2) void stem3x3_fwd_kernel(
+    const float* __restrict__ img, const float* __restrict__ w, void* __restrict__ yv,
+    float* __restrict__ colstats, int H, int W, int Ho, int Wo, int tiles_x, int tiles_y, int ntiles) {
+    constexpr int TH = S3_FWD_TH, C0 = 16 * NCB, XB = F32 ? 16 : 8;
+    constexpr int XS_BYTES = S3G<TH>::NPIX * XB;
+    constexpr int OROW = C0 * 2 + 16;                                  // bf16 strip: bytes per pixel
+    constexpr int MID_BYTES = F32 ? 27 * C0 * 4 : 4 * 16 * OROW;       // fp32: the weights [27][C0]; bf16: the strips
+    static_assert(XS_BYTES % 16 == 0 && MID_BYTES % 16 == 0, "16-byte aligned LDS regions");
+    __shared__ __attribute__((aligned(16))) char smem[XS_BYTES + MID_BYTES + 4 * 2 * C0 * 4];
+    char* Xs = smem;
+    char* Ms = smem + XS_BYTES;
+    float* red = (float*)(smem + XS_BYTES + MID_BYTES);  // [4 waves][2][C0]
+    const int tid = threadIdx.x, lane = tid & 63, l15 = lane & 15, g = lane >> 4;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+
+    // ---- the weights, once per workgroup
+    [[maybe_unused]] bf16x8 a[NCB][2];
+    if constexpr (F32) {
+        float* Wf = (float*)Ms;  // [k = (ky 3 + kx) 3 + c][C0]
+        for (int i = tid; i < 27 * C0; i += DC_THREADS) {
+            const int co = i % C0, k = i / C0, c = k % 3, tap = k / 3;
+            Wf[i] = w[co * 27 + c * 9 + tap];
+        }
+    } else {
+        // MFMA step s, k = 8 g + j  <->  kernel row 2 s + (g >> 1), window pixel 2 (g & 1) + (j >> 2), channel j & 3
+#pragma unroll
+        for (int n = 0; n < NCB; ++n)
+#pragma unroll
+            for (int s = 0; s < 2; ++s)
+#pragma unroll
+                for (int j = 0; j < 8; ++j) {
+                    const int ky = 2 * s + (g >> 1), px = 2 * (g & 1) + (j >> 2), c = j & 3;
+                    float f = 0.f;
+                    if (ky < 3 && px < 3 && c < 3) f = w[(16 * n + l15) * 27 + c * 9 + ky * 3 + px];
+                    a[n][s][j] = (__bf16)f;
+                }
+    }
+
+    float xr[S3G<TH>::IT][3];
+    int tile = blockIdx.x;
+    if (tile < ntiles) s3_load<TH>(xr, img, s3_tile(tile, tiles_x, tiles_y, TH), H, W, tid);
+    for (; tile < ntiles; tile += gridDim.x) {
+        const S3Tile tp = s3_tile(tile, tiles_x, tiles_y, TH);
+        __syncthreads();  // the previous tile's window and statistics have been consumed
+        s3_stage<TH, F32>(Xs, xr, tid);
+        __syncthreads();
+        if (tile + (int)gridDim.x < ntiles)  // in flight while this tile is computed
+            s3_load<TH>(xr, img, s3_tile(tile + gridDim.x, tiles_x, tiles_y, TH), H, W, tid);
+
+        // statistics of this wave's share of the tile.  bf16: one channel per lane and 16-channel block (the lane's
+        // four pixels are added at once); fp32: four channels of one pixel per lane and block
+        [[maybe_unused]] f32x4 ssum[NCB], ssq[NCB];
+        [[maybe_unused]] float csum[NCB], csq[NCB];
+#pragma unroll
+        for (int n = 0; n < NCB; ++n) {
+            ssum[n] = ssq[n] = f32x4{0, 0, 0, 0};
+            csum[n] = csq[n] = 0.f;
+        }
+        const int oy = tp.oy0 + wave;
+        if (oy < Ho) {
+            for (int grp = 0; grp < S3_TW / 16; ++grp) {
+                const int oxg = tp.ox0 + grp * 16;  // wave-uniform
+                if (oxg >= Wo) break;
+                const int oxl = grp * 16 + l15;
+                f32x4 acc[NCB];
+#pragma unroll
+                for (int n = 0; n < NCB; ++n) acc[n] = f32x4{0, 0, 0, 0};
+                const size_t row0 = ((size_t)tp.b * Ho + oy) * Wo + oxg;  // first pixel of the group
+                if constexpr (F32) {
+                    const float* Wf = (const float*)Ms;
+#pragma unroll 1  // (unrolled, the 27 C0 weights are hoisted into registers across the group loop and spill)
+                    for (int tap = 0; tap < 9; ++tap) {
+                        const f32x4 xv = *(const f32x4*)(Xs + ((2 * wave + tap / 3) * S3_RW + 2 * oxl + tap % 3) * 16);
+#pragma unroll
+                        for (int c = 0; c < 3; ++c)
+#pragma unroll
+                            for (int n = 0; n < NCB; ++n)
+                                acc[n] += xv[c] * *(const f32x4*)(Wf + (tap * 3 + c) * C0 + 16 * n + 4 * g);
+                    }
+                    // acc[n][r] = channel 16 n + 4 g + r of pixel oxl: 16 bytes of its row
+                    if (oxg + l15 < Wo) {
+#pragma unroll
+                        for (int n = 0; n < NCB; ++n) {
+                            st4((float*)yv + (row0 + l15) * C0 + 16 * n + 4 * g, acc[n]);
+                            ssum[n] += acc[n];
+                            ssq[n] += acc[n] * acc[n];
+                        }
+                    }
+                } else {
+                    const char* xp = Xs + ((2 * wave + (g >> 1)) * S3_RW + 2 * oxl + 2 * (g & 1)) * 8;
+                    const bf16x8 x0 = *(const bf16x8*)xp;
+                    bf16x8 x1;  // kernel rows 2 (g < 2) and 3 (does not exist: zeros)
+#pragma unroll
+                    for (int j = 0; j < 8; ++j) x1[j] = (__bf16)0.f;
+                    if (g < 2) x1 = *(const bf16x8*)(xp + 2 * S3_RW * 8);
+                    // pixels are the rows of the product, channels its columns: acc[n][r] = pixel 4 g + r of the
+                    // group, channel 16 n + l15 — a lane adds its four pixels into ONE statistics pair per block
+#pragma unroll
+                    for (int n = 0; n < NCB; ++n) {
+                        acc[n] = MFMA16(x0, a[n][0], acc[n]);
+                        acc[n] = MFMA16(x1, a[n][1], acc[n]);
+                    }
+                    char* Os = Ms + wave * (16 * OROW);
+#pragma unroll
+                    for (int n = 0; n < NCB; ++n)
+#pragma unroll
+                        for (int r = 0; r < 4; ++r) {
+                            const bf16_t h = f2bf(acc[n][r]);
+                            *(bf16_t*)(Os + (4 * g + r) * OROW + (16 * n + l15) * 2) = h;
+                            if (oxg + 4 * g + r < Wo) {  // statistics of the STORED values
+                                const float v = bf2f(h);
+                                csum[n] += v;
+                                csq[n] += v * v;
+                            }
+                        }
+                    s3_wave_sync();
+                    bf16_t* y = (bf16_t*)yv;
+#pragma unroll
+                    for (int i = 0; i < (32 * NCB + 63) / 64; ++i) {  // 16-byte pieces of 16 whole pixel rows
+                        const int q = lane + 64 * i, p = q / (2 * NCB), j = q % (2 * NCB);
+                        if (q < 32 * NCB && oxg + p < Wo)
+                            *(u32x4*)(y + (row0 + p) * C0 + 8 * j) = *(const u32x4*)(Os + p * OROW + j * 16);
+                    }
+                    s3_wave_sync();
+                }
+            }
+        }
+        if (colstats) {
+            if constexpr (F32) {
+#pragma unroll
+                for (int n = 0; n < NCB; ++n)
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) {
+                        float s = ssum[n][r], q = ssq[n][r];
+#pragma unroll
+                        for (int o = 1; o < 16; o <<= 1) {  // over the 16 pixels
+                            s += __shfl_xor(s, o, 64);
+                            q += __shfl_xor(q, o, 64);
+                        }
+                        if (l15 == 0) {
+                            red[(wave * 2) * C0 + 16 * n + 4 * g + r] = s;
+                            red[(wave * 2 + 1) * C0 + 16 * n + 4 * g + r] = q;
+                        }
+                    }
+            } else {
+#pragma unroll
+                for (int n = 0; n < NCB; ++n) {
+                    float s = csum[n], q = csq[n];
+#pragma unroll
+                    for (int o = 16; o < 64; o <<= 1) {  // over the four pixel quads
+                        s += __shfl_xor(s, o, 64);
+                        q += __shfl_xor(q, o, 64);
+                    }
+                    if (g == 0) {
+                        red[(wave * 2) * C0 + 16 * n + l15] = s;
+                        red[(wave * 2 + 1) * C0 + 16 * n + l15] = q;
+                    }
+                }
+            }
+            __syncthreads();
+            if (tid < 2 * C0) {  // [2][C0] of this tile, the four rows added in order
+                const float s = ((red[tid] + red[2 * C0 + tid]) + red[4 * C0 + tid]) + red[6 * C0 + tid];
+                colstats[(size_t)tile * 2 * C0 + tid] = s;
+            }
+        }
+    }
+}
+
+// partial[workgroup][C0][3][3][3] fp32.  bf16: tiles of 2 x 64 pixels, wave w takes the 32 pixels (row w >> 1,
+// columns 32 (w & 1) ..) of every tile; fp32: tiles of 1 x 64, thread = up to five (channel, tap) pairs.
+template <int NCB, bool F32>
+__global__ __launch_bounds__(DC_THREADS) void stem3x3_wgrad_kernel(
+    const void* __restrict__ dyv, const float* __restrict__ img, float* __restrict__ partial, int H, int W,
+    int Ho, int Wo, int tiles_x, int tiles_y, int ntiles) {
+    constexpr int TH = F32 ? 1 : 2, C0 = 16 * NCB, NP2 = (NCB + 1) / 2, XB = F32 ? 16 : 8;
+    constexpr int XS_BYTES = (S3G<TH>::NPIX * XB + 15) / 16 * 16;
+    // bf16 dy image: [128 pixels][32 NP2 channels] + 8 bytes (the four pixel groups of a gather on different banks)
+    constexpr int DROW = F32 ? C0 * 4 : 64 * NP2 + 8;
+    constexpr int DS_BYTES = TH * S3_TW * DROW;
+    static_assert(F32 || DS_BYTES >= NP2 * 4 * 64 * 16, "the accumulator exchange fits in the dy image");
+    __shared__ __attribute__((aligned(16))) char smem[XS_BYTES + DS_BYTES];
+    char* Xs = smem;
+    char* Ds = smem + XS_BYTES;
+    const int tid = threadIdx.x, lane = tid & 63, l15 = lane & 15, g = lane >> 4;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    constexpr int CPP = F32 ? 4 * NCB : 2 * NCB;  // 16-byte pieces of a dy pixel row; NCB pieces per thread and tile
+
+    // bf16 accumulators: [32-channel group][even / odd channels][column block]; row 4 g + r, column l15
+    [[maybe_unused]] f32x4 acc[NP2][2][2];
+    constexpr int NI = F32 ? (C0 * 9 + DC_THREADS - 1) / DC_THREADS : 1;
+    [[maybe_unused]] float facc[NI][3];
+    [[maybe_unused]] int xoff[2];       // bf16: byte offset of this lane's patch entry (column block 0 / 1), -1: none
+    [[maybe_unused]] int xbase = 0, dbase = 0;
+    if constexpr (F32) {
+#pragma unroll
+        for (int i = 0; i < NI; ++i) facc[i][0] = facc[i][1] = facc[i][2] = 0.f;
+    } else {
+#pragma unroll
+        for (int p = 0; p < NP2; ++p)
+#pragma unroll
+            for (int e = 0; e < 4; ++e) acc[p][e >> 1][e & 1] = f32x4{0, 0, 0, 0};
+#pragma unroll
+        for (int cb = 0; cb < 2; ++cb) {
+            const int k = cb * 16 + l15, tap = k / 3, c = k % 3;
+            xoff[cb] = k < 27 ? ((tap / 3) * S3_RW + tap % 3) * 8 + c * 2 : -1;
+        }
+        const int oyl = wave >> 1, oxl0 = (wave & 1) * 32 + 8 * g;  // this lane's first pixel of the wave's 32
+        xbase = (2 * oyl * S3_RW + 2 * oxl0) * 8;
+        dbase = (oyl * S3_TW + oxl0) * DROW + l15 * 4;
+        // channels C0 .. 32 NP2 of the dy image and the row padding are never staged: zero them once
+        for (int i = tid; i < DS_BYTES / 4; i += DC_THREADS) ((unsigned*)Ds)[i] = 0u;
+    }
+
+    float xr[S3G<TH>::IT][3];
+    u32x4 dr[NCB];
+    auto load_dy = [&](const S3Tile tp) {
+#pragma unroll
+        for (int i = 0; i < NCB; ++i) {
+            const int idx = tid + i * DC_THREADS, p = idx / CPP, ch = idx % CPP;
+            const int oy = tp.oy0 + p / S3_TW, ox = tp.ox0 + p % S3_TW;
+            dr[i] = u32x4{0, 0, 0, 0};
+            if (oy < Ho && ox < Wo)
+                dr[i] = *(const u32x4*)((const char*)dyv + ((((size_t)tp.b * Ho + oy) * Wo + ox) * CPP + ch) * 16);
+        }
+    };
+    int tile = blockIdx.x;
+    if (tile < ntiles) {
+        const S3Tile tp = s3_tile(tile, tiles_x, tiles_y, TH);
+        s3_load<TH>(xr, img, tp, H, W, tid);
+        load_dy(tp);
+    }
+    for (; tile < ntiles; tile += gridDim.x) {
+        __syncthreads();  // the previous tile has been consumed (first pass: the zero fill is complete)
+        s3_stage<TH, F32>(Xs, xr, tid);
+#pragma unroll
+        for (int i = 0; i < NCB; ++i) {
+            const int idx = tid + i * DC_THREADS, p = idx / CPP, ch = idx % CPP;
+            if constexpr (F32) *(u32x4*)(Ds + p * DROW + ch * 16) = dr[i];
+            else {  // rows are 8-byte aligned only
+                *(u32x2*)(Ds + p * DROW + ch * 16) = u32x2{dr[i][0], dr[i][1]};
+                *(u32x2*)(Ds + p * DROW + ch * 16 + 8) = u32x2{dr[i][2], dr[i][3]};
+            }
+        }
+        __syncthreads();
+        if (tile + (int)gridDim.x < ntiles) {
+            const S3Tile tn = s3_tile(tile + gridDim.x, tiles_x, tiles_y, TH);
+            s3_load<TH>(xr, img, tn, H, W, tid);
+            load_dy(tn);
+        }
+        if constexpr (F32) {
+#pragma unroll
+            for (int i = 0; i < NI; ++i) {
+                const int it = tid + i * DC_THREADS;
+                if (it < C0 * 9) {
+                    const int co = it % C0, tap = it / C0;
+                    const char* xp = Xs + ((tap / 3) * S3_RW + tap % 3) * 16;
+                    const float* dp = (const float*)Ds + co;
+                    float s0 = facc[i][0], s1 = facc[i][1], s2 = facc[i][2];
+#pragma unroll 4
+                    for (int p = 0; p < S3_TW; ++p) {
+                        const f32x4 xv = *(const f32x4*)(xp + 2 * p * 16);
+                        const float d = dp[p * C0];
+                        s0 += d * xv[0];
+                        s1 += d * xv[1];
+                        s2 += d * xv[2];
+                    }
+                    facc[i][0] = s0; facc[i][1] = s1; facc[i][2] = s2;
+                }
+            }
+        } else {
+            // B operand: this lane's patch entry at its 8 pixels (window starts 16 bytes apart)
+            bf16x8 xb[2];
+#pragma unroll
+            for (int cb = 0; cb < 2; ++cb) {
+                u16x8 t = {0, 0, 0, 0, 0, 0, 0, 0};
+                if (xoff[cb] >= 0) {
+#pragma unroll
+                    for (int j = 0; j < 8; ++j) t[j] = *(const unsigned short*)(Xs + xbase + xoff[cb] + j * 16);
+                }
+                xb[cb] = __builtin_bit_cast(bf16x8, t);
+            }
+#pragma unroll
+            for (int p = 0; p < NP2; ++p) {
+                unsigned v[8];  // channels 32 p + 2 l15 (low half) and + 1 (high half) of the lane's 8 pixels
+#pragma unroll
+                for (int j = 0; j < 8; ++j) v[j] = *(const unsigned*)(Ds + dbase + j * DROW + p * 64);
+                u32x4 ev, od;
+#pragma unroll
+                for (int m = 0; m < 4; ++m) {
+                    ev[m] = (v[2 * m] & 0xffffu) | (v[2 * m + 1] << 16);
+                    od[m] = (v[2 * m] >> 16) | (v[2 * m + 1] & 0xffff0000u);
+                }
+                const bf16x8 ae = __builtin_bit_cast(bf16x8, ev), ao = __builtin_bit_cast(bf16x8, od);
+#pragma unroll
+                for (int cb = 0; cb < 2; ++cb) {
+                    acc[p][0][cb] = MFMA16(ae, xb[cb], acc[p][0][cb]);
+                    acc[p][1][cb] = MFMA16(ao, xb[cb], acc[p][1][cb]);
+                }
+            }
+        }
+    }
+    float* out = partial + (size_t)blockIdx.x * (C0 * 27);
+    if constexpr (F32) {
+#pragma unroll
+        for (int i = 0; i < NI; ++i) {
+            const int it = tid + i * DC_THREADS;
+            if (it < C0 * 9) {
+                const int co = it % C0, tap = it / C0;
+#pragma unroll
+                for (int c = 0; c < 3; ++c) out[co * 27 + c * 9 + tap] = facc[i][c];
+            }
+        }
+    } else {
+        // waves 1..3 hand their block to wave 0 through LDS, one after the other (fixed order)
+        f32x4* ex = (f32x4*)Ds;
+        for (int wv = 1; wv < 4; ++wv) {
+            __syncthreads();
+            if (wave == wv) {
+#pragma unroll
+                for (int p = 0; p < NP2; ++p)
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) ex[(p * 4 + e) * 64 + lane] = acc[p][e >> 1][e & 1];
+            }
+            __syncthreads();
+            if (wave == 0) {
+#pragma unroll
+                for (int p = 0; p < NP2; ++p)
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) acc[p][e >> 1][e & 1] += ex[(p * 4 + e) * 64 + lane];
+            }
+        }
+        if (wave == 0) {
+#pragma unroll
+            for (int p = 0; p < NP2; ++p)
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    const int k = (e & 1) * 16 + l15, tap = k / 3, c = k % 3;
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) {
+                        const int co = 32 * p + 2 * (4 * g + r) + (e >> 1);
+                        if (k < 27 && co < C0) out[co * 27 + c * 9 + tap] = acc[p][e >> 1][e & 1][r];
+                    }
+                }
+        }
+    }
+}
+
+static bool stem3_ok(int B, int H, int W, int C0, int dtype) {
+    return B > 0 && H >= 2 && W >= 2 && C0 >= 16 && C0 <= 128 && C0 % 16 == 0 &&
+           (dtype == SSL4GIE_BF16 || dtype == SSL4GIE_F32) &&
+           (long long)B * H * W * 3 < (1LL << 31) && (long long)B * H * W * C0 < (1LL << 33);
+}
+static int stem3_tiles(int B, int H, int W, int th, int* tx, int* ty) {
+    const int Ho = (H - 1) / 2 + 1, Wo = (W - 1) / 2 + 1;
+    *tx = (Wo + S3_TW - 1) / S3_TW;
+    *ty = (Ho + th - 1) / th;
+    return B * *tx * *ty;
+}
+// resident workgroups per CU of a kernel (registers and LDS as compiled), asked once per kernel; 1..8
+static int s3_per_cu(const void* kernel) {
+    static std::mutex mu;
+    static std::map<const void*, int> memo;
+    std::lock_guard<std::mutex> lk(mu);
+    auto it = memo.find(kernel);
+    if (it != memo.end()) return it->second;
+    int n = 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, kernel, DC_THREADS, 0) != hipSuccess || n < 1) n = 1;
+    if (n > 8) n = 8;
+    memo[kernel] = n;
+    return n;
+}
+extern "C" int ssl4gie_stem3x3_tiles(int B, int H, int W) {
+    if (B <= 0 || H < 2 || W < 2 || (long long)B * H * W * 3 >= (1LL << 31)) return 0;
+    int tx, ty;
+    return stem3_tiles(B, H, W, S3_FWD_TH, &tx, &ty);
+}
+#define S3_DISPATCH(KERNEL, ...)                                        \
+    switch (C0 / 16 + (dtype == SSL4GIE_F32 ? 8 : 0)) {                 \
+        case 1: KERNEL(1, false, __VA_ARGS__); break;                   \
+        case 2: KERNEL(2, false, __VA_ARGS__); break;                   \
+        case 3: KERNEL(3, false, __VA_ARGS__); break;                   \
+        case 4: KERNEL(4, false, __VA_ARGS__); break;                   \
+        case 5: KERNEL(5, false, __VA_ARGS__); break;                   \
+        case 6: KERNEL(6, false, __VA_ARGS__); break;                   \
+        case 7: KERNEL(7, false, __VA_ARGS__); break;                   \
+        case 8: KERNEL(8, false, __VA_ARGS__); break;                   \
+        case 9: KERNEL(1, true, __VA_ARGS__); break;                    \
+        case 10: KERNEL(2, true, __VA_ARGS__); break;                   \
+        case 11: KERNEL(3, true, __VA_ARGS__); break;                   \
+        case 12: KERNEL(4, true, __VA_ARGS__); break;                   \
+        case 13: KERNEL(5, true, __VA_ARGS__); break;                   \
+        case 14: KERNEL(6, true, __VA_ARGS__); break;                   \
+        case 15: KERNEL(7, true, __VA_ARGS__); break;                   \
+        case 16: KERNEL(8, true, __VA_ARGS__); break;                   \
+        default: return ARG_ERR;                                        \
+    }
+extern "C" int ssl4gie_stem3x3_fwd(const float* img, const float* weight, void* y, float* colstats, int dtype,
+                                   int B, int H, int W, int C0, void* stream) {
+    REQUIRE(img && weight && y && stem3_ok(B, H, W, C0, dtype));
+    const int Ho = (H - 1) / 2 + 1, Wo = (W - 1) / 2 + 1;
+    int tx, ty;
+    const int ntiles = stem3_tiles(B, H, W, S3_FWD_TH, &tx, &ty);
+    int per_cu = 0;
+#define S3_OCC(N, F, ...) per_cu = s3_per_cu((const void*)stem3x3_fwd_kernel<N, F>)
+    S3_DISPATCH(S3_OCC, 0)
+#undef S3_OCC
+    const int cap = per_cu * ssl4gie_internal_compute_cus();  // one resident wave of workgroups: they overlap each
+    const int grid = ntiles < cap ? ntiles : cap;             // other's staging, compute and stores
+    hipStream_t st = (hipStream_t)stream;
+    ProfScope prof(PROF_GEMM_NT, 2.0 * B * Ho * (double)Wo * C0 * 27, st);
+#define S3_FWD(N, F, ...)                                                                                          \
+    hipLaunchKernelGGL((stem3x3_fwd_kernel<N, F>), dim3(grid), dim3(DC_THREADS), 0, st, img, weight, y, colstats, \
+                       H, W, Ho, Wo, tx, ty, ntiles)
+    S3_DISPATCH(S3_FWD, 0)
+#undef S3_FWD
+    LAUNCH_CHECK();
+    return 0;
+}
+static int stem3_wgrad_grid(int B, int H, int W, int C0, int dtype, int* tx, int* ty, int* ntiles) {
+    *ntiles = stem3_tiles(B, H, W, dtype == SSL4GIE_F32 ? 1 : 2, tx, ty);
+    int per_cu = 0;
+#define S3_OCC(N, F, ...) per_cu = s3_per_cu((const void*)stem3x3_wgrad_kernel<N, F>)
+    S3_DISPATCH(S3_OCC, 0)
+#undef S3_OCC
+    const int cap = per_cu * ssl4gie_internal_compute_cus();
+    return *ntiles < cap ? *ntiles : cap;
+}
+extern "C" size_t ssl4gie_stem3x3_wgrad_workspace_bytes(int dtype, int B, int H, int W, int C0) {
+    if (!stem3_ok(B, H, W, C0, dtype)) return 0;
+    int tx, ty, nt;
+    return (size_t)stem3_wgrad_grid(B, H, W, C0, dtype, &tx, &ty, &nt) * C0 * 27 * sizeof(float);
+}
+extern "C" int ssl4gie_stem3x3_wgrad(const void* dy, const float* img, float* dweight, void* workspace,
+                                     size_t workspace_bytes, int dtype, int B, int H, int W, int C0,
+                                     int accumulate, void* stream) {
+    REQUIRE(dy && img && dweight && workspace && stem3_ok(B, H, W, C0, dtype));
+    REQUIRE(workspace_bytes >= ssl4gie_stem3x3_wgrad_workspace_bytes(dtype, B, H, W, C0));
+    const int Ho = (H - 1) / 2 + 1, Wo = (W - 1) / 2 + 1;
+    int tx, ty, ntiles;
+    const int grid = stem3_wgrad_grid(B, H, W, C0, dtype, &tx, &ty, &ntiles);
+    hipStream_t st = (hipStream_t)stream;
+    {
+        ProfScope prof(PROF_GEMM_TN, 2.0 * B * Ho * (double)Wo * C0 * 27, st);
+#define S3_WG(N, F, ...)                                                                                       \
+    hipLaunchKernelGGL((stem3x3_wgrad_kernel<N, F>), dim3(grid), dim3(DC_THREADS), 0, st, dy, img,            \
+                       (float*)workspace, H, W, Ho, Wo, tx, ty, ntiles)
+        S3_DISPATCH(S3_WG, 0)
+#undef S3_WG
+        LAUNCH_CHECK();
+    }
+    return ssl4gie_internal_reduce_partials((const float*)workspace, dweight, grid, C0 * 27, (size_t)C0 * 27,
                                             accumulate, st);
 }

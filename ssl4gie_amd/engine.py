@@ -751,6 +751,46 @@ class MatmulNTFn(torch.autograd.Function):
         return da, db
 
 
+def _assemble_tokens(y, cls, pos, B, nsel, ids=None):
+    """[cls | y rows] + position table -> fp32 [B, 1 + nsel, D] (the second half of a patch embedding)"""
+    return ops.tokens_assemble(y, cls.detach().contiguous().view(-1),
+                               pos.detach().contiguous().view(-1, pos.shape[-1]), B, nsel, ids=ids)
+
+
+def _assemble_tokens_bwd(dx, dtype, tc, tpos, acc):
+    """backward of _assemble_tokens: the position table's gradient (tpos, when it is trainable), the cls gradient
+    (tc) and -> the gradient of the embedded rows in the operand type"""
+    if tpos is not None:
+        dpos = dx.sum(0, keepdim=True)  # [1, 1 + L, D]
+        if acc:
+            tpos.add_(dpos)
+        else:
+            tpos.copy_(dpos)
+    return ops.tokens_assemble_bwd(dx, dtype, dcls_out=tc, accumulate=acc)
+
+
+class TokensAssembleFn(torch.autograd.Function):
+    """the token-assembly half of a patch embedding on its own, for embeddings that are not one GEMM (the MoCo-v3
+    ConvStem, reference Models/moco_v3/vits.py:104-112 + timm's cls concat / pos_embed add): y [B * N, D] operand rows
+    -> fp32 [B, 1 + N, D]."""
+
+    @staticmethod
+    def forward(ctx, y, cls, pos, B, dtype, sink):
+        y = y.contiguous()
+        x = _assemble_tokens(y, cls, pos, B, y.shape[0] // B)
+        ctx.save_for_backward(cls, pos)
+        ctx.sink, ctx.dtype = sink, dtype
+        return x
+
+    @staticmethod
+    def backward(ctx, dx):
+        cls, pos = ctx.saved_tensors
+        pos_grad = pos.requires_grad
+        tgs, acc, rets = ctx.sink.plan([cls] + ([pos] if pos_grad else []))
+        dy = _assemble_tokens_bwd(dx.contiguous(), ctx.dtype, tgs[0], tgs[1] if pos_grad else None, acc)
+        return dy, rets[0], (rets[1] if pos_grad else None), None, None, None
+
+
 class PatchEmbedFn(torch.autograd.Function):
     """PatchEmbed conv (k=s=p) as gather + GEMM, + pos-embed add + cls concat, computed ONLY for the
     patches that survive masking (`ids[:, :nsel]`): identical per-row arithmetic to embedding all
@@ -764,9 +804,7 @@ class PatchEmbedFn(torch.autograd.Function):
         w, _ = lp.get(weight, dtype)
         y = ops.linear_fwd(cols, w, bias.detach(), out_dtype=dtype)
         nsel_eff = cols.shape[0] // B
-        x = ops.tokens_assemble(y, cls.detach().contiguous().view(-1),
-                                pos.detach().contiguous().view(-1, pos.shape[-1]), B, nsel_eff,
-                                ids=ids)
+        x = _assemble_tokens(y, cls, pos, B, nsel_eff, ids=ids)
         ctx.save_for_backward(cols, weight, bias, cls, pos)
         ctx.sink, ctx.dtype = sink, dtype
         # a trainable position table (timm's default; the MAE / MoCo tables are fixed) gets its
@@ -782,14 +820,7 @@ class PatchEmbedFn(torch.autograd.Function):
         plist = [weight, bias, cls] + ([pos] if ctx.pos_grad else [])
         tgs, acc, rets = ctx.sink.plan(plist)
         tw, tb, tc = tgs[:3]
-        dx = dx.contiguous()
-        if ctx.pos_grad and tgs[3] is not None:
-            dpos = dx.sum(0, keepdim=True)  # [1, 1 + L, D]
-            if acc:
-                tgs[3].add_(dpos)
-            else:
-                tgs[3].copy_(dpos)
-        dy = ops.tokens_assemble_bwd(dx, ctx.dtype, dcls_out=tc, accumulate=acc)
+        dy = _assemble_tokens_bwd(dx.contiguous(), ctx.dtype, tc, tgs[3] if ctx.pos_grad else None, acc)
         if tw is not None:
             ops.linear_bwd_weight(dy, cols, out=tw, accumulate=acc, bias_out=tb)
         elif tb is not None:

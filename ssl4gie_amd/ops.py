@@ -841,6 +841,51 @@ def stem7x7_wgrad(dy, packed, B, H, W):
     return out[:, :, :7, :3].permute(0, 3, 1, 2)  # [co, c, ky, kx]
 
 
+def stem3x3_ok(imgs, C0):
+    """whether ssl4gie_stem3x3_{fwd,wgrad} take this image batch / width (ConvStem layer 1)"""
+    return imgs.dim() == 4 and imgs.shape[1] == 3 and imgs.shape[2] >= 2 and imgs.shape[3] >= 2 \
+        and C0 % 16 == 0 and 16 <= C0 <= 128
+
+
+def stem3x3_fwd(imgs, weight, dtype, colstats=False):
+    """nn.Conv2d(3, C0, 3, stride 2, pad 1, bias=False) on the fp32 NCHW image -> y [B,Ho,Wo,C0] in `dtype`
+    (+ BatchNorm partial statistics [tiles, 2, C0]); weight = the fp32 parameter [C0, 3, 3, 3]"""
+    _dev(imgs, weight)
+    _f32(imgs, weight)
+    assert imgs.dim() == 4 and imgs.shape[1] == 3 and imgs.is_contiguous(), "stem3x3: fp32 NCHW image, 3 channels"
+    assert weight.dim() == 4 and weight.shape[1:] == (3, 3, 3) and weight.is_contiguous()
+    B, _, H, W = imgs.shape
+    C0 = weight.shape[0]
+    Ho, Wo = (H - 1) // 2 + 1, (W - 1) // 2 + 1
+    L = _lib.load()
+    y = torch.empty(B, Ho, Wo, C0, dtype=dtype, device=imgs.device)
+    stats = torch.empty(max(L.ssl4gie_stem3x3_tiles(B, H, W), 1), 2, C0, dtype=torch.float32, device=imgs.device) \
+        if colstats else None
+    _lib.check(L.ssl4gie_stem3x3_fwd(ptr(imgs), ptr(weight), ptr(y), ptr(stats), code(dtype), B, H, W, C0, stream()),
+               "stem3x3_fwd")
+    return (y, stats) if colstats else y
+
+
+def stem3x3_wgrad(dy, imgs, out=None, accumulate=False):
+    """weight gradient [C0, 3, 3, 3] fp32 (+)= of the 3x3 stride-2 stem from dy [B,Ho,Wo,C0] and the fp32 image"""
+    _dev(dy, imgs, out)
+    _f32(imgs)
+    assert imgs.dim() == 4 and imgs.shape[1] == 3 and imgs.is_contiguous()
+    B, _, H, W = imgs.shape
+    C0 = dy.shape[-1]
+    assert dy.is_contiguous() and dy.shape == (B, (H - 1) // 2 + 1, (W - 1) // 2 + 1, C0), dy.shape
+    if out is None:
+        assert not accumulate
+        out = torch.empty(C0, 3, 3, 3, dtype=torch.float32, device=dy.device)
+    assert out.dtype == torch.float32 and out.shape == (C0, 3, 3, 3) and out.is_contiguous()
+    L = _lib.load()
+    nb = L.ssl4gie_stem3x3_wgrad_workspace_bytes(code(dy.dtype), B, H, W, C0)
+    ws = torch.empty(max(nb, 16), dtype=torch.uint8, device=dy.device)
+    _lib.check(L.ssl4gie_stem3x3_wgrad(ptr(dy), ptr(imgs), ptr(out), ptr(ws), nb, code(dy.dtype), B, H, W, C0,
+                                       int(accumulate), stream()), "stem3x3_wgrad")
+    return out
+
+
 def col2im3x3(dcols, B, H, W, C, stride):
     _dev(dcols)
     dx = torch.empty(B, H, W, C, dtype=dcols.dtype, device=dcols.device)

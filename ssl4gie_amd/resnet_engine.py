@@ -117,6 +117,43 @@ class StemConvFn(torch.autograd.Function):
         return None, rets[0], None, None, None, None
 
 
+class StemConv3x3Fn(torch.autograd.Function):
+    """MoCo-v3 ConvStem layer 1: Conv2d(3, C0, 3, stride 2, pad 1, bias=False) on the fp32 NCHW image (reference
+    Models/moco_v3/vits.py:92-96) by the direct stem kernels (csrc/conv_direct.hip), in both precisions: no patch
+    matrix, no packed image, and the weight operand is the fp32 parameter itself (nothing cached per step).
+    Returns (y [B,Ho,Wo,C0] in `dtype`, BatchNorm partial statistics of y) with want_stats, else y.  There is no
+    data gradient: the input is the image."""
+
+    @staticmethod
+    def forward(ctx, imgs, weight, dtype, sink: GradSink, want_stats=False):
+        imgs = imgs.contiguous().float()
+        if not ops.stem3x3_ok(imgs, weight.shape[0]):
+            raise NotImplementedError(f"no stem kernel for a {tuple(weight.shape)} convolution on a "
+                                      f"{tuple(imgs.shape)} batch (3 input channels, width % 16 == 0, <= 128)")
+        ctx.save_for_backward(imgs, weight)
+        ctx.sink = sink
+        w = weight.detach().contiguous()
+        if want_stats:
+            y, stats = ops.stem3x3_fwd(imgs, w, dtype, colstats=True)
+            ctx.mark_non_differentiable(stats)
+            ctx.set_materialize_grads(False)  # no zero tensor for the statistics' (absent) gradient
+            return y, stats
+        return ops.stem3x3_fwd(imgs, w, dtype)
+
+    @staticmethod
+    def backward(ctx, dy, *unused):
+        if dy is None:  # the map itself was not used downstream (gradients are not materialised)
+            return (None,) * 5
+        imgs, weight = ctx.saved_tensors
+        (tw,), acc, rets = ctx.sink.plan([weight])
+        if tw is not None:
+            if tw.is_contiguous():
+                ops.stem3x3_wgrad(dy.contiguous(), imgs, out=tw, accumulate=acc)   # straight into the gradient slice
+            else:
+                _write_grad(tw, ops.stem3x3_wgrad(dy.contiguous(), imgs), acc)
+        return None, rets[0], None, None, None
+
+
 class Subsample2Fn(torch.autograd.Function):
     """the pixel pick of a stride-2 1x1 convolution (Bottleneck.downsample[0]).  join: engine.GradJoin of
     the block input, which also feeds conv1: the scattered gradient is deposited there and summed in
