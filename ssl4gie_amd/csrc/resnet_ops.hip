@@ -252,17 +252,21 @@ __global__ void bn_fwd_coef_kernel(const float* __restrict__ mean, const float* 
     coef[c] = a;
     coef[C + c] = b;
 }
-// dx = coef[c] g + coef[C+c] x + coef[2C+c]   (expansion of gamma rstd (g - s1/n - xhat s2/n))
+// dx = coef[c] g + coef[C+c] (x - mu[c]) + coef[2C+c]   (gamma rstd (g - s1/n - xhat s2/n) with xhat = (x - mean) rstd)
+// x is centred BEFORE the product: folding mean into the constant term (coef[C+c] x + const) cancels two numbers of
+// size |mean| rstd |s2/n| and loses |mean| rstd bits of dx — unbounded when a small batch sits far from 0.
+// mu: a 16-byte-aligned copy of mean for the apply kernel's vector loads (callers' mean may be a slice)
 __global__ void bn_bwd_coef_kernel(const float* __restrict__ mean, const float* __restrict__ rstd,
                                    const float* __restrict__ gamma, const float* __restrict__ sums,
-                                   float inv_n, float* __restrict__ coef, int C) {
+                                   float inv_n, float* __restrict__ coef, int C, float* __restrict__ mu) {
     const int c = blockIdx.x * blockDim.x + threadIdx.x;
     if (c >= C) return;
     const float r = rstd[c], a = r * (gamma ? gamma[c] : 1.f);
     const float s1 = sums[c] * inv_n, s2 = sums[C + c] * inv_n;
     coef[c] = a;
     coef[C + c] = -a * r * s2;
-    coef[2 * C + c] = a * (mean[c] * r * s2 - s1);
+    coef[2 * C + c] = -a * s1;
+    mu[c] = mean[c];
 }
 // Tails of the single-GPU BatchNorm: the partition partials are summed by 4 waves x 64 channels per
 // block (a fixed order: deterministic), and the per-channel results are finished in the same
@@ -329,7 +333,7 @@ __global__ __launch_bounds__(1024) void bn_bwd_tail_kernel(
     const float* __restrict__ partial, int parts, const float* __restrict__ mean,
     const float* __restrict__ rstd, const float* __restrict__ gamma, float inv_n,
     float* __restrict__ coef, float* __restrict__ dgamma, float* __restrict__ dbeta,
-    int accumulate, int C, const float* __restrict__ beta, float* __restrict__ mcoef) {
+    int accumulate, int C, const float* __restrict__ beta, float* __restrict__ mcoef, float* __restrict__ mu) {
     __shared__ float red[15][2][64];
     float s, q;
     if (!bn_sum_partials(partial, parts, C, s, q, red)) return;
@@ -344,7 +348,8 @@ __global__ __launch_bounds__(1024) void bn_bwd_tail_kernel(
     const float s1 = s * inv_n, s2 = q * inv_n;
     coef[c] = a;
     coef[C + c] = -a * r * s2;
-    coef[2 * C + c] = a * (mean[c] * r * s2 - s1);
+    coef[2 * C + c] = -a * s1;
+    mu[c] = mean[c];
     if (dbeta) dbeta[c] = accumulate ? dbeta[c] + s : s;
     if (dgamma) dgamma[c] = accumulate ? dgamma[c] + q : q;
 }
@@ -482,17 +487,17 @@ __global__ __launch_bounds__(256) void bn_bwd_reduce_kernel(
         }
     }
 }
-// dx = coef[c] g + coef[C + c] x + coef[2C + c];  mcoef (optional, [2][C]): g = x mcoef[c] + mcoef[C + c] > 0 ? dy : 0
+// dx = coef[c] g + coef[C + c] (x - mu[c]) + coef[2C + c];  mcoef (optional, [2][C]): g = x mcoef[c] + mcoef[C + c] > 0 ? dy : 0
 template <typename T>
 __global__ void bn_bwd_apply_kernel(const T* __restrict__ dy, const T* __restrict__ y,
                                     const T* __restrict__ x, const float* __restrict__ coef,
                                     T* __restrict__ dx, int relu, int C, long long total,
-                                    const float* __restrict__ mcoef) {
+                                    const float* __restrict__ mcoef, const float* __restrict__ mu) {
     constexpr int V = V16<T>::N;
     const long long idx = ((long long)blockIdx.x * blockDim.x + threadIdx.x) * V;
     if (idx >= total) return;
     const int c = (int)(idx % C);
-    float g[V], xv[V], yy[V], a[V], b[V], d[V];
+    float g[V], xv[V], yy[V], a[V], b[V], d[V], m[V];
     un<T>(*(const typename V16<T>::raw*)(dy + idx), g);
     un<T>(*(const typename V16<T>::raw*)(x + idx), xv);
     if (mcoef) {  // the forward's pre-activation, sign only
@@ -510,11 +515,12 @@ __global__ void bn_bwd_apply_kernel(const T* __restrict__ dy, const T* __restric
         *(f32x4*)(a + j) = ld4(coef + c + j);
         *(f32x4*)(b + j) = ld4(coef + C + c + j);
         *(f32x4*)(d + j) = ld4(coef + 2 * C + c + j);
+        *(f32x4*)(m + j) = ld4(mu + c + j);
     }
 #pragma unroll
     for (int j = 0; j < V; ++j) {
         const float gg = (relu && !(yy[j] > 0.f)) ? 0.f : g[j];
-        g[j] = a[j] * gg + b[j] * xv[j] + d[j];
+        g[j] = a[j] * gg + b[j] * (xv[j] - m[j]) + d[j];
     }
     *(typename V16<T>::raw*)(dx + idx) = pk<T>(g);
 }
@@ -795,7 +801,7 @@ static int bn_fold(const float* partial, int parts, float* scratch, int C, hipSt
 extern "C" size_t ssl4gie_bn_workspace_bytes(long long rows, int C) {
     size_t parts = (size_t)bn_parts(rows, C);
     if (parts < 64) parts = 64;  // the partials paths fold into 64 x 2C floats of this workspace
-    // coef 3C, partials parts x 2C, sums 2C, pivot C, fold scratch 64 x 2C (backward tail)
+    // coef 3C, partials parts x 2C, sums 2C, pivot C (backward: mask coefficients, copy of mean), fold scratch 64 x 2C
     return ((parts + 1) * 2 + 1 + 3 + 2 * BN_FOLD) * C * sizeof(float);
 }
 // forward: statistics over the rows of x [rows, C] (biased variance), optional running-stat update,
@@ -867,14 +873,12 @@ static int bn_bwd_impl(const void* dy, const void* y, const void* x, const float
     }
 #undef BN_REDUCE
     LAUNCH_CHECK();
-    // dbeta = sum g, dgamma = sum g xhat, and the dx coefficients, in one launch (after a 64-way
-    // fold when the reduction left hundreds of partials: the tail's blocks are few and sequential)
-    const float* pp; int np;
-    float* fold_scratch = partial + ((size_t)parts * 2 + 3) * C;
-    int rc = bn_fold(partial, parts, fold_scratch, C, st, &pp, &np);
-    if (rc) return rc;
-    hipLaunchKernelGGL(bn_bwd_tail_kernel, dim3((C + 63) / 64), bn_tail_block(np), 0, st, pp, np, mean,
-                       rstd, gamma, 1.0f / (float)rows, coef, dgamma, dbeta, accumulate, C, beta, mcoef);
+    // dbeta = sum g, dgamma = sum g xhat, and the dx coefficients, in one launch.  No fold in front: bn_parts caps
+    // the partitions at 1024 <= BN_TAIL_WIDE, so the tail always sums the reduction's partials itself (the fold
+    // belongs to the statistics-from-partials entry points, whose producers hand over thousands of rows)
+    float* mu = partial + ((size_t)parts * 2 + 2) * C;  // the forward's `pivot` slot: free here
+    hipLaunchKernelGGL(bn_bwd_tail_kernel, dim3((C + 63) / 64), bn_tail_block(parts), 0, st, partial, parts, mean,
+                       rstd, gamma, 1.0f / (float)rows, coef, dgamma, dbeta, accumulate, C, beta, mcoef, mu);
     LAUNCH_CHECK();
     const long long total = rows * C;
     // with a residual branch the reduction pass has just written dres = the MASKED gradient (dy or 0, no
@@ -885,7 +889,7 @@ static int bn_bwd_impl(const void* dy, const void* y, const void* x, const float
     const void* ysrc = masked ? nullptr : y;
     const int relu_apply = masked ? 0 : relu;
     RN_LAUNCH(dtype, bn_bwd_apply_kernel, total / rvn(dtype), (const T*)gsrc, (const T*)ysrc, (const T*)x,
-              coef, (T*)dx, relu_apply, C, total, (const float*)mcoef);
+              coef, (T*)dx, relu_apply, C, total, (const float*)mcoef, (const float*)mu);
     return 0;
 }
 extern "C" int ssl4gie_bn_bwd(const void* dy, const void* y, const void* x, const float* gamma,
@@ -1172,15 +1176,16 @@ extern "C" int ssl4gie_bn_bwd_apply_xmask(const void* dy, const void* x, const f
             C % 8 == 0);
     hipStream_t st = (hipStream_t)stream;
     float* mcoef = workspace + 3 * (size_t)C;  // [2][C] behind the dx coefficients
+    float* mu = workspace + 5 * (size_t)C;     // ... and the aligned copy of mean behind them
     hipLaunchKernelGGL(bn_bwd_coef_kernel, dim3((C + 255) / 256), dim3(256), 0, st, mean, rstd, gamma,
-                       sums, inv_count, workspace, C);
+                       sums, inv_count, workspace, C, mu);
     LAUNCH_CHECK();
     hipLaunchKernelGGL(bn_fwd_coef_kernel, dim3((C + 255) / 256), dim3(256), 0, st, mean, rstd, gamma, beta,
                        mcoef, C);
     LAUNCH_CHECK();
     const long long total = rows * C;
     RN_LAUNCH(dtype, bn_bwd_apply_kernel, total / rvn(dtype), (const T*)dy, (const T*)nullptr, (const T*)x,
-              workspace, (T*)dx, 1, C, total, (const float*)mcoef);
+              workspace, (T*)dx, 1, C, total, (const float*)mcoef, (const float*)mu);
     return 0;
 }
 extern "C" int ssl4gie_bn_bwd_apply(const void* dy, const void* y, const void* x, const float* gamma,
@@ -1191,12 +1196,13 @@ extern "C" int ssl4gie_bn_bwd_apply(const void* dy, const void* y, const void* x
             C % 8 == 0);
     REQUIRE(!relu || y);
     hipStream_t st = (hipStream_t)stream;
+    float* mu = workspace + 5 * (size_t)C;  // aligned copy of mean behind the coefficients
     hipLaunchKernelGGL(bn_bwd_coef_kernel, dim3((C + 255) / 256), dim3(256), 0, st, mean, rstd, gamma,
-                       sums, inv_count, workspace, C);
+                       sums, inv_count, workspace, C, mu);
     LAUNCH_CHECK();
     const long long total = rows * C;
     RN_LAUNCH(dtype, bn_bwd_apply_kernel, total / rvn(dtype), (const T*)dy, (const T*)y, (const T*)x,
-              workspace, (T*)dx, relu, C, total, (const float*)nullptr);
+              workspace, (T*)dx, relu, C, total, (const float*)nullptr, (const float*)mu);
     return 0;
 }
 
