@@ -135,10 +135,100 @@ __global__ void gelu_map_kernel(const T* __restrict__ x, const T* __restrict__ d
 
 // ------------------------------------------------------------------ LayerNorm over whole maps
 // x [B, M] (M = H*W*C elements of one image, channels-last), weight / bias fp32 [M] in the SAME
-// element order.  partial[(b * parts + p) * 2 + {0, 1}] = sum, sum of squares about the image's
-// first element (pivot: no catastrophic cancellation when |mean| >> std).
+// element order.
+//
+// Forward statistics.  Block p of image b owns the 16-byte vectors p * 256 + t + k * 65536 (t: thread) and goes
+// over them twice (the second time out of L2): their sum about 0 gives the part's first mean m0, the sums of
+// d = x - m0 and d^2 its (mean, M2 = sum (x - mean)^2): partial[(b * parts + p) * 2 + {0, 1}].  The finalize
+// kernel combines the 256 (count, mean, M2) triples (Chan et al.).  Every sum of squares is taken about a mean of
+// the data it covers, so the variance does not depend on where an outlier sits; sums about the image's first
+// element, as this kernel once took, lose var entirely when that element is the outlier
+// (var = E[d^2] - E[d]^2 with both ~ (500 sigma)^2).
 #define MLN_PARTS 256
-template <typename T, bool BWD>
+__host__ __device__ inline long long mapln_part_vectors(long long nvec, int p) {  // vectors part p owns
+    const long long rem = nvec % (MLN_PARTS * 256) - (long long)p * 256;
+    return nvec / (MLN_PARTS * 256) * 256 + (rem < 0 ? 0 : rem > 256 ? 256 : rem);
+}
+DEVI float mapln_block_sum(float v, float* red /*[4]*/) {  // 256 threads; red is not reused by the caller
+    v = wave_sum(v);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+    __syncthreads();
+    return (red[0] + red[1]) + (red[2] + red[3]);
+}
+template <typename T>
+__global__ __launch_bounds__(256) void mapln_stats_kernel(const T* __restrict__ x, float* __restrict__ partial,
+                                                          long long M) {
+    constexpr int V = V16<T>::N;
+    typedef typename V16<T>::raw raw_t;
+    __shared__ float red[3][4];
+    const int b = blockIdx.y, p = blockIdx.x;
+    const T* xb = x + (size_t)b * M;
+    const long long first = ((long long)p * 256 + threadIdx.x) * V, step = (long long)MLN_PARTS * 256 * V;
+    const float n = (float)(mapln_part_vectors(M / V, p) * V);
+    float s = 0.f;
+    for (long long i = first; i < M; i += step) {
+        float f[V];
+        un<T>(*(const raw_t*)(xb + i), f);
+#pragma unroll
+        for (int j = 0; j < V; ++j) s += f[j];
+    }
+    const float m0 = n > 0.f ? mapln_block_sum(s, red[0]) / n : 0.f;  // n is the same for the whole block
+    s = 0.f;
+    float q = 0.f;
+    for (long long i = first; i < M; i += step) {
+        float f[V];
+        un<T>(*(const raw_t*)(xb + i), f);
+#pragma unroll
+        for (int j = 0; j < V; ++j) {
+            const float d = f[j] - m0;
+            s += d;
+            q += d * d;
+        }
+    }
+    s = mapln_block_sum(s, red[1]);
+    q = mapln_block_sum(q, red[2]);
+    if (threadIdx.x == 0) {
+        float* o = partial + ((size_t)b * MLN_PARTS + p) * 2;
+        const float d = n > 0.f ? s / n : 0.f;
+        const float m2 = q - s * d;
+        o[0] = m0 + d;
+        o[1] = m2 > 0.f ? m2 : 0.f;
+    }
+}
+// one wave per image: mean = sum n_p mean_p / M, taken about 0 and then corrected about itself;
+// M2 = sum (M2_p + n_p (mean_p - mean)^2)
+__global__ __launch_bounds__(64) void mapln_stats_finalize_kernel(const float* __restrict__ partial,
+                                                                  float* __restrict__ mean,
+                                                                  float* __restrict__ rstd, long long M, int V,
+                                                                  float eps) {
+    const int b = blockIdx.x, lane = threadIdx.x;
+    const float n = (float)M;
+    float np[MLN_PARTS / 64], mp[MLN_PARTS / 64], a = 0.f;
+#pragma unroll
+    for (int k = 0; k < MLN_PARTS / 64; ++k) {
+        const int p = lane + 64 * k;
+        np[k] = (float)(mapln_part_vectors(M / V, p) * V);
+        mp[k] = partial[((size_t)b * MLN_PARTS + p) * 2];
+        a += np[k] * mp[k];
+    }
+    const float m0 = wave_sum(a) / n;
+    a = 0.f;
+#pragma unroll
+    for (int k = 0; k < MLN_PARTS / 64; ++k) a += np[k] * (mp[k] - m0);
+    const float mu = m0 + wave_sum(a) / n;
+    float q = 0.f;
+#pragma unroll
+    for (int k = 0; k < MLN_PARTS / 64; ++k) {
+        const float e = mp[k] - mu;
+        q += partial[((size_t)b * MLN_PARTS + lane + 64 * k) * 2 + 1] + np[k] * e * e;
+    }
+    q = wave_sum(q);
+    if (lane != 0) return;
+    mean[b] = mu;
+    rstd[b] = rsqrtf(q / n + eps);
+}
+// backward sums: partial[(b * parts + p) * 2 + {0, 1}] = sum g, sum g xhat with g = dy * w
+template <typename T>
 __global__ __launch_bounds__(256) void mapln_reduce_kernel(
     const T* __restrict__ x, const T* __restrict__ dy, const float* __restrict__ w,
     const float* __restrict__ mean, const float* __restrict__ rstd, float* __restrict__ partial,
@@ -148,32 +238,20 @@ __global__ __launch_bounds__(256) void mapln_reduce_kernel(
     __shared__ float red[2][4];
     const int b = blockIdx.y, p = blockIdx.x;
     const T* xb = x + (size_t)b * M;
-    float piv = 0.f, mu = 0.f, rs = 0.f;
-    if (BWD) { mu = mean[b]; rs = rstd[b]; }
-    else { float f[V]; un<T>(*(const raw_t*)xb, f); piv = f[0]; }
+    const float mu = mean[b], rs = rstd[b];
     float s = 0.f, q = 0.f;
     for (long long i = ((long long)p * 256 + threadIdx.x) * V; i < M; i += (long long)MLN_PARTS * 256 * V) {
-        float f[V];
+        float f[V], g[V];
         un<T>(*(const raw_t*)(xb + i), f);
-        if (BWD) {  // s = sum g, q = sum g xhat with g = dy * w
-            float g[V];
-            un<T>(*(const raw_t*)(dy + (size_t)b * M + i), g);
+        un<T>(*(const raw_t*)(dy + (size_t)b * M + i), g);
 #pragma unroll
-            for (int j = 0; j < V; j += 4) {
-                const f32x4 ww = ld4(w + i + j);
+        for (int j = 0; j < V; j += 4) {
+            const f32x4 ww = ld4(w + i + j);
 #pragma unroll
-                for (int k = 0; k < 4; ++k) {
-                    const float gg = g[j + k] * ww[k];
-                    s += gg;
-                    q += gg * ((f[j + k] - mu) * rs);
-                }
-            }
-        } else {
-#pragma unroll
-            for (int j = 0; j < V; ++j) {
-                const float d = f[j] - piv;
-                s += d;
-                q += d * d;
+            for (int k = 0; k < 4; ++k) {
+                const float gg = g[j + k] * ww[k];
+                s += gg;
+                q += gg * ((f[j + k] - mu) * rs);
             }
         }
     }
@@ -188,12 +266,10 @@ __global__ __launch_bounds__(256) void mapln_reduce_kernel(
         o[1] = red[1][0] + red[1][1] + red[1][2] + red[1][3];
     }
 }
-// one wave per image: fold the partials; forward: mean / rstd; backward: the two means of dx
-template <typename T>
+// one wave per image: fold the partials into the two means of dx
 __global__ __launch_bounds__(64) void mapln_finalize_kernel(const float* __restrict__ partial,
-                                                            const T* __restrict__ x, float* __restrict__ o0,
-                                                            float* __restrict__ o1, long long M, float eps,
-                                                            int bwd) {
+                                                            float* __restrict__ o0, float* __restrict__ o1,
+                                                            long long M) {
     const int b = blockIdx.x, lane = threadIdx.x;
     float s = 0.f, q = 0.f;
     for (int p = lane; p < MLN_PARTS; p += 64) {
@@ -204,19 +280,8 @@ __global__ __launch_bounds__(64) void mapln_finalize_kernel(const float* __restr
     q = wave_sum(q);
     if (lane != 0) return;
     const float n = (float)M;
-    if (bwd) {
-        o0[b] = s / n;  // mean(g)
-        o1[b] = q / n;  // mean(g xhat)
-    } else {
-        constexpr int V = V16<T>::N;
-        float f[V];
-        un<T>(*(const typename V16<T>::raw*)(x + (size_t)b * M), f);
-        const float d = s / n;
-        float var = q / n - d * d;
-        var = var > 0.f ? var : 0.f;
-        o0[b] = f[0] + d;
-        o1[b] = rsqrtf(var + eps);
-    }
+    o0[b] = s / n;  // mean(g)
+    o1[b] = q / n;  // mean(g xhat)
 }
 template <typename T>
 __global__ void mapln_apply_kernel(const T* __restrict__ x, const float* __restrict__ w,
@@ -321,19 +386,13 @@ extern "C" int ssl4gie_map_layernorm_fwd(const void* x, const float* w, const fl
             M % 8 == 0 && B <= 65535);
     hipStream_t st = (hipStream_t)stream;
     dim3 grid(MLN_PARTS, B), block(256);
-    if (dtype == SSL4GIE_BF16) {
-        hipLaunchKernelGGL((mapln_reduce_kernel<bf16_t, false>), grid, block, 0, st, (const bf16_t*)x,
-                           (const bf16_t*)nullptr, (const float*)nullptr, (const float*)nullptr,
-                           (const float*)nullptr, workspace, M);
-        hipLaunchKernelGGL(mapln_finalize_kernel<bf16_t>, dim3(B), dim3(64), 0, st, workspace,
-                           (const bf16_t*)x, mean, rstd, M, eps, 0);
-    } else {
-        hipLaunchKernelGGL((mapln_reduce_kernel<float, false>), grid, block, 0, st, (const float*)x,
-                           (const float*)nullptr, (const float*)nullptr, (const float*)nullptr,
-                           (const float*)nullptr, workspace, M);
-        hipLaunchKernelGGL(mapln_finalize_kernel<float>, dim3(B), dim3(64), 0, st, workspace,
-                           (const float*)x, mean, rstd, M, eps, 0);
-    }
+    if (dtype == SSL4GIE_BF16)
+        hipLaunchKernelGGL(mapln_stats_kernel<bf16_t>, grid, block, 0, st, (const bf16_t*)x, workspace, M);
+    else
+        hipLaunchKernelGGL(mapln_stats_kernel<float>, grid, block, 0, st, (const float*)x, workspace, M);
+    LAUNCH_CHECK();
+    hipLaunchKernelGGL(mapln_stats_finalize_kernel, dim3(B), dim3(64), 0, st, workspace, mean, rstd, M, vn(dtype),
+                       eps);
     LAUNCH_CHECK();
     const long long total = (long long)B * M;
     DET_LAUNCH(dtype, mapln_apply_kernel, total / vn(dtype), (const T*)x, w, bias, mean, rstd, (T*)y, M,
@@ -351,17 +410,14 @@ extern "C" int ssl4gie_map_layernorm_bwd(const void* x, const void* dy, const fl
     dim3 grid(MLN_PARTS, B), block(256);
     float* mg = workspace + (size_t)B * MLN_PARTS * 2;
     float* mgx = mg + B;
-    if (dtype == SSL4GIE_BF16) {
-        hipLaunchKernelGGL((mapln_reduce_kernel<bf16_t, true>), grid, block, 0, st, (const bf16_t*)x,
-                           (const bf16_t*)dy, w, mean, rstd, workspace, M);
-        hipLaunchKernelGGL(mapln_finalize_kernel<bf16_t>, dim3(B), dim3(64), 0, st, workspace,
-                           (const bf16_t*)x, mg, mgx, M, 0.f, 1);
-    } else {
-        hipLaunchKernelGGL((mapln_reduce_kernel<float, true>), grid, block, 0, st, (const float*)x,
-                           (const float*)dy, w, mean, rstd, workspace, M);
-        hipLaunchKernelGGL(mapln_finalize_kernel<float>, dim3(B), dim3(64), 0, st, workspace,
-                           (const float*)x, mg, mgx, M, 0.f, 1);
-    }
+    if (dtype == SSL4GIE_BF16)
+        hipLaunchKernelGGL(mapln_reduce_kernel<bf16_t>, grid, block, 0, st, (const bf16_t*)x, (const bf16_t*)dy, w,
+                           mean, rstd, workspace, M);
+    else
+        hipLaunchKernelGGL(mapln_reduce_kernel<float>, grid, block, 0, st, (const float*)x, (const float*)dy, w,
+                           mean, rstd, workspace, M);
+    LAUNCH_CHECK();
+    hipLaunchKernelGGL(mapln_finalize_kernel, dim3(B), dim3(64), 0, st, workspace, mg, mgx, M);
     LAUNCH_CHECK();
     DET_LAUNCH(dtype, mapln_bwd_apply_kernel, M / vn(dtype), (const T*)x, (const T*)dy, w, mean, rstd, mg,
                mgx, (T*)dx, dw, db, accumulate, B, M);
