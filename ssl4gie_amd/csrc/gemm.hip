@@ -995,6 +995,8 @@ extern "C" int ssl4gie_gemm(const ssl4gie_gemm_desc* d, void* workspace, size_t 
     }
     // generic
     REQUIRE(!d->conv && !d->colstats);
+    // the column-sum pass's workspace is checked before anything is launched: a refused call writes nothing
+    REQUIRE(!d->colsum_a || (workspace && workspace_bytes >= ssl4gie_colsum_workspace_bytes(d->K, d->M)));
     GemmArgs g;
     g.M = d->M; g.N = d->N; g.K = d->K; g.batch2 = d->batch2;
     g.A = d->A; g.sAm = d->sAm; g.sAk = d->sAk; g.sAb1 = d->sAb1; g.sAb2 = d->sAb2;
@@ -1014,11 +1016,9 @@ extern "C" int ssl4gie_gemm(const ssl4gie_gemm_desc* d, void* workspace, size_t 
     else
         hipLaunchKernelGGL((gemm_generic_kernel<float, bf16_t>), grid, block, 0, st, g);
     LAUNCH_CHECK();
-    if (d->colsum_a) {
-        REQUIRE(workspace && workspace_bytes >= ssl4gie_colsum_workspace_bytes(d->K, d->M));
+    if (d->colsum_a)
         return ssl4gie_colsum(d->A, d->dtype_ab, d->colsum_a, d->accumulate, (float*)workspace,
                               d->K, d->M, d->sAk, stream);
-    }
     return 0;
 }
 

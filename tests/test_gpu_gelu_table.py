@@ -29,6 +29,18 @@ def test_gelu_table_header_is_current():
     assert np.array_equal(np.array(vals, dtype=np.uint32), gt.table())
 
 
+DGELU_ABS = 8e-3     # absolute bound of the emulated gelu' (output rounding included)
+
+
+def bound_g(ud, yr):
+    """bound of the emulated gelu at pre-activations ud (float64), yr = the exact gelu(ud).
+    g = bf16(u Phi(bf16 u)): Phi's argument is off by <= 2^-8 |u| (first order: u^2 phi(u) 2^-8; 2 covers the
+    curvature in the tail), the output rounding by <= 2^-8 |g|; below Phi = 6e-5 (u < -3.85) the fp16 Phi is
+    subnormal (spacing 6e-8): absolute error <= 3e-8 |u| < 5e-7 there"""
+    phi = np.exp(-0.5 * ud * ud) / np.sqrt(2 * np.pi)
+    return (2.0 * ud * ud * phi + 1.07 * np.abs(yr)) * 2.0 ** -8 + 5e-7  # 1.07: the fp16 Phi adds 2^-12
+
+
 def test_gelu_table_accuracy_cpu():
     """the emulated outputs are bf16-accurate everywhere (output rounding + the argument-rounding term), including
     the clamped ends"""
@@ -42,15 +54,10 @@ def test_gelu_table_accuracy_cpu():
     y = F.gelu(t)
     y.sum().backward()
     yr, dr = y.detach().numpy(), t.grad.numpy()
-    # g = bf16(u Phi(bf16 u)): Phi's argument is off by <= 2^-8 |u| (first order: u^2 phi(u) 2^-8; 2 covers the
-    # curvature in the tail), the output rounding by <= 2^-8 |g|; below Phi = 6e-5 (u < -3.85) the fp16 Phi is
-    # subnormal (spacing 6e-8): absolute error <= 3e-8 |u| < 5e-7 there
-    ud = u.astype(np.float64)
-    phi = np.exp(-0.5 * ud * ud) / np.sqrt(2 * np.pi)
-    bound_g = (2.0 * ud * ud * phi + 1.07 * np.abs(yr)) * 2.0 ** -8 + 5e-7  # 1.07: the fp16 Phi adds 2^-12
-    assert np.all(np.abs(gf - yr) <= bound_g), float(np.max(np.abs(gf - yr) / bound_g))
+    bg = bound_g(u.astype(np.float64), yr)
+    assert np.all(np.abs(gf - yr) <= bg), float(np.max(np.abs(gf - yr) / bg))
     assert np.linalg.norm(gf - yr) / np.linalg.norm(yr) < 2.5e-3
-    assert np.max(np.abs(df - dr)) < 8e-3 and np.linalg.norm(df - dr) / np.linalg.norm(dr) < 3e-3
+    assert np.max(np.abs(df - dr)) < DGELU_ABS and np.linalg.norm(df - dr) / np.linalg.norm(dr) < 3e-3
     # sign and the trivial ends are exact
     assert np.array_equal(g[u > 16], gt.bf16_round_bits(u[u > 16])) and np.all(gf[u < -16] == 0)
     assert np.all(df[u > 16] == 1) and np.all(df[u < -16] == 0)
