@@ -14,7 +14,8 @@
  *   - returns 0 on success, SSL4GIE_EARG (1000) for an invalid argument, otherwise a hipError_t;
  *   - callable from any host thread; the only mutable process-wide settings are the execution
  *     options ssl4gie_set_wgrad_stream / ssl4gie_set_compute_cus and the profiler;
- *   - ssl4gie_abi_version() = 8 (7: before ssl4gie_stem3x3_{tiles,fwd,wgrad_workspace_bytes,wgrad} existed — additions only; 6: before ssl4gie_bn_coef_stats / ssl4gie_bn_apply_bits / ssl4gie_bn_bwd_reduce_bits existed — additions only; 5: before SSL4GIE_PROF_KINDS grew from 5 to 7 — the profiler's arrays; 1: before ssl4gie_gemm_desc gained `colsum_a` / `conv`; 2: before
+ *   - ssl4gie_abi_version() = 9 (8: before ssl4gie_grad_norm_{workspace_bytes,arena} / ssl4gie_grad_scale_arena /
+ *     ssl4gie_adamw_arena_range_ctl existed — additions only; 7: before ssl4gie_stem3x3_{tiles,fwd,wgrad_workspace_bytes,wgrad} existed — additions only; 6: before ssl4gie_bn_coef_stats / ssl4gie_bn_apply_bits / ssl4gie_bn_bwd_reduce_bits existed — additions only; 5: before SSL4GIE_PROF_KINDS grew from 5 to 7 — the profiler's arrays; 1: before ssl4gie_gemm_desc gained `colsum_a` / `conv`; 2: before
  *     ssl4gie_block_bwd's `accumulate` became a flag word and the grouped / deferred weight-gradient
  *     entry points existed; 3: before the direct transport's error word / time-out / all-gather,
  *     ssl4gie_bn_combine_stats and ssl4gie_debug_nt256_stamps existed — additions only; 4: before
@@ -615,6 +616,41 @@ int ssl4gie_adamw_arena_range(float* p, const float* g, float* m, float* v, cons
                               const float* seg_lr, const float* seg_wd, int S, float beta1, float beta2,
                               float eps, int step, long long lo, long long hi, void* lp_bf16,
                               void* stream);
+/* ---- the reference's scaler object over the arena (Models/mae/util/misc.py:251-292,
+ * NativeScalerWithGradNormCount: unscale_ -> get_grad_norm_ / clip_grad_norm_ -> scaler.step; driven from
+ * Models/mae/engine_pretrain.py:39-69 and engine_finetune.py:66 / main_finetune.py --clip_grad).
+ * seg_mask [S]: < 0 skips the segment (frozen, or no gradient this step: its slice of g may hold stale
+ * values and is not read) — the optimizers' seg_lr table has that meaning already and can be passed.
+ * ctl: 4 floats on the device, written by grad_norm_arena and read by the other two:
+ *   ctl[0] L2 norm of inv_scale * g over the active segments      (misc.py:280-292 get_grad_norm_)
+ *   ctl[1] min(1, max_norm / (ctl[0] + 1e-6)), exactly 1 for max_norm <= 0   (torch clip_grad_norm_, misc.py:263)
+ *   ctl[2] 1 if any active element of g is inf or NaN, else 0 — per element, as GradScaler.unscale_'s
+ *          _amp_foreach_non_finite_check_and_unscale_ decides it (misc.py:262,265)
+ *   ctl[3] 0 (reserved)
+ * grad_norm_arena: one pass over g (fixed grid, fixed order, no atomics; four fp32 sums per thread, added
+ *   as doubles before the wave shuffle, fp64 from there on):
+ *   bit-identical from run to run for the same g, tables and n.  workspace: grad_norm_workspace_bytes(),
+ *   8-byte aligned.  n % 4 == 0.
+ * grad_scale_arena: g *= ctl[1] over the active segments — clip_grad_norm_'s side effect on p.grad;
+ *   writes nothing when ctl[1] is exactly 1. */
+size_t ssl4gie_grad_norm_workspace_bytes(void);
+int ssl4gie_grad_norm_arena(const float* g, const long long* seg_start, const float* seg_mask, int S,
+                            float inv_scale, float max_norm, void* workspace, float* ctl, long long n,
+                            void* stream);
+int ssl4gie_grad_scale_arena(float* g, const long long* seg_start, const float* seg_mask, int S,
+                             const float* ctl, long long n, void* stream);
+/* ssl4gie_adamw_arena_range with the control block (misc.py:267 `self._scaler.step(optimizer)` after a
+ * clip): the gradient is ctl[1] * g (g itself is left as it is), and with skip_nonfinite != 0 NOTHING is
+ * written while ctl[2] is set — not p, m, v, nor lp_bf16 — GradScaler.step's skip.  torch does not call
+ * optimizer.step() for a skipped update, so its bias-correction step does not advance either; the host
+ * cannot know without synchronising, so the count of APPLIED updates lives on the device: *applied (one
+ * int, caller-owned, 0 for a fresh optimizer) is read by the kernel (step = *applied + 1), and with
+ * advance != 0 a one-thread launch behind it adds 1 unless the update was skipped.  Pass advance on the
+ * last range of a step only. */
+int ssl4gie_adamw_arena_range_ctl(float* p, const float* g, float* m, float* v, const long long* seg_start,
+                                  const float* seg_lr, const float* seg_wd, int S, float beta1, float beta2,
+                                  float eps, int* applied, long long lo, long long hi, void* lp_bf16,
+                                  const float* ctl, int skip_nonfinite, int advance, void* stream);
 size_t ssl4gie_lars_workspace_bytes(int S);
 int ssl4gie_lars_arena(float* p, const float* g, float* mu, const long long* seg_start,
                        const float* seg_lr, const float* seg_wd, const float* seg_mat, int S,

@@ -21,7 +21,7 @@ if _dbg == "1" or _dbg.startswith("x"):  # "x<tag>": a tools/build_variant.sh ex
 
 # the one copy of the ABI revision on the Python side: build(), the tests and load() compare the
 # library's ssl4gie_abi_version() with it (include/ssl4gie_hip.h documents the history)
-ABI_VERSION = 8
+ABI_VERSION = 9
 
 PROF_KINDS = 7  # SSL4GIE_PROF_KINDS: entries of the launch profiler's arrays
 
@@ -160,6 +160,11 @@ PROTOTYPES = {
     "ssl4gie_adamw_arena": (i32, [vp, vp, vp, vp, vp, vp, vp, i32, f32, f32, f32, i32, i64, vp]),
     "ssl4gie_adamw_arena_lp": (i32, [vp, vp, vp, vp, vp, vp, vp, i32, f32, f32, f32, i32, i64, vp, vp]),
     "ssl4gie_adamw_arena_range": (i32, [vp, vp, vp, vp, vp, vp, vp, i32, f32, f32, f32, i32, i64, i64, vp, vp]),
+    "ssl4gie_adamw_arena_range_ctl": (i32, [vp, vp, vp, vp, vp, vp, vp, i32, f32, f32, f32, vp, i64, i64, vp, vp,
+                                            i32, i32, vp]),
+    "ssl4gie_grad_norm_workspace_bytes": (sz, []),
+    "ssl4gie_grad_norm_arena": (i32, [vp, vp, vp, i32, f32, f32, vp, vp, i64, vp]),
+    "ssl4gie_grad_scale_arena": (i32, [vp, vp, vp, i32, vp, i64, vp]),
     "ssl4gie_lars_workspace_bytes": (sz, [i32]),
     "ssl4gie_lars_arena": (i32, [vp, vp, vp, vp, vp, vp, vp, i32, f32, f32, vp, i64, vp]),
     "ssl4gie_normalize_u8": (i32, [vp, vp, C.POINTER(C.c_float), C.POINTER(C.c_float), i32, i32, i32, vp]),

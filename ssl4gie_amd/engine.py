@@ -36,6 +36,21 @@ def _align(n, a=256):
 # ------------------------------------------------------------------------------------------------
 # parameter / gradient arena
 # ------------------------------------------------------------------------------------------------
+_ARENAS = weakref.WeakSet()  # every live arena: lets code that is handed bare parameters find theirs
+
+
+def arena_of(params):
+    """the live ParamArena that owns EVERY one of `params` (Models/mae/util/misc.py is handed
+    `model.parameters()`, not the model), or None"""
+    params = list(params)
+    if not params:
+        return None
+    for a in list(_ARENAS):
+        if all(a.owns(p) for p in params):
+            return a
+    return None
+
+
 class ParamArena:
     """All parameters of a model as views of ONE flat fp32 buffer (registration order) and all
     gradients as views of a second one: gradient buckets for the data-parallel all-reduce are
@@ -63,6 +78,8 @@ class ParamArena:
                 p.data = v
                 self._index[id(p)] = o
         self.device = dev
+        self._grad_norm_state = None  # optim._norm_pass: segment tables + control block of norms taken over this arena
+        _ARENAS.add(self)
 
     @staticmethod
     def _shaped(flat, p):

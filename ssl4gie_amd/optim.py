@@ -8,6 +8,12 @@ launch chain per parameter group.  Both take torch-style parameter groups, keep 
 (so `lr_sched.adjust_learning_rate` and friends work unchanged) and skip parameters that are frozen
 or have no gradient in this step, as torch does.
 
+`get_grad_norm_`, `clip_grad_norm_` and `ArenaAdamW.step(clip_grad=, skip_nonfinite=)` are the rest of
+the reference's update (`Models/mae/util/misc.py:251-292`, NativeScalerWithGradNormCount: unscale_ ->
+gradient norm / clip -> `scaler.step`): one pass over the gradient arena writes the norm, the clip
+coefficient and the non-finite flag into a small device block, and the scale / AdamW kernels read them
+there — no per-tensor launches and nothing read back by the host.
+
 The north_star leaves the optimizer step host-side (torch); these are the optional fused variants.
 The engine's operand caches are keyed on torch's version counters, which raw-pointer kernels do not
 bump: `step()` advances `engine.weights_epoch` instead.
@@ -19,8 +25,96 @@ import ctypes as C
 import torch
 
 from . import _lib
-from .engine import bump_weights_epoch
+from .engine import ParamArena, bump_weights_epoch
 from .ops import ptr, stream
+
+
+def _adopt_grads(a, params):
+    """a gradient autograd produced with torch ops lives outside the gradient arena the kernels read:
+    move it into the parameter's slice (parallel.DataParallel does the same)"""
+    base, index = a.grad.data_ptr(), a._index
+    for p in params:
+        g = p.grad
+        if g is not None and g.data_ptr() != base + 4 * index[id(p)]:  # (no view is built for one in place)
+            v = a.grad_view(p)
+            v.copy_(g)
+            p.grad = v
+
+
+class _GradNorm:
+    """workspace + control block [norm, clip coefficient, found_inf, 0] of the arena norm kernels; the
+    tensors handed out are VIEWS of the block: the next pass through the same object overwrites them"""
+
+    def __init__(self, dev):
+        L = _lib.load()
+        self.ws = torch.empty(L.ssl4gie_grad_norm_workspace_bytes(), dtype=torch.uint8, device=dev)
+        self.ctl = torch.zeros(4, device=dev)
+        self.norm, self.coef, self.found_inf = self.ctl[0], self.ctl[1], self.ctl[2]
+
+    def run(self, a, start, mask, S, max_norm=None, inv_scale=1.0):
+        _lib.check(_lib.load().ssl4gie_grad_norm_arena(
+            ptr(a.grad), ptr(start), ptr(mask), S, float(inv_scale), float(max_norm or 0.0), ptr(self.ws),
+            ptr(self.ctl), a.numel, stream()), "grad_norm_arena")
+        return self.norm
+
+    def scale(self, a, start, mask, S):
+        _lib.check(_lib.load().ssl4gie_grad_scale_arena(ptr(a.grad), ptr(start), ptr(mask), S, ptr(self.ctl),
+                                                        a.numel, stream()), "grad_scale_arena")
+
+
+def _norm_pass(target, max_norm, parameters=None):
+    """the norm kernel over `target`'s gradients (an _ArenaOptimizer: its own active parameters; a model
+    parallel.DataParallel or a ParamArena: every parameter with a gradient, or those of `parameters`
+    that have one); with max_norm the gradients are then scaled in place.  Returns the _GradNorm."""
+    if isinstance(target, _ArenaOptimizer):
+        a = target._arena()
+        start, mask, _, _, S = target._build_tables(a)
+        gn = target._grad_norm(a)
+    else:
+        from .parallel import before_optimizer_step
+        before_optimizer_step()
+        if not isinstance(target, ParamArena) and not hasattr(target, "arena"):
+            raise TypeError("get_grad_norm_ / clip_grad_norm_ take an engine model, a parallel.DataParallel "
+                            f"or an arena optimizer, not {type(target).__name__}")
+        a = target if isinstance(target, ParamArena) else target.arena()
+        _adopt_grads(a, a.params)
+        chosen = None if parameters is None else {id(p) for p in parameters}
+        active = tuple(p.grad is not None and (chosen is None or id(p) in chosen) for p in a.params)
+        st = a._grad_norm_state
+        if st is None or st["active"] != active:
+            # built when the set of parameters with gradients changes, not per step; pinned + non-blocking:
+            # no host synchronisation
+            host = (torch.tensor(list(a.offsets) + [a.numel], dtype=torch.int64).pin_memory(),
+                    torch.tensor([1.0 if on else -1.0 for on in active]).pin_memory())
+            gn = st["gn"] if st is not None else _GradNorm(a.data.device)
+            st = {"active": active, "host": host, "gn": gn,
+                  "dev": tuple(h.to(a.data.device, non_blocking=True) for h in host)}
+            a._grad_norm_state = st
+        (start, mask), S, gn = st["dev"], len(a.params), st["gn"]
+    gn.run(a, start, mask, S, max_norm)
+    if max_norm is not None:
+        gn.scale(a, start, mask, S)
+    return gn
+
+
+@torch.no_grad()
+def get_grad_norm_(model_or_optimizer):
+    """L2 norm of all gradients (the reference's `misc.get_grad_norm_`, `misc.py:280-292`, norm_type 2)
+    as a 0-d device tensor: ONE pass over the gradient arena, bit-identical from run to run, no host
+    synchronisation.  An open data-parallel pass is closed first (the norm is that of the reduced
+    gradients) and gradients living outside the arena are adopted.  The result is a view of a device
+    block the next call overwrites: read or copy it before calling again."""
+    return _norm_pass(model_or_optimizer, None).norm
+
+
+@torch.no_grad()
+def clip_grad_norm_(model_or_optimizer, max_norm):
+    """`torch.nn.utils.clip_grad_norm_(parameters, max_norm)` over the arena: gradients are multiplied in
+    place by min(1, max_norm / (norm + 1e-6)) (nothing is written when that is 1); returns the norm
+    BEFORE clipping as a 0-d device tensor (same caveats as `get_grad_norm_`).  One difference from
+    torch: max_norm <= 0 means "no clipping" (coefficient exactly 1, the kernels' convention), where
+    torch would scale the gradients to zero."""
+    return _norm_pass(model_or_optimizer, float(max_norm)).norm
 
 
 class _ArenaOptimizer:
@@ -38,6 +132,7 @@ class _ArenaOptimizer:
         self.defaults = dict(defaults)
         self._tables_key = None
         self._hyper = None
+        self._gn = None            # _GradNorm of get_grad_norm_ / clip_grad_norm_ / step(clip_grad=) through self
         self.step_count = 0
 
     # ------------------------------------------------------------------ segment tables
@@ -49,15 +144,13 @@ class _ArenaOptimizer:
         a = self.model.arena()
         own = [p for g in self.param_groups for p in g["params"]]
         assert all(a.owns(p) for p in own), "every optimised parameter must live in the model's arena"
-        # a gradient autograd produced with torch ops lives outside the gradient arena the kernels
-        # read: move it into the parameter's slice (parallel.DataParallel does the same)
-        for p in own:
-            if p.grad is not None:
-                v = a.grad_view(p)
-                if p.grad.data_ptr() != v.data_ptr():
-                    v.copy_(p.grad)
-                    p.grad = v
+        _adopt_grads(a, own)
         return a
+
+    def _grad_norm(self, a):
+        if self._gn is None or self._gn.ctl.device != a.data.device:
+            self._gn = _GradNorm(a.data.device)
+        return self._gn
 
     def _build_tables(self, a):
         """device tables [start | lr | wd | is_matrix] per arena parameter.  The layout (start, mat)
@@ -78,8 +171,12 @@ class _ArenaOptimizer:
             pin = dev.type == "cuda"
             start = torch.tensor(list(a.offsets) + [a.numel], dtype=torch.int64)
             mat = torch.tensor([1.0 if (active[i] and p.ndim > 1) else 0.0 for i, p in enumerate(a.params)])
+            if pin:  # kept alive in _host_layout: the copies below do not wait for the host
+                start, mat = start.pin_memory(), mat.pin_memory()
+            self._host_layout = (start, mat)
             self._host = (torch.empty(n, pin_memory=pin), torch.empty(n, pin_memory=pin))
-            self._dev = [start.to(dev), torch.empty(n, device=dev), torch.empty(n, device=dev), mat.to(dev)]
+            self._dev = [start.to(dev, non_blocking=pin), torch.empty(n, device=dev), torch.empty(n, device=dev),
+                         mat.to(dev, non_blocking=pin)]
             self._gidx = [group_of.get(id(p), -1) if active[i] else -1 for i, p in enumerate(a.params)]
             self._tables_key, self._hyper = layout_key, None
         if hyper != self._hyper:
@@ -144,10 +241,27 @@ class ArenaAdamW(_ArenaOptimizer):
     gradient all-reduce has to come first).  Measured on the MAE ViT-B step it does NOT pay (24.1 vs
     23.9-24.0 ms, same box): the HBM-bound update competes with the backward GEMMs' operand traffic for
     about what it hides.  Kept, off by default, because the result is bitwise the plain step's
-    (tests/test_gpu_optim.py) and a model with more idle CUs in its backward may differ."""
+    (tests/test_gpu_optim.py) and a model with more idle CUs in its backward may differ.
+
+    `step(clip_grad=None, skip_nonfinite=False)`: with either option the step is the reference scaler's
+    update (`Models/mae/util/misc.py:259-268`) in three launches: the arena norm pass, the AdamW kernel
+    reading its control block, and a one-thread counter update.  clip_grad: the update uses
+    min(1, clip_grad / (norm + 1e-6)) * g, torch's `clip_grad_norm_` coefficient.  skip_nonfinite: if
+    any active gradient element is inf or NaN NOTHING is updated (parameters, moments, bf16 copies) and
+    the bias-correction step does not advance — `GradScaler.step`'s skip, decided on the device.
+    `last_grad_norm` / `last_found_inf` are 0-d device tensors (views the next such step overwrites).
+    On this fused path `p.grad` is left UNSCALED (torch's clip_grad_norm_ scales it in place; use
+    `optim.clip_grad_norm_` + `step()` where the clipped gradient itself is needed) — the reference
+    loop zeroes the gradients straight after the step.  Once such a step has been taken the count of
+    applied updates lives on the device; `step_count` / `state_dict()` read it back (a synchronisation,
+    at checkpoint time only).  Both options need every gradient before the first update: together with
+    overlap_backward=True they raise ValueError."""
 
     def __init__(self, model, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2,
                  overlap_backward=False):
+        self._host_steps = 0       # count of applied updates while it lives on the host ...
+        self._dev_steps = None     # ... and once a step(clip_grad= / skip_nonfinite=) moved it to the device
+        self._ctl_plain = None     # control block [0, 1, 0, 0] of a plain step() behind the device-side count
         super().__init__(model, params, dict(lr=lr, weight_decay=weight_decay))
         self.betas, self.eps = betas, eps
         self.exp_avg = self.exp_avg_sq = None
@@ -158,9 +272,23 @@ class ArenaAdamW(_ArenaOptimizer):
         self._seen = {}            # id(p) -> tracker calls in the current pass
         self._hooked = False
         self._lp = None
+        self.last_grad_norm = self.last_found_inf = None
 
     def _state_buffers(self):
         return {"exp_avg": self.exp_avg, "exp_avg_sq": self.exp_avg_sq}
+
+    # ------------------------------------------------------------------ count of applied updates
+    # host-side until the first step(clip_grad= / skip_nonfinite=); then ONE int32 on the device, which
+    # the _ctl kernel reads and advances (a skipped update must not advance the bias corrections)
+    @property
+    def step_count(self):
+        return self._host_steps if self._dev_steps is None else int(self._dev_steps.item())
+
+    @step_count.setter
+    def step_count(self, n):
+        self._host_steps = int(n)
+        if self._dev_steps is not None:
+            self._dev_steps.fill_(int(n))
 
     # ------------------------------------------------------------------ in-backward updates
     def _hook(self):
@@ -233,8 +361,35 @@ class ArenaAdamW(_ArenaOptimizer):
         assert self._tables_key == saved and group_of is not None
         return tuple(self._dev) + (n,)
 
+    def _step_ctl(self, a, clip_grad, skip_nonfinite):
+        """norm pass (when an option asks for it) + the AdamW kernel behind the control block"""
+        start, lr, wd, _, S = self._tables
+        dev = a.data.device
+        if self._dev_steps is None:
+            self._dev_steps = torch.full((1,), self._host_steps, dtype=torch.int32, device=dev)
+        elif self._dev_steps.device != dev:  # the model moved: the count follows it (a copy between devices)
+            self._dev_steps = self._dev_steps.to(dev)
+        if clip_grad is not None or skip_nonfinite:
+            gn = self._grad_norm(a)
+            gn.run(a, start, lr, S, clip_grad)
+            self.last_grad_norm, self.last_found_inf = gn.norm, gn.found_inf
+            ctl = gn.ctl
+        else:  # a plain step() after the counter moved to the device: coefficient 1, nothing found
+            if self._ctl_plain is None or self._ctl_plain.device != dev:
+                self._ctl_plain = torch.zeros(4, device=dev)
+                self._ctl_plain[1] = 1.0
+            ctl = self._ctl_plain
+        _lib.check(_lib.load().ssl4gie_adamw_arena_range_ctl(
+            ptr(a.data), ptr(a.grad), ptr(self.exp_avg), ptr(self.exp_avg_sq), ptr(start), ptr(lr), ptr(wd), S,
+            self.betas[0], self.betas[1], self.eps, ptr(self._dev_steps), 0, a.numel, ptr(self._lp), ptr(ctl),
+            int(bool(skip_nonfinite)), 1, stream()), "adamw_arena_range_ctl")
+
     @torch.no_grad()
-    def step(self):
+    def step(self, clip_grad=None, skip_nonfinite=False):
+        ctl_path = clip_grad is not None or skip_nonfinite
+        if ctl_path and self._overlap:
+            raise ValueError("ArenaAdamW(overlap_backward=True) applies updates while the backward pass is "
+                             "still running; clip_grad / skip_nonfinite need the norm of EVERY gradient first")
         a = self._arena()
         if self.exp_avg is None or self.exp_avg.numel() != a.numel:
             self.exp_avg = torch.zeros_like(a.data)
@@ -248,15 +403,19 @@ class ArenaAdamW(_ArenaOptimizer):
         # the kernels also write the bf16 operand copy of what they update into the arena's flat shadow
         # (engine.ParamArena.lp_views): the next forward then only needs the batched transposes
         self._lp = a.lp_flat_for_update() if a.data.is_cuda else None
-        st = stream()
-        pos = 0
-        for lo, hi in sorted(self._done) + [(a.numel, a.numel)]:  # the complement of the ranges done
-            if lo > pos:
-                self._launch(a, pos, lo, st)
-            pos = max(pos, hi)
-        if self._done:
-            torch.cuda.current_stream(a.data.device).wait_stream(self._stream)
-        self.step_count += 1
+        if ctl_path or self._dev_steps is not None:
+            assert not self._done, "in-backward updates and the device-side step count do not mix"
+            self._step_ctl(a, clip_grad, skip_nonfinite)
+        else:
+            st = stream()
+            pos = 0
+            for lo, hi in sorted(self._done) + [(a.numel, a.numel)]:  # the complement of the ranges done
+                if lo > pos:
+                    self._launch(a, pos, lo, st)
+                pos = max(pos, hi)
+            if self._done:
+                torch.cuda.current_stream(a.data.device).wait_stream(self._stream)
+            self.step_count += 1
         self._done, self._seen, self._tables = [], {}, None
         bump_weights_epoch(touched=[p for g in self.param_groups for p in g["params"]])
         if self._lp is not None:
