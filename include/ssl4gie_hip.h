@@ -14,7 +14,8 @@
  *   - returns 0 on success, SSL4GIE_EARG (1000) for an invalid argument, otherwise a hipError_t;
  *   - callable from any host thread; the only mutable process-wide settings are the execution
  *     options ssl4gie_set_wgrad_stream / ssl4gie_set_compute_cus and the profiler;
- *   - ssl4gie_abi_version() = 9 (8: before ssl4gie_grad_norm_{workspace_bytes,arena} / ssl4gie_grad_scale_arena /
+ *   - ssl4gie_abi_version() = 10 (9: before ssl4gie_infonce_{workspace_bytes,loss} / ssl4gie_cross_entropy{_workspace_bytes,} /
+ *     ssl4gie_bt_loss{_workspace_bytes,,_grad} existed — additions only; 8: before ssl4gie_grad_norm_{workspace_bytes,arena} / ssl4gie_grad_scale_arena /
  *     ssl4gie_adamw_arena_range_ctl existed — additions only; 7: before ssl4gie_stem3x3_{tiles,fwd,wgrad_workspace_bytes,wgrad} existed — additions only; 6: before ssl4gie_bn_coef_stats / ssl4gie_bn_apply_bits / ssl4gie_bn_bwd_reduce_bits existed — additions only; 5: before SSL4GIE_PROF_KINDS grew from 5 to 7 — the profiler's arrays; 1: before ssl4gie_gemm_desc gained `colsum_a` / `conv`; 2: before
  *     ssl4gie_block_bwd's `accumulate` became a flag word and the grouped / deferred weight-gradient
  *     entry points existed; 3: before the direct transport's error word / time-out / all-gather,
@@ -709,6 +710,40 @@ int ssl4gie_ssi_loss(const float* pred, const float* target, float* loss, float*
 size_t ssl4gie_dice_loss_workspace_bytes(int B);
 int ssl4gie_dice_loss(const float* logits, const float* target, float* loss, float* dlogits, int B,
                       long long n, float smooth, void* workspace, void* stream);
+
+/* ---------------------------------------------------------------- loss heads of the pretraining / classification steps (ABI 10)
+ * fp32 arithmetic, two-stage reductions in a fixed order (bit-identical from run to run), no atomics.
+ *
+ * InfoNCE of MoCo-v3 (Models/moco_v3/moco/builder.py:63-73, `MoCo.contrastive_loss`): q fp32 [N, C] (queries, the only
+ * operand with a gradient), k fp32 [M, C] (the keys of all ranks, already gathered); row i's label is
+ * label_offset + i.  q^ = q / max(||q||, 1e-12), k^ likewise, logits = q^ k^T / T (fp32 FMA chains, never stored),
+ * loss = 2 T mean_i (logsumexp_j logits_ij - logits_i,label); dq (may be NULL) = dloss/dq through the normalisation.
+ * The softmax is online (running maximum subtracted before every exp).  At most four launches.
+ * SSL4GIE_EARG for N, M, C < 1, C > 1024, T <= 0, label_offset < 0 or label_offset + N > M.
+ *
+ * nn.CrossEntropyLoss(weight), mean reduction (Classification/train_classification.py:278): logits fp32 [B, C],
+ * target int64 [B], weight fp32 [C] or NULL (all ones): loss = sum_i w[t_i] (lse_i - x_i,t_i) / sum_i w[t_i],
+ * dlogits (may be NULL) = w[t_i] (p_ij - [j == t_i]) / sum w[t].  sum w[t] = 0 gives NaN, as torch does; a target
+ * outside [0, C) is never used as an index: the loss and that row of dlogits are NaN.  Two launches.
+ *
+ * Barlow Twins loss terms on the reduced D x D fp32 correlation matrix c (ssl4gie_amd/Models/barlow_twins,
+ * `cross_corr_loss_terms` and the operand casts of `CrossCorrLossFn.backward`):
+ *   bt_loss       loss = sum_i (c_ii - 1)^2 + lambd sum_{i != j} c_ij^2 in one read of c (off-diagonal terms summed
+ *                 directly; fp32 block partials, finished in fp64);
+ *   bt_loss_grad  one read of c, both GEMM operands of the backward: w[i][j] = round_dtype(dc_ij s), wt[j][i] =
+ *                 w[i][j], s = *scale (device scalar), dc_ij = c_ij (float)(2 lambd) off the diagonal and
+ *                 2 (c_ii - 1) on it; every product rounded to fp32 in this order, so the operands equal the torch
+ *                 ops' bit for bit.  dtype = SSL4GIE_BF16 | SSL4GIE_F32.  One launch. */
+size_t ssl4gie_infonce_workspace_bytes(int N, int M, int C);
+int ssl4gie_infonce_loss(const float* q, const float* k, float* loss, float* dq, int N, int M, int C, float T,
+                         int label_offset, void* workspace, void* stream);
+size_t ssl4gie_cross_entropy_workspace_bytes(int B, int C);
+int ssl4gie_cross_entropy(const float* logits, const long long* target, const float* weight, float* loss,
+                          float* dlogits, int B, int C, void* workspace, void* stream);
+size_t ssl4gie_bt_loss_workspace_bytes(int D);
+int ssl4gie_bt_loss(const float* c, float* loss, int D, float lambd, void* workspace, void* stream);
+int ssl4gie_bt_loss_grad(const float* c, const float* scale, void* w, void* wt, int dtype, int D, float lambd,
+                         void* stream);
 
 /* ---------------------------------------------------------------- direct xGMI gradient all-reduce
  * replaces the NCCL bucket all-reduce of DistributedDataParallel (Models/mae/main_pretrain.py:175,

@@ -52,8 +52,17 @@ def exchange_cross_corr(c, group=None):
     return c
 
 
+def _fused_bt_loss(c):
+    import os
+    return (c.is_cuda and os.environ.get("SSL4GIE_FUSED_BT_LOSS", "0") == "1"
+            and os.environ.get("SSL4GIE_FUSED_LOSS", "1") != "0")
+
+
 class CrossCorrLossFn(torch.autograd.Function):
-    """loss(zn1, zn2) with zn* [N_local, D] already batch-normalised (operand dtype)."""
+    """loss(zn1, zn2) with zn* [N_local, D] already batch-normalised (operand dtype).
+    SSL4GIE_FUSED_BT_LOSS=1: the loss is one read of c and the two operands of the backward GEMMs one more
+    (csrc/loss_ops.hip: ssl4gie_bt_loss / ssl4gie_bt_loss_grad) instead of ~ten elementwise passes over D x D;
+    the operands are bit-identical to the torch ops'."""
 
     @staticmethod
     def forward(ctx, zn1, zn2, lambd, n_global, group):
@@ -61,20 +70,28 @@ class CrossCorrLossFn(torch.autograd.Function):
         c = ops.linear_bwd_weight(zn1, zn2)  # fp32 [D, D] = zn1^T zn2 (split-K TN GEMM over the batch)
         c.div_(n_global)
         exchange_cross_corr(c, group)
+        ctx.n_global = n_global
+        ctx.fused = _fused_bt_loss(c)
+        if ctx.fused:
+            ctx.lambd = float(lambd)
+            ctx.save_for_backward(zn1, zn2, c)
+            return ops.bt_loss(c, ctx.lambd)
         loss, dc = cross_corr_loss_terms(c, lambd)
         ctx.save_for_backward(zn1, zn2, dc)
-        ctx.n_global = n_global
         return loss
 
     @staticmethod
     def backward(ctx, g):
         zn1, zn2, dc = ctx.saved_tensors
         dt = zn1.dtype
-        dc = dc * (g / ctx.n_global)  # dL/d(zn1^T zn2); every rank's local product sees the same dL/dc
-        if dt == torch.float32:
-            w, wt = dc, dc.t().contiguous()
+        if ctx.fused:
+            w, wt = ops.bt_loss_grad(dc, g / ctx.n_global, dt, ctx.lambd)  # `dc` holds c itself here
         else:
-            w, wt = ops.cast(dc, dt), ops.cast_transpose(dc, dt)
+            dc = dc * (g / ctx.n_global)  # dL/d(zn1^T zn2); every rank's local product sees the same dL/dc
+            if dt == torch.float32:
+                w, wt = dc, dc.t().contiguous()
+            else:
+                w, wt = ops.cast(dc, dt), ops.cast_transpose(dc, dt)
         dzn1 = ops.linear_fwd(zn2, w)   # [N, D_i] = sum_j zn2[n, j] dc[i, j]
         dzn2 = ops.linear_fwd(zn1, wt)  # [N, D_j] = sum_i zn1[n, i] dc[i, j]
         return dzn1, dzn2, None, None, None

@@ -10,7 +10,8 @@ What runs where:
   * the momentum update (:57-61) is ONE axpby kernel over the parameter arena: base and momentum
     encoders are registered back to back with identical layouts, so `zip(parameters)` is a slice pair;
   * the InfoNCE loss (:63-73: normalise, all_gather of the keys, [N, N*W] logits, cross entropy x 2T)
-    stays host-side torch on [N, 256] tensors — "loss reductions" in BASELINE.json's north_star.
+    is host-side torch on [N, 256] tensors by default — "loss reductions" in BASELINE.json's north_star;
+    SSL4GIE_FUSED_INFONCE=1 runs it as the fused device kernels of csrc/loss_ops.hip (`losses.info_nce`).
 """
 from __future__ import annotations
 
@@ -82,17 +83,23 @@ class MoCo(EngineModule):
 
     def contrastive_loss(self, q, k):
         import torch.distributed as dist
-        q = nn.functional.normalize(q, dim=1)
-        k = nn.functional.normalize(k, dim=1)
+        import os
+        from ....losses import info_nce, info_nce_normalized
         rank, world = 0, 1
         if dist.is_available() and dist.is_initialized():
             rank, world = dist.get_rank(), dist.get_world_size()
+        n = q.shape[0]  # batch size per GPU
+        if (q.is_cuda and os.environ.get("SSL4GIE_FUSED_INFONCE", "0") == "1"
+                and os.environ.get("SSL4GIE_FUSED_LOSS", "1") != "0"):
+            # csrc/loss_ops.hip: the kernels normalise the rows themselves, so the raw keys are gathered
+            if world > 1:
+                k = concat_all_gather(k)
+            return info_nce(q, k.detach(), self.T, n * rank)
+        q = nn.functional.normalize(q, dim=1)
+        k = nn.functional.normalize(k, dim=1)
         if world > 1:
             k = concat_all_gather(k)
-        logits = (MatmulNTFn.apply(q, k) if q.is_cuda else q @ k.t()) / self.T  # einsum('nc,mc->nm') of builder.py:83
-        n = logits.shape[0]  # batch size per GPU
-        labels = torch.arange(n, dtype=torch.long, device=logits.device) + n * rank
-        return nn.functional.cross_entropy(logits, labels) * (2 * self.T)
+        return info_nce_normalized(q, k, self.T, n * rank)
 
     def encode(self, enc, x):
         raise NotImplementedError

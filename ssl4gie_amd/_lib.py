@@ -21,7 +21,7 @@ if _dbg == "1" or _dbg.startswith("x"):  # "x<tag>": a tools/build_variant.sh ex
 
 # the one copy of the ABI revision on the Python side: build(), the tests and load() compare the
 # library's ssl4gie_abi_version() with it (include/ssl4gie_hip.h documents the history)
-ABI_VERSION = 9
+ABI_VERSION = 10
 
 PROF_KINDS = 7  # SSL4GIE_PROF_KINDS: entries of the launch profiler's arrays
 
@@ -188,6 +188,13 @@ PROTOTYPES = {
     "ssl4gie_ssi_loss": (i32, [vp, vp, vp, vp, i32, i32, i32, f32, i32, vp, vp]),
     "ssl4gie_dice_loss_workspace_bytes": (sz, [i32]),
     "ssl4gie_dice_loss": (i32, [vp, vp, vp, vp, i32, i64, f32, vp, vp]),
+    "ssl4gie_infonce_workspace_bytes": (sz, [i32, i32, i32]),
+    "ssl4gie_infonce_loss": (i32, [vp, vp, vp, vp, i32, i32, i32, f32, i32, vp, vp]),
+    "ssl4gie_cross_entropy_workspace_bytes": (sz, [i32, i32]),
+    "ssl4gie_cross_entropy": (i32, [vp, vp, vp, vp, vp, i32, i32, vp, vp]),
+    "ssl4gie_bt_loss_workspace_bytes": (sz, [i32]),
+    "ssl4gie_bt_loss": (i32, [vp, vp, i32, f32, vp, vp]),
+    "ssl4gie_bt_loss_grad": (i32, [vp, vp, vp, vp, i32, i32, f32, vp]),
     "ssl4gie_allreduce_direct_blob_bytes": (sz, []),
     "ssl4gie_allreduce_direct_init": (i32, [i32, i32, sz, vp, C.POINTER(vp)]),
     "ssl4gie_allreduce_direct_connect": (i32, [vp, vp]),

@@ -3,7 +3,9 @@
 the torch formulations below are that path, and the parity reference.  On the HIP device the two
 module classes run fused device kernels instead (csrc/loss_ops.hip — value and
 gradient in five / three launches instead of ~100 small ones); SSL4GIE_FUSED_LOSS=0 or CPU tensors
-select the torch formulation.  Same call signature and numerics as the reference's
+select the torch formulation.  The same file holds the loss heads of the other workloads: `CrossEntropyLoss`
+(the classification finetune's weighted cross-entropy, `Classification/train_classification.py:278`) and
+`info_nce` (MoCo-v3's contrastive loss, `Models/moco_v3/moco/builder.py:63-73`).  Same call signature and numerics as the reference's
 `Depth_estimation/Metrics/losses.py` (scale-and-shift-invariant depth loss, :120-146): per-image
 closed-form 2x2 least squares for (scale, shift) on the valid pixels (:5-25), masked MSE / (2M)
 (:51-57) and alpha x a 4-scale masked gradient L1 (:60-77, :104-117), batch-based reduction
@@ -154,3 +156,96 @@ class SoftDiceLoss(torch.nn.Module):
         m2 = targets.view(num, -1)
         score = 2.0 * ((m1 * m2).sum(1) + self.smooth) / ((m1 * m1).sum(1) + (m2 * m2).sum(1) + self.smooth)
         return 1 - score.sum() / num
+
+
+class _CeFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, logits, target, weight):
+        from . import _lib
+        from .ops import ptr, stream
+        L = _lib.load()
+        x = logits.contiguous().float()
+        t = target.contiguous()
+        w = None if weight is None else weight.to(device=x.device, dtype=torch.float32).contiguous()
+        B, C = x.shape
+        ws = torch.empty(L.ssl4gie_cross_entropy_workspace_bytes(B, C), dtype=torch.uint8, device=x.device)
+        loss = torch.empty((), dtype=torch.float32, device=x.device)
+        dx = torch.empty_like(x)
+        _lib.check(L.ssl4gie_cross_entropy(ptr(x), ptr(t), ptr(w), ptr(loss), ptr(dx), B, C, ptr(ws), stream()),
+                   "cross_entropy")
+        ctx.save_for_backward(dx)
+        ctx.dtype = logits.dtype
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        (dx,) = ctx.saved_tensors
+        return (dx * g).to(ctx.dtype), None, None
+
+
+class CrossEntropyLoss(nn.Module):
+    """`nn.CrossEntropyLoss(weight)` of the classification finetune (`train_classification.py:278`), mean
+    reduction: one fused value-and-gradient kernel pair for fp32 / bf16 logits [B, C] with int64 class targets on
+    the device; the torch formulation for CPU tensors, SSL4GIE_FUSED_LOSS=0 and every other input rank."""
+
+    def __init__(self, weight=None):
+        super().__init__()
+        self.register_buffer("weight", None if weight is None else torch.as_tensor(weight, dtype=torch.float32))
+
+    def forward(self, logits, target):
+        if (_fused_ok(logits, target) and logits.dim() == 2 and target.dim() == 1
+                and target.dtype == torch.int64 and logits.dtype in (torch.float32, torch.bfloat16)):
+            return _CeFn.apply(logits, target, self.weight)
+        w = self.weight
+        if w is not None and w.dtype != logits.dtype:
+            w = w.to(logits.dtype)
+        return nn.functional.cross_entropy(logits, target, weight=w)
+
+
+class _InfoNceFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, q, k_all, T, label_offset):
+        from . import _lib
+        from .ops import ptr, stream
+        L = _lib.load()
+        qf = q.contiguous().float()
+        kf = k_all.detach().contiguous().float()
+        (N, C), M = qf.shape, kf.shape[0]
+        ws = torch.empty(L.ssl4gie_infonce_workspace_bytes(N, M, C), dtype=torch.uint8, device=qf.device)
+        loss = torch.empty((), dtype=torch.float32, device=qf.device)
+        dq = torch.empty_like(qf)
+        _lib.check(L.ssl4gie_infonce_loss(ptr(qf), ptr(kf), ptr(loss), ptr(dq), N, M, C, float(T), int(label_offset),
+                                          ptr(ws), stream()), "infonce_loss")
+        ctx.save_for_backward(dq)
+        ctx.dtype = q.dtype
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        (dq,) = ctx.saved_tensors
+        return (dq * g).to(ctx.dtype), None, None, None
+
+
+def info_nce_normalized(q, k_all, T, label_offset=0):
+    """the tail of the reference's `MoCo.contrastive_loss` (builder.py:68-73) on rows that are already
+    L2-normalised: logits = q k_all^T / T, labels = arange(n) + label_offset, cross entropy x 2T (torch ops)"""
+    if q.is_cuda:
+        from .engine import MatmulNTFn
+        logits = MatmulNTFn.apply(q, k_all) / T  # einsum('nc,mc->nm') of builder.py:83
+    else:
+        logits = q @ k_all.t() / T
+    n = logits.shape[0]  # batch size per GPU
+    labels = torch.arange(n, dtype=torch.long, device=logits.device) + label_offset
+    return nn.functional.cross_entropy(logits, labels) * (2 * T)
+
+
+def info_nce(q, k_all, T, label_offset=0):
+    """MoCo-v3's InfoNCE (`builder.py:63-73`): q [N, C] queries, k_all [M, C] the gathered keys of all ranks (no
+    gradient), row i's positive key is `label_offset + i`.  On the device one fused kernel chain (row norms, online
+    softmax over key chunks, dq through the normalisation; the [N, M] logits never reach memory); the torch
+    formulation for CPU tensors, keys that require a gradient, C > 1024 or SSL4GIE_FUSED_LOSS=0."""
+    if (_fused_ok(q, k_all) and q.dim() == 2 and k_all.dim() == 2 and not k_all.requires_grad
+            and q.shape[1] == k_all.shape[1] and q.shape[1] <= 1024):
+        return _InfoNceFn.apply(q, k_all, T, label_offset)
+    return info_nce_normalized(nn.functional.normalize(q, dim=1), nn.functional.normalize(k_all, dim=1), T,
+                               label_offset)

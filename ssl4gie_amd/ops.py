@@ -401,6 +401,34 @@ def cast_transpose(src2d, dtype, out=None):
     return out
 
 
+def bt_loss(c, lambd):
+    """Barlow Twins loss of the fp32 [D, D] correlation matrix: sum_i (c_ii - 1)^2 + lambd sum_{i != j} c_ij^2"""
+    _dev(c)
+    _f32(c)
+    D = c.shape[0]
+    assert c.shape == (D, D)
+    L = _lib.load()
+    ws = torch.empty(L.ssl4gie_bt_loss_workspace_bytes(D), dtype=torch.uint8, device=c.device)
+    loss = torch.empty((), dtype=torch.float32, device=c.device)
+    _lib.check(L.ssl4gie_bt_loss(ptr(c), ptr(loss), D, float(lambd), ptr(ws), stream()), "bt_loss")
+    return loss
+
+
+def bt_loss_grad(c, scale, dtype, lambd):
+    """(w, wt): dL/dc of the Barlow Twins loss times the device scalar `scale`, rounded to `dtype`, and its
+    transpose — the two operands of the backward GEMMs from one read of c"""
+    _dev(c)
+    _f32(c)
+    D = c.shape[0]
+    assert c.shape == (D, D)
+    scale = scale.to(device=c.device, dtype=torch.float32).reshape(()).contiguous()
+    w = torch.empty(D, D, dtype=dtype, device=c.device)
+    wt = torch.empty(D, D, dtype=dtype, device=c.device)
+    _lib.check(_lib.load().ssl4gie_bt_loss_grad(ptr(c), ptr(scale), ptr(w), ptr(wt), code(dtype), D, float(lambd),
+                                                stream()), "bt_loss_grad")
+    return w, wt
+
+
 def add_cast(a, b=None, want_f32=True, lp_dtype=None):
     """out = a + b on the fp32 gradient stream; optionally also its operand-type copy."""
     _dev(a, b)
