@@ -14,12 +14,13 @@
  *   - returns 0 on success, SSL4GIE_EARG (1000) for an invalid argument, otherwise a hipError_t;
  *   - callable from any host thread; the only mutable process-wide settings are the execution
  *     options ssl4gie_set_wgrad_stream / ssl4gie_set_compute_cus and the profiler;
- *   - ssl4gie_abi_version() = 10 (9: before ssl4gie_infonce_{workspace_bytes,loss} / ssl4gie_cross_entropy{_workspace_bytes,} /
+ *   - ssl4gie_abi_version() = 11 (10: before the diagnostics entry point that read the 256x256 NT kernel's in-kernel
+ *     time stamps was REMOVED with the debug build of the library — the one removal in this history; 9: before ssl4gie_infonce_{workspace_bytes,loss} / ssl4gie_cross_entropy{_workspace_bytes,} /
  *     ssl4gie_bt_loss{_workspace_bytes,,_grad} existed — additions only; 8: before ssl4gie_grad_norm_{workspace_bytes,arena} / ssl4gie_grad_scale_arena /
  *     ssl4gie_adamw_arena_range_ctl existed — additions only; 7: before ssl4gie_stem3x3_{tiles,fwd,wgrad_workspace_bytes,wgrad} existed — additions only; 6: before ssl4gie_bn_coef_stats / ssl4gie_bn_apply_bits / ssl4gie_bn_bwd_reduce_bits existed — additions only; 5: before SSL4GIE_PROF_KINDS grew from 5 to 7 — the profiler's arrays; 1: before ssl4gie_gemm_desc gained `colsum_a` / `conv`; 2: before
  *     ssl4gie_block_bwd's `accumulate` became a flag word and the grouped / deferred weight-gradient
  *     entry points existed; 3: before the direct transport's error word / time-out / all-gather,
- *     ssl4gie_bn_combine_stats and ssl4gie_debug_nt256_stamps existed — additions only; 4: before
+ *     ssl4gie_bn_combine_stats and that time-stamp reader existed — additions only; 4: before
  *     ssl4gie_gemm_desc gained `scale` / `relu` (appended; SSL4GIE_EPI_AFFINE_AUX_RELU and the
  *     statistics-only product with C == NULL) and ssl4gie_bn_bwd_xmask / ssl4gie_bn_coef_partials / ssl4gie_bn_maxpool3x3s2_fwd /
  *     ssl4gie_conv3x3_direct_{fwd,wgrad}_affine / ssl4gie_bn_fwd_partials_bits / ssl4gie_bn_bwd_bits /
@@ -767,10 +768,6 @@ int ssl4gie_bt_loss_grad(const float* c, const float* scale, void* w, void* wt, 
  *   destroy  unmaps / frees (after the streams that used the handle have drained).
  * init fails (hipError_t) when fine-grained device memory is not available: peer stores and in-kernel
  * flag polls are not coherent on coarse-grained memory, so there is no fallback to it. */
-/* Diagnostics: the in-kernel time stamps of the 256x256 NT kernel (SSL4GIE_NT256_NOEPI=4; csrc/gemm_nt256.hip):
- * [16 workgroups][16 tiles][5] uint64 ticks of the 100 MHz s_memrealtime counter, copied to host memory. */
-int ssl4gie_debug_nt256_stamps(void* dst, size_t bytes);
-
 typedef struct ssl4gie_ar_handle ssl4gie_ar_handle;
 size_t ssl4gie_allreduce_direct_blob_bytes(void);
 int ssl4gie_allreduce_direct_init(int rank, int world, size_t max_elems, void* export_blob,

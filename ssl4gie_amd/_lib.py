@@ -10,18 +10,9 @@ import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libssl4gie_hip.so")
-# kernel-development builds only: `make -C ssl4gie_amd/csrc DEBUG_KNOBS=1` produces a second library with the
-# ablation / time-stamp modes of the NT GEMM compiled in; it is loaded only on this explicit request (and says
-# so on stderr) — the release library has no environment knob that changes results.
-_dbg = os.environ.get("SSL4GIE_DEBUG_LIB", "")
-if _dbg == "1" or _dbg.startswith("x"):  # "x<tag>": a tools/build_variant.sh experiment library
-    LIB_PATH = os.path.join(_HERE, "libssl4gie_hip_dbg.so" if _dbg == "1" else f"libssl4gie_hip_{_dbg}.so")
-    import sys as _sys
-    print(f"ssl4gie_amd: SSL4GIE_DEBUG_LIB=1 -> loading the DEBUG library {LIB_PATH}", file=_sys.stderr)
-
 # the one copy of the ABI revision on the Python side: build(), the tests and load() compare the
 # library's ssl4gie_abi_version() with it (include/ssl4gie_hip.h documents the history)
-ABI_VERSION = 10
+ABI_VERSION = 11
 
 PROF_KINDS = 7  # SSL4GIE_PROF_KINDS: entries of the launch profiler's arrays
 
@@ -207,7 +198,6 @@ PROTOTYPES = {
     "ssl4gie_conv3x3_weight_pack_batch": (i32, [vp, vp, vp, vp, vp, vp, i32, i32, vp]),
     "ssl4gie_conv3x3_weight_pack": (i32, [vp, vp, i32, i32, i32, i32, i32, vp]),
     "ssl4gie_conv3x3_wgrad_unpack": (i32, [vp, vp, i32, i32, i32, i32, vp]),
-    "ssl4gie_debug_nt256_stamps": (i32, [vp, sz]),
     "ssl4gie_prof_begin": (i32, [i32]),
     "ssl4gie_prof_collect": (i32, [vp, vp, vp]),
     "ssl4gie_prof_end": (i32, []),

@@ -23,10 +23,6 @@
 #include <stdlib.h>
 #include <type_traits>
 
-#ifndef TN256_ABL
-#define TN256_ABL 0
-#endif
-
 DEVI int q_swz(int k) { return ((k & 3) | ((k >> 1) & 4)) << 1; }
 
 // MFMA operand (16 x-values x 32 k) out of a k-major half-tile image: lane l gets, for
@@ -60,9 +56,6 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_tn256_kernel(
     int tiles_n, int ntiles, int splits, float alpha, int accumulate, float* __restrict__ colsum,
     float* __restrict__ colsum_part, ConvK cg, TnExtras ex) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    // -DTN256_ABL=<bits> (tools/build_variant.sh experiment libraries; timing only, garbage outputs): bit 0 no output
-    // stores, bit 1 no fragment reads, bit 2 no LDS-DMA, bit 3 no MFMA — which of the K-loop's streams sets its time
-    constexpr int dbg = TN256_ABL;
     const bool tn_m_inner_ok = ex.m_inner != 0;
     const int t = threadIdx.x, lane = t & 63;
     const int wave = __builtin_amdgcn_readfirstlane(t >> 6);
@@ -139,7 +132,7 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_tn256_kernel(
     int s_kt = 0;  // stream cursor (K-tile relative to kt0)
     auto issue = [&](auto Jc) {
         constexpr int J = decltype(Jc)::value;
-        if (s_kt < total_kt && !(dbg & 4)) {
+        if (s_kt < total_kt) {
             const unsigned dst = lds0 + (s_kt & 1) * P_BUF + J * P_HALF;
             const size_t krow = (size_t)(kt0 + s_kt) * P_BK;
             const bf16_t* base = (J & 1) ? At + krow * ldat : Bt + krow * ldbt;
@@ -179,16 +172,16 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_tn256_kernel(
     using I3 = std::integral_constant<int, 3>;
 
     const int kl = 8 * (lane >> 4);
-    bf16x8 dbg_z;
+    // Unused: what is left of the retired fragment-read ablation.  The optimiser deletes it, but without it the
+    // compiler orders the prologue of six instantiations differently (same registers, four of them 4 bytes longer),
+    // and the shipped kernels stay as they were measured (profiles/gemm256_dispatch_codegen.md).
+    [[maybe_unused]] bf16x8 unused_z;
 #pragma unroll
-    for (int j = 0; j < 8; ++j) dbg_z[j] = (__bf16)(0.001f * (float)(lane + j));
-    auto dbg_frag = [&]() -> bf16x8 { return dbg_z; };
+    for (int j = 0; j < 8; ++j) unused_z[j] = (__bf16)(0.001f * (float)(lane + j));
     auto ldA = [&](int buf, int h, int mi, int ks) -> bf16x8 {
-        if (dbg & 2) return dbg_frag();
         return q_frag(smem + buf * P_BUF + (h ? 3 : 1) * P_HALF, ks * 32 + kl, wr * 64 + mi * 16, lane);
     };
     auto ldB = [&](int buf, int h, int ni, int ks) -> bf16x8 {
-        if (dbg & 2) return dbg_frag();
         return q_frag(smem + buf * P_BUF + (h ? 2 : 0) * P_HALF, ks * 32 + kl, wc * 32 + ni * 16, lane);
     };
 
@@ -220,7 +213,6 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_tn256_kernel(
     }
     auto mma = [&](auto QMc, auto QNc, bf16x8 (&bb)[2][2]) {
         constexpr int QM = decltype(QMc)::value, QN = decltype(QNc)::value;
-        if (dbg & 8) return;
         __builtin_amdgcn_s_setprio(1);
         if constexpr (CONV == 2 && QM == 0) {  // P0 has just loaded b0, P1 b1
 #pragma unroll
@@ -347,10 +339,6 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_tn256_kernel(
     const long long ldo = (splits == 1) ? ldc : N;
     const float al = (splits == 1) ? alpha : 1.f;
     const bool accu = (splits == 1) && accumulate;
-    if (dbg & 1) {
-        asm volatile("" ::"v"(acc[0][0][0]), "v"(acc[7][3][3]), "v"(acc[3][1][2]));
-        return;
-    }
     if (m0 + P_BM <= M && n0 + P_BN <= N)
         p_store_f32<true, false>(acc, stg, al, zero4, nullptr, 0, accu, out, ldo, m0 + wr * 128,
                                  n0 + wc * 64, M, N, lane);
@@ -362,7 +350,7 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_tn256_kernel(
 // =====================================================================================
 // Round 5: the K-SPLIT form of the same product (plain operands, full or clamped tiles).
 //
-// What the ablations of the kernel above showed (tools/build_variant.sh -DTN256_ABL, profiles/r05a): its K-loop is
+// What the ablations of the kernel above showed (profiles/r05a; the ablation switches are retired, profiles/HISTORY.md): its K-loop is
 // not bound by the transposed reads (reads + skeleton alone: 0.2 us per K-tile) but by two things that add up —
 // the four-phase skeleton around the MFMAs (1.67 us per K-tile with MFMAs only: 8 intervals of 16 MFMAs + ~110
 // cycles of barrier / wait overhead each, where the NT kernel's two-phase form has 4 of 32) and the LDS-DMA stream
@@ -391,7 +379,7 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_tn256_kernel(
 // bit-identical, so SSL4GIE_TN256K=0 (A/B timing) changes nothing else.
 DEVI int k_swz(int k) { return (k & 3) | ((k >> 1) & 4); }
 
-template <bool COLSUM, int RING>
+template <bool COLSUM>
 __global__ __launch_bounds__(512, 2) void gemm_bf16_tn256k_kernel(
     const bf16_t* __restrict__ At, long long ldat, const bf16_t* __restrict__ Bt, long long ldbt,
     float* __restrict__ C, long long ldc, float* __restrict__ slabs, int M, int N, int K,
@@ -447,24 +435,21 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_tn256k_kernel(
         vb0 = offs(0, false); vb1 = offs(1, false);
     }
     const unsigned lds0 = __builtin_amdgcn_readfirstlane(p_lds_addr(smem) + wave * 2048);
-    // ring slots: A stages 0-3 at 0 .. 64 KiB, B stages 0-3 at 64 .. 128 KiB; RING == 5: a fifth stage in the 32 KiB the
-    // epilogue's staging area occupies AFTER the loop (A at 128 KiB, B at 144 KiB)
-    auto a_slot = [](int t) -> unsigned { return t < 4 ? (unsigned)t * 16384u : 131072u; };
-    auto b_slot = [](int t) -> unsigned { return t < 4 ? 65536u + (unsigned)t * 16384u : 147456u; };
+    // ring slots: A stages 0-3 at 0 .. 64 KiB, B stages 0-3 at 64 .. 128 KiB
+    auto a_slot = [](int t) -> unsigned { return (unsigned)t * 16384u; };
+    auto b_slot = [](int t) -> unsigned { return 65536u + (unsigned)t * 16384u; };
     const char* baseA = (const char*)(At + (size_t)kt0 * P_BK * ldat);
     const char* baseB = (const char*)(Bt + (size_t)kt0 * P_BK * ldbt);
     const long long stepA = 64LL * ldat, stepB = 64LL * ldbt;  // 32 rows, in bytes
     int s_ph = 0;  // stream cursor (stage index)
     auto issue = [&](auto STc) {
         constexpr int ST = decltype(STc)::value;  // ring slot of the stage being issued
-        if (s_ph < nph && !(TN256_ABL & 4)) {
+        if (s_ph < nph) {
             const unsigned da = lds0 + a_slot(ST), db = lds0 + b_slot(ST);
             p_glds2(baseA, va0, va1, da, da + 1024);
             p_glds2(baseB, vb0, vb1, db, db + 1024);
-            if (!(TN256_ABL & 16)) {  // (bit 4: the stream re-reads its first stage — an L2-resident DMA stream)
-                baseA += stepA;
-                baseB += stepB;
-            }
+            baseA += stepA;
+            baseB += stepB;
         }
         ++s_ph;
     };
@@ -472,7 +457,6 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_tn256k_kernel(
     using I1 = std::integral_constant<int, 1>;
     using I2 = std::integral_constant<int, 2>;
     using I3 = std::integral_constant<int, 3>;
-    using I4 = std::integral_constant<int, 4>;
 
     // ---- fragment addresses: lane (g = l >> 4, q = (l & 15) >> 2, p = l & 3) reads row 8 g + q (+ 4 for the second
     // read) of the stage, 8 bytes at p * 8 of the swizzled 32-byte unit
@@ -483,16 +467,7 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_tn256k_kernel(
     for (int mi = 0; mi < 8; ++mi) aoff[mi] = (unsigned)(frow + (((wr * 8 + mi) ^ fsw) << 5));
 #pragma unroll
     for (int ni = 0; ni < 4; ++ni) boff[ni] = (unsigned)(65536 + frow + (((wc * 4 + ni) ^ fsw) << 5));
-    bf16x8 dbg_z;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) dbg_z[j] = (__bf16)(0.001f * (float)(lane + j));
-    unsigned aoff4[8], boff4[4];
-#pragma unroll
-    for (int mi = 0; mi < 8; ++mi) aoff4[mi] = aoff[mi] + 131072u;
-#pragma unroll
-    for (int ni = 0; ni < 4; ++ni) boff4[ni] = boff[ni] + 81920u;   // 147456 = 65536 + 81920
     auto frag = [&](unsigned off, int imm) -> bf16x8 {
-        if (TN256_ABL & 2) return dbg_z;
         typedef __attribute__((address_space(3))) s16x4* lp_t;
         const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lp_t)(smem + off + imm));
         const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lp_t)(smem + off + imm + 2048));
@@ -517,16 +492,14 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_tn256k_kernel(
     auto phase = [&](auto STc, int s) {
         constexpr int ST = decltype(STc)::value;
         // ---------------- LOAD
-        // (slot 4 of the five-stage ring lies beyond a 16-bit immediate from the slot-0 addresses: its own base registers)
 #pragma unroll
-        for (int ni = 0; ni < 4; ++ni) b[ni] = ST < 4 ? frag(boff[ni], ST * 16384) : frag(boff4[ni], 0);
+        for (int ni = 0; ni < 4; ++ni) b[ni] = frag(boff[ni], ST * 16384);
 #pragma unroll
-        for (int mi = 0; mi < 8; ++mi) a[mi] = ST < 4 ? frag(aoff[mi], ST * 16384) : frag(aoff4[mi], 0);
+        for (int mi = 0; mi < 8; ++mi) a[mi] = frag(aoff[mi], ST * 16384);
         __builtin_amdgcn_sched_barrier(0);
-        issue(std::integral_constant<int, (ST + RING - 1) % RING>{});
+        issue(std::integral_constant<int, (ST + 3) % 4>{});
         // stage s + 1 must have landed: all but this wave's pieces of the stages after it may stay in flight
-        if (s + RING - 1 < nph) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(4 * (RING - 2)) : "memory");
-        else if (RING == 5 && s + 3 < nph) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
+        if (s + 3 < nph) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
         else if (s + 2 < nph) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
         else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
@@ -534,7 +507,7 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_tn256k_kernel(
         __builtin_amdgcn_s_barrier();
         // ---------------- MMA
         __builtin_amdgcn_s_setprio(1);
-        if constexpr (COLSUM && !(TN256_ABL & 8)) {
+        if constexpr (COLSUM) {
             if (do_cs) {
                 auto cs = [&](const bf16x8& lo, const bf16x8& hi) {
                     accb[0] = P_MFMA(ones, lo, accb[0]);
@@ -546,12 +519,10 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_tn256k_kernel(
                 else cs(a[3], a[7]);
             }
         }
-        if constexpr (!(TN256_ABL & 8)) {
 #pragma unroll
-            for (int mi = 0; mi < 8; ++mi)
+        for (int mi = 0; mi < 8; ++mi)
 #pragma unroll
-                for (int ni = 0; ni < 4; ++ni) acc[mi][ni] = P_MFMA(b[ni], a[mi], acc[mi][ni]);
-        }
+            for (int ni = 0; ni < 4; ++ni) acc[mi][ni] = P_MFMA(b[ni], a[mi], acc[mi][ni]);
         __builtin_amdgcn_s_setprio(0);
         __builtin_amdgcn_sched_barrier(0);
         __builtin_amdgcn_s_barrier();
@@ -559,34 +530,21 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_tn256k_kernel(
 
     if (total_kt > 0) {
         issue(I0{}); issue(I1{}); issue(I2{});
-        if constexpr (RING == 5) issue(I3{});
         // stage 0 landed: the later ones (nph is even: >= 2) may stay in flight
-        if (nph >= RING - 1) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(4 * (RING - 2)) : "memory");
+        if (nph >= 3) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
         else asm volatile("s_waitcnt vmcnt(4)" ::: "memory");  // nph == 2: stage 1 may
         __builtin_amdgcn_s_barrier();
         if (wr == 1) __builtin_amdgcn_s_barrier();
         int s = 0;
-        if constexpr (RING == 4) {
-            for (; s + 3 < nph; s += 4) {
-                phase(I0{}, s);
-                phase(I1{}, s + 1);
-                phase(I2{}, s + 2);
-                phase(I3{}, s + 3);
-            }
-            if (s < nph) {  // an odd number of K-tiles: two more stages, slots 0 and 1
-                phase(I0{}, s);
-                phase(I1{}, s + 1);
-            }
-        } else {
-            // one loop body of five guarded phases (wave-uniform conditions): a separate tail of up to four phases
-            // made the register allocator migrate the accumulators between the copies (256 VGPRs + spills)
-            for (; s < nph; s += 5) {
-                phase(I0{}, s);
-                if (s + 1 < nph) phase(I1{}, s + 1);
-                if (s + 2 < nph) phase(I2{}, s + 2);
-                if (s + 3 < nph) phase(I3{}, s + 3);
-                if (s + 4 < nph) phase(I4{}, s + 4);
-            }
+        for (; s + 3 < nph; s += 4) {
+            phase(I0{}, s);
+            phase(I1{}, s + 1);
+            phase(I2{}, s + 2);
+            phase(I3{}, s + 3);
+        }
+        if (s < nph) {  // an odd number of K-tiles: two more stages, slots 0 and 1
+            phase(I0{}, s);
+            phase(I1{}, s + 1);
         }
         if (wr == 0) __builtin_amdgcn_s_barrier();
     }
@@ -663,44 +621,6 @@ int ssl4gie_internal_tn256_splits(const ssl4gie_gemm_desc* d) {
     return s;
 }
 
-// Predicted HBM bytes of a paired launch with `splits` K-splits (tools/tn_traffic_model.py, checked against the PMC
-// counters: 405 MB per launch predicted, 397 measured): consecutive logical workgroups share an XCD's L2
-// (xcd_remap), so an XCD chunk holding r m-tiles and c n-tiles of one split of one product reads r + c operand
-// slabs; plus the fp32 slabs (GEMM write, reduce read + write).
-static double tn256_pair_traffic(const ssl4gie_gemm_desc* const* ds, int n, int splits, bool m_inner_ok) {
-    int tm[2], tn[2], nt[2], all = 0;
-    for (int i = 0; i < n; ++i) {
-        tm[i] = (ds[i]->M + P_BM - 1) / P_BM; tn[i] = (ds[i]->N + P_BN - 1) / P_BN;
-        if (tm[i] > 64 || tn[i] > 64) return 1e30;  // (bit sets below; no such product in the models)
-        nt[i] = tm[i] * tn[i]; all += nt[i];
-    }
-    const int G = all * splits, q = G / 8, r = G % 8;
-    long long slabs = 0;
-    int lo = 0;
-    for (int x = 0; x < 8; ++x) {  // the 8 contiguous chunks of logical ids xcd_remap deals to the XCDs
-        const int hi = lo + q + (x < r ? 1 : 0);
-        int cur_s = -1, cur_p = -1;
-        unsigned long long rows = 0, cols = 0;
-        for (int lid = lo; lid < hi; ++lid) {
-            const int sidx = lid / all;
-            int t = lid % all, p = 0;
-            while (p < n - 1 && t >= nt[p]) t -= nt[p++];
-            if (sidx != cur_s || p != cur_p) {
-                slabs += __builtin_popcountll(rows) + __builtin_popcountll(cols);
-                rows = cols = 0; cur_s = sidx; cur_p = p;
-            }
-            const bool m_inner = tm[p] < tn[p] && m_inner_ok;
-            const int mt = m_inner ? t % tm[p] : t / tn[p], ntile = m_inner ? t / tm[p] : t % tn[p];
-            rows |= 1ull << mt; cols |= 1ull << ntile;
-        }
-        slabs += __builtin_popcountll(rows) + __builtin_popcountll(cols);
-        lo = hi;
-    }
-    double out = 0;
-    for (int i = 0; i < n; ++i) out += (double)ds[i]->M * ds[i]->N * 4;
-    return (double)slabs * 256 * ((double)ds[0]->K / splits) * 2 + (splits > 1 ? out * (2 * splits + 1) : out);
-}
-
 int ssl4gie_internal_tn256_pair_splits(const ssl4gie_gemm_desc* a, const ssl4gie_gemm_desc* b) {
     const int tiles = ((a->M + P_BM - 1) / P_BM) * ((a->N + P_BN - 1) / P_BN) +
                       ((b->M + P_BM - 1) / P_BM) * ((b->N + P_BN - 1) / P_BN);
@@ -720,22 +640,6 @@ int ssl4gie_internal_tn256_pair_splits(const ssl4gie_gemm_desc* a, const ssl4gie
     if (s > nkt / 8) s = nkt / 8;
     if (s < 1) s = 1;
     if (s > 64) s = 64;
-    // SSL4GIE_TN_ALIGN=1 (A/B): among the split counts that keep 70 .. 110 % of the target's workgroups, the one
-    // with the least predicted HBM traffic (chunks of whole K-splits per XCD read every operand slab once)
-    static int align = -1;
-    if (align < 0) { const char* e = getenv("SSL4GIE_TN_ALIGN"); align = e ? atoi(e) : 0; }
-    if (align) {
-        const ssl4gie_gemm_desc* ds[2] = {a, b};
-        int best = s;
-        double best_t = tn256_pair_traffic(ds, 2, s, true);
-        for (int c = 1; c <= 64 && c <= nkt / 8; ++c) {
-            const int wgs = c * tiles;
-            if (wgs * 10 < target * 7 || wgs * 10 > target * 11) continue;
-            const double t = tn256_pair_traffic(ds, 2, c, true);
-            if (t < best_t * 0.97) { best_t = t; best = c; }
-        }
-        s = best;
-    }
     return s;
 }
 
@@ -799,80 +703,35 @@ static int tn256_launch_impl(const ssl4gie_gemm_desc* descs, int n, int splits, 
     static int m_inner = -1;  // SSL4GIE_TN_INNER=n: the row-by-row tile walk of rounds 1-2 (A/B)
     if (m_inner < 0) { const char* s = getenv("SSL4GIE_TN_INNER"); m_inner = (s && (s[0] == 'n' || s[0] == 'N')) ? 0 : 1; }
     sec.m_inner = m_inner;
-    dim3 grid((tm * tn + sec.total_tiles) * splits), block(512);
+    dim3 grid((tm * tn + sec.total_tiles) * splits);
     ConvK ck{};
     if (d->conv) {
         const int rc = ssl4gie_internal_conv_k(d->conv, &ck);
         if (rc) return rc;
     }
-#define Q_LAUNCH(CS_, CONV_) do { if (partial) Q_LAUNCH_P(CS_, CONV_, true); else Q_LAUNCH_P(CS_, CONV_, false); } while (0)
-#define Q_LAUNCH_P(CS_, CONV_, PART_)                                                              \
-    do {                                                                                           \
-        auto kfn = gemm_bf16_tn256_kernel<CS_, CONV_, PART_>;                                      \
-        static bool attr_set = false; /* idempotent; a benign race only repeats the call */        \
-        if (!attr_set) {                                                                           \
-            HIP_RET(hipFuncSetAttribute((const void*)kfn,                                          \
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, P_LDS_BYTES)); \
-            attr_set = true;                                                                       \
-        }                                                                                          \
-        hipLaunchKernelGGL(kfn, grid, block, P_LDS_BYTES, st, (const bf16_t*)d->A, d->sAk,         \
-                           (const bf16_t*)d->B, d->sBk, (float*)d->C, d->ldc, slabs, d->M, d->N,   \
-                           d->K, tn, tm * tn, splits, d->alpha, d->accumulate, d->colsum_a,        \
-                           colsum_part, ck, sec);                                                  \
-    } while (0)
     const int cv = d->conv ? (d->conv->relu ? 2 : 1) : 0;
     // a lone plain product whose tiles M x N does not fill (ResNet's narrow 1x1 weight gradients)
     const bool partial = n == 1 && cv == 0 && (d->M % P_BM != 0 || d->N % P_BN != 0);
-    // plain operands, no skipped fragment blocks: the k-split kernel (SSL4GIE_TN256K=0: the column-split one; the
-    // results are bit-identical, the knob exists for A/B timing)
+    // the arguments both kernels share; `tail`: (ck, sec) for the column-split kernel, (sec) for the k-split one
+    auto run = [&](auto k, const auto&... tail) {
+        return p_launch<decltype(k)::fn>(grid, st, (const bf16_t*)d->A, d->sAk, (const bf16_t*)d->B, d->sBk,
+                                         (float*)d->C, d->ldc, slabs, d->M, d->N, d->K, tn, tm * tn, splits,
+                                         d->alpha, d->accumulate, d->colsum_a, colsum_part, tail...);
+    };
+    // plain operands, no skipped fragment blocks: the k-split kernel (SSL4GIE_TN256K=0: the column-split one of
+    // rounds 1-4; the results are bit-identical, the knob exists for A/B timing)
     static int ksplit = -1;
-    if (ksplit < 0) {  // SSL4GIE_TN256K=0: the column-split kernel of rounds 1-4 (A/B); =5 (debug library only): a five-stage ring, measured null
-        const char* s = getenv("SSL4GIE_TN256K");
-        ksplit = !s ? 1 : (s[0] == '0' ? 0 : 1);
-#ifdef SSL4GIE_DEBUG_KNOBS
-        if (s && s[0] == '5') ksplit = 5;
-#endif
-    }
-    if (ksplit && cv == 0 && !partial) {
-#define K_LAUNCH(CS_, RING_)                                                                          \
-    do {                                                                                           \
-        auto kfn = gemm_bf16_tn256k_kernel<CS_, RING_>;                                            \
-        static bool attr_set = false;                                                              \
-        if (!attr_set) {                                                                           \
-            HIP_RET(hipFuncSetAttribute((const void*)kfn,                                          \
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, P_LDS_BYTES)); \
-            attr_set = true;                                                                       \
-        }                                                                                          \
-        hipLaunchKernelGGL(kfn, grid, block, P_LDS_BYTES, st, (const bf16_t*)d->A, d->sAk,         \
-                           (const bf16_t*)d->B, d->sBk, (float*)d->C, d->ldc, slabs, d->M, d->N,   \
-                           d->K, tn, tm * tn, splits, d->alpha, d->accumulate, d->colsum_a,        \
-                           colsum_part, sec);                                                      \
-    } while (0)
-        // SSL4GIE_TN256K=5: a five-stage ring (the fifth stage in the epilogue's staging area: one more stage in
-        // flight, 24 more address registers) — built, bit-identical, measured NULL against the four-stage ring
-        // (pair launches 589 vs 586-591 us, MAE step 22.08 vs 22.09-22.13 ms same-box: profiles/r05j): the
-        // stream's cost is not latency a deeper ring would cover (an L2-RESIDENT stream makes the kernel 14 % faster,
-        // profiles/r05b, so it is the L2 -> LDS path under load)
-#ifdef SSL4GIE_DEBUG_KNOBS
-        if (ksplit == 5) { if (any_colsum) K_LAUNCH(true, 5); else K_LAUNCH(false, 5); }
-        else
-#endif
-        { if (any_colsum) K_LAUNCH(true, 4); else K_LAUNCH(false, 4); }
-#undef K_LAUNCH
-        LAUNCH_CHECK();
-        return 0;
-    }
-    if (any_colsum) {
-        if (cv == 0) Q_LAUNCH(true, 0);
-        else if (cv == 1) Q_LAUNCH(true, 1);
-        else Q_LAUNCH(true, 2);
-    } else {
-        if (cv == 0) Q_LAUNCH(false, 0);
-        else if (cv == 1) Q_LAUNCH(false, 1);
-        else Q_LAUNCH(false, 2);
-    }
-#undef Q_LAUNCH
-#undef Q_LAUNCH_P
-    LAUNCH_CHECK();
-    return 0;
+    if (ksplit < 0) { const char* s = getenv("SSL4GIE_TN256K"); ksplit = (s && s[0] == '0') ? 0 : 1; }
+    if (ksplit && cv == 0 && !partial)
+        return any_colsum ? run(P_KERNEL<gemm_bf16_tn256k_kernel<true>>{}, sec)
+                          : run(P_KERNEL<gemm_bf16_tn256k_kernel<false>>{}, sec);
+    // the column-split kernel, (COLSUM, CONV, PARTIAL): PARTIAL exists for plain operands only
+    auto column_split = [&](auto cs) {
+        constexpr bool CS = decltype(cs)::value;
+        if (partial) return run(P_KERNEL<gemm_bf16_tn256_kernel<CS, 0, true>>{}, ck, sec);
+        if (cv == 0) return run(P_KERNEL<gemm_bf16_tn256_kernel<CS, 0, false>>{}, ck, sec);
+        if (cv == 1) return run(P_KERNEL<gemm_bf16_tn256_kernel<CS, 1, false>>{}, ck, sec);
+        return run(P_KERNEL<gemm_bf16_tn256_kernel<CS, 2, false>>{}, ck, sec);
+    };
+    return any_colsum ? column_split(std::true_type{}) : column_split(std::false_type{});
 }

@@ -18,7 +18,7 @@ Variants reached, from one `rocprofv3 --kernel-trace --stats` run of this module
 GEMM / reduction kernels; `route` labels every case and the last test prints the counts per label):
     gemm_generic_kernel<TAB, TC>            all four: <f32,f32> <f32,bf16> <bf16,f32> <bf16,bf16>
     gemm_bf16_nt_kernel<TC, MODE>           all fourteen: TC in {f32, bf16} x MODE 0..6
-    gemm_bf16_nt256_kernel<TC, MODE, CONV=0, STATS, ROLE=0, NJ, PH2=true, NTS (streaming), TAB (table)>
+    gemm_bf16_nt256_kernel<TC, MODE, CONV=0, STATS, NJ, NTS (streaming), TAB (table)>
         f32,  MODE 0 / 1 / 3          NJ 3, 4            NTS false and true
         bf16, MODE 0 / 1              NJ 3, 4            NTS false and true;   NJ 2: NTS true only (*)
         bf16, MODE 2 / 5              NJ 3 (polynomial)  NTS false and true;   NJ 4: TAB, NTS false and true (**)
@@ -26,14 +26,15 @@ GEMM / reduction kernels; `route` labels every case and the last test prints the
         bf16, MODE 8 / 9              NJ 2, 3, 4         NTS false and true
         bf16, MODE 0, STATS           NJ 2, 3, 4         (no streaming twin exists)
     gemm_bf16_tn_kernel; slab_reduce_kernel, slab_reduce_wide_kernel<4>, <16>
-    gemm_bf16_tn256k_kernel<CS, 4>          CS false and true (lone products, pair, group)
+    gemm_bf16_tn256k_kernel<CS>             CS false and true (lone products, pair, group)
     gemm_bf16_tn256_kernel<CS, 0, PART=true>  CS false and true (the partial kernel)
   Reachable in the default environment and not reached: none.  Not reachable without a knob, hence not here:
     (*)  bf16 MODE 0 / 1 on NJ 2 without streaming stores: the heuristic wants 128 tiles, one column tile means
          M >= 32513, and streaming starts at M = 16384 (SSL4GIE_NT256=1 or SSL4GIE_NT_STREAM_M would reach it);
     (**) MODE 2 / 5 on NJ 4 in the polynomial form (SSL4GIE_GELU_TABLE=0);
     gemm_bf16_tn256_kernel<CS, 0, PART=false>, the column-split kernel for full tiles (SSL4GIE_TN256K=0);
-    ROLE 1, PH2 false and the five-stage ring (the debug library's knobs);
+    (the loader-wave and four-phase forms of the NT kernel and the five-stage ring of the k-split TN kernel, which a
+    debug build of the library used to hold, no longer exist: profiles/HISTORY.md, "Retired knobs");
     CONV 1 / 2 and MODE 7 (the implicit-convolution operand): tests/test_gpu_conv.py.
   FULL is no instantiation of its own: gemm256.h takes the full / ragged epilogue per tile at run time, so every ragged
   shape with more than one tile runs both; the full-tile twins (16384, 32768 rows) run the full one alone.

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """relative error of the bf16 attention backward against an fp64 evaluation, several seeds (A/B of two builds:
-SSL4GIE_DEBUG_LIB=1 loads the other library)"""
+run it once from each tree)"""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
 import torch
