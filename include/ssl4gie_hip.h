@@ -14,7 +14,9 @@
  *   - returns 0 on success, SSL4GIE_EARG (1000) for an invalid argument, otherwise a hipError_t;
  *   - callable from any host thread; the only mutable process-wide settings are the execution
  *     options ssl4gie_set_wgrad_stream / ssl4gie_set_compute_cus and the profiler;
- *   - ssl4gie_abi_version() = 11 (10: before the diagnostics entry point that read the 256x256 NT kernel's in-kernel
+ *   - ssl4gie_abi_version() = 12 (11: before the sixteen BatchNorm entry points that had grown one per fusion (ssl4gie_bn_fwd / _fwd_partials / _fwd_partials_bits /
+ *     _coef_partials / _coef_stats / _apply_bits, _stats / _stats_partials, _bwd / _bwd_xmask / _bwd_bits, _bwd_reduce / _reduce_xmask / _reduce_bits,
+ *     _bwd_apply / _apply_xmask) were REPLACED by five with a source and a mask kind — the same launches, new signatures; 10: before the diagnostics entry point that read the 256x256 NT kernel's in-kernel
  *     time stamps was REMOVED with the debug build of the library — the one removal in this history; 9: before ssl4gie_infonce_{workspace_bytes,loss} / ssl4gie_cross_entropy{_workspace_bytes,} /
  *     ssl4gie_bt_loss{_workspace_bytes,,_grad} existed — additions only; 8: before ssl4gie_grad_norm_{workspace_bytes,arena} / ssl4gie_grad_scale_arena /
  *     ssl4gie_adamw_arena_range_ctl existed — additions only; 7: before ssl4gie_stem3x3_{tiles,fwd,wgrad_workspace_bytes,wgrad} existed — additions only; 6: before ssl4gie_bn_coef_stats / ssl4gie_bn_apply_bits / ssl4gie_bn_bwd_reduce_bits existed — additions only; 5: before SSL4GIE_PROF_KINDS grew from 5 to 7 — the profiler's arrays; 1: before ssl4gie_gemm_desc gained `colsum_a` / `conv`; 2: before
@@ -145,7 +147,7 @@ typedef struct ssl4gie_gemm_desc {
     const ssl4gie_conv3x3_geom* conv;
     /* optional fp32 [ceil(M / 128)][2][N]: per 128-row block, the column sums ([0]) and sums of
      * squares ([1]) of the STORED outputs — the batch statistics of the BatchNorm that follows a
-     * convolution, produced by the GEMM's epilogue (see ssl4gie_bn_fwd_partials).  NT products with
+     * convolution, produced by the GEMM's epilogue (see ssl4gie_bn_fwd, FROM_PARTIALS).  NT products with
      * bf16 C, EPI_NONE, no accumulate, N % 8 == 0 only; anything else is SSL4GIE_EARG.  With C == NULL the
      * product only produces these statistics (of the values it WOULD store, bf16-rounded): nothing is written
      * to C — the first half of the BatchNorm-fused 1x1 convolution (SSL4GIE_EPI_AFFINE_AUX_RELU). */
@@ -367,7 +369,7 @@ int ssl4gie_col2im3x3(const void* dcols, void* dx, int dtype, int B, int H, int 
  *     relu_mask [B,H,W,Cout] bf16 — the data gradient of a convolution behind a ReLU)
  * colstats (optional, not together with relu_mask): fp32 [ssl4gie_conv3x3_direct_tiles(B,H,W)][2][Cout],
  * per 8 x 32 pixel tile the column sums ([0]) and sums of squares ([1]) of the stored y — the
- * partial statistics ssl4gie_bn_fwd_partials / ssl4gie_bn_stats_partials take (as
+ * partial statistics ssl4gie_bn_fwd (FROM_PARTIALS) / ssl4gie_bn_stats take (as
  * ssl4gie_gemm_desc.colstats, with one partial per tile instead of per 128 rows).
  * The data gradient is the same call on dy with w2 := weight.flip(2,3) as [Cin, 9*Cout].
  * _ok(): Cin % 32 == 0 and Cout % 8 == 0 (any H, W); otherwise the calls return SSL4GIE_EARG.
@@ -387,10 +389,10 @@ int ssl4gie_conv3x3_direct_wgrad(const void* dy, const void* x, float* dw2, floa
                                  void* workspace, size_t workspace_bytes, int B, int H, int W, int Cin,
                                  int Cout, int relu_in, int accumulate, void* stream);
 /* The same two kernels with a training-mode BatchNorm (+ ReLU) applied to their input on the way in: the operand
- * is act(x in_coef[0][ci] + in_coef[1][ci]) rounded to bf16 (in_coef [2][Cin] as ssl4gie_bn_coef_partials writes
+ * is act(x in_coef[0][ci] + in_coef[1][ci]) rounded to bf16 (in_coef [2][Cin] as the coefficients-only ssl4gie_bn_fwd writes
  * it; act = ReLU if relu_in), zero-padded AFTER the normalisation — torchvision Bottleneck bn1 -> relu -> conv2
- * without a BatchNorm pass or a normalised map in memory (its backward: ssl4gie_bn_bwd_xmask on the data gradient).
- * Values equal ssl4gie_bn_fwd_partials followed by the plain kernels bit for bit. */
+ * without a BatchNorm pass or a normalised map in memory (its backward: ssl4gie_bn_bwd with MASK_X on the data gradient).
+ * Values equal ssl4gie_bn_fwd (FROM_PARTIALS) followed by the plain kernels bit for bit. */
 int ssl4gie_conv3x3_direct_fwd_affine(const void* x, const float* in_coef, const void* w2, const float* bias,
                                       void* y, float* colstats, int B, int H, int W, int Cin, int Cout,
                                       int relu_in, void* stream);
@@ -422,7 +424,7 @@ int ssl4gie_stem7x7_wgrad(const void* dy, const void* packed, float* dw2s, void*
  * SSL4GIE_BF16 (image and weight rounded to bf16 on the way in, MFMA) or SSL4GIE_F32 (plain fp32 FMA chains).
  *   fwd:   img fp32 [B,3,H,W], weight fp32 [C0][3][3][3] (the parameter) -> y [B,Ho,Wo,C0].  colstats
  *          (optional): fp32 [ssl4gie_stem3x3_tiles(B,H,W)][2][C0], per-tile column sums / sums of squares of
- *          the STORED y, as ssl4gie_bn_fwd_partials / ssl4gie_bn_coef_partials / ssl4gie_bn_stats_partials take.
+ *          the STORED y, as ssl4gie_bn_fwd (FROM_PARTIALS) / ssl4gie_bn_stats take.
  *   wgrad: dweight fp32 [C0][3][3][3] (+)= sum over output pixels of dy [B,Ho,Wo,C0] x image patch.
  *          Deterministic: one fp32 partial per workgroup in `workspace` + a fixed-order reduction.
  * Any other shape returns SSL4GIE_EARG. */
@@ -473,51 +475,70 @@ int ssl4gie_stem_im2col7x7(const float* img, void* cols, int dtype, int B, int H
                            long long ld, void* stream);
 int ssl4gie_subsample2(const void* x, void* y, int dtype, int B, int H, int W, int C, int backward,
                        void* stream);
-/* BatchNorm2d / BatchNorm1d in training mode over the rows of x [rows, C] (C % 8 == 0): batch
- * statistics in fp32 (biased variance for the normalisation, unbiased for running_var, momentum as
- * nn.BatchNorm: running = (1-m) running + m batch), y = act(xhat gamma + beta (+ res)) with
- * act = ReLU if `relu`; gamma / beta / res / running_* may be NULL.  mean / rstd [C] are outputs
- * kept for backward; `workspace` (ssl4gie_bn_workspace_bytes) is always required (with training == 0 they are INPUTS: the caller's running statistics, no
- * reduction runs).  Backward: g = relu ? (y > 0 ? dy : 0) : dy; dgamma = sum g xhat, dbeta = sum g,
- * dx = gamma rstd (g - mean(g) - xhat mean(g xhat)); dres (optional) = g. */
+/* BatchNorm2d / BatchNorm1d / SyncBatchNorm in training mode over the rows of a channels-last map x [rows, C]
+ * (C % 8 == 0), fused with the bottleneck's residual add and ReLU: y = act(xhat gamma + beta (+ res)), statistics in
+ * fp32 (biased variance for the normalisation, unbiased for running_var, momentum as nn.BatchNorm: running =
+ * (1-m) running + m batch).  Backward: g = masked dy, dgamma = sum g xhat, dbeta = sum g,
+ * dx = gamma rstd (g - mean(g) - xhat mean(g xhat)), dres (optional) = g.  Five functions span a small product; a
+ * combination outside it (a pointer the form does not use included: pass NULL) is SSL4GIE_EARG.  gamma / beta / res /
+ * running_* may be NULL wherever they are used.
+ *
+ * ssl4gie_bn_fwd: where the normalisation comes from (`source`) x what is written.
+ *   FROM_X         statistics pass over x; mean / rstd are OUTPUTS (kept for backward), running_* updated; writes y.
+ *   FROM_PARTIALS  the same statistics from `partial` [parts][2][C], the per-128-row sums the producing GEMM wrote
+ *                  (ssl4gie_gemm_desc::colstats), instead of a pass over x.  Writes y (+ relu_bits), or — y, x, res
+ *                  NULL — only the coefficients coef [2][C] with y = x coef[0][c] + coef[1][c], for a consumer that
+ *                  applies them itself: ssl4gie_bn_maxpool3x3s2_fwd, ssl4gie_conv3x3_direct_*_affine, the
+ *                  SSL4GIE_EPI_AFFINE_AUX_RELU epilogue (MoCo's momentum encoder, moco/builder.py:127-135).
+ *   FROM_STATS     mean / rstd are INPUTS (evaluation, or the GLOBAL statistics of a SyncBatchNorm exchange): no
+ *                  reduction runs, running_* must be NULL.  Writes y, or — y, x, res, workspace NULL, only C > 0
+ *                  required — coef.
+ *   FROM_COEF      coef is an INPUT (as the coefficients-only forms write it): y and relu_bits (both required, bf16,
+ *                  relu != 0); mean / rstd / gamma / beta / workspace NULL.
+ *   relu_bits (FROM_PARTIALS and FROM_COEF, bf16, relu != 0): bit j of relu_bits[i] = (y[8 i + j] > 0), rows * C / 8
+ *   bytes — the backward's ReLU mask at 1/16 of y's bytes (bn3 of a torchvision Bottleneck).
+ *
+ * ssl4gie_bn_stats: the LOCAL (mean, biased var) of SyncBatchNorm's forward, from a pass over x or (x NULL) from
+ *   `partial`; the caller combines the ranks (ssl4gie_bn_combine_stats) and calls ssl4gie_bn_fwd(FROM_STATS).
+ *
+ * Backward: where the ReLU mask comes from (`mask_kind`, `mask`) x how the pass is split.
+ *   MASK_NONE  no ReLU; mask NULL.
+ *   MASK_Y     mask = the ReLU output y.
+ *   MASK_X     BatchNorm + ReLU WITHOUT a residual input (mask and dres NULL): the mask is rebuilt as x a + b > 0 from
+ *              the forward's own coefficients (a = rstd gamma, b = beta - mean a: gamma / beta must be the forward's),
+ *              the ReLU output is not read.  Equals MASK_Y exactly unless the forward rounded a positive
+ *              pre-activation below the operand type's smallest subnormal to zero.
+ *   MASK_BITS  mask = the forward's relu_bits (bf16); dres (required) receives the masked gradient, which the apply
+ *              pass reads.  Equals MASK_Y exactly.
+ *   beta is read by MASK_X only (NULL otherwise).
+ *   ssl4gie_bn_bwd         one rank: reduction, dgamma / dbeta (overwritten or accumulated), dx, dres.
+ *   ssl4gie_bn_bwd_reduce  SyncBatchNorm, first half: sums [2][C] = LOCAL (sum g, sum g xhat), and dres; gamma is
+ *                          read by MASK_X only.  The caller all-reduces sums.
+ *   ssl4gie_bn_bwd_apply   second half: dx from the GLOBAL sums and inv_count = 1 / global row count.  MASK_NONE, _Y
+ *                          or _X; after a MASK_BITS (or any residual + ReLU) reduce, apply on its dres with MASK_NONE.
+ *   (convert_sync_batchnorm: Depth_estimation/train_depth.py:225, Models/moco_v3/main_moco.py:196.)
+ *
+ * `workspace`: ssl4gie_bn_workspace_bytes(rows, C) bytes, as floats [coef 3C][partials parts x 2C][sums 2C][pivot C]
+ * with room for the 64 x 2C fold of caller-supplied partials; the backward reuses the regions (`sums`: the mask
+ * coefficients of MASK_X, `pivot`: an aligned copy of mean). */
+enum { SSL4GIE_BN_FROM_X = 0, SSL4GIE_BN_FROM_PARTIALS = 1, SSL4GIE_BN_FROM_STATS = 2, SSL4GIE_BN_FROM_COEF = 3 };
+enum { SSL4GIE_BN_MASK_NONE = 0, SSL4GIE_BN_MASK_Y = 1, SSL4GIE_BN_MASK_X = 2, SSL4GIE_BN_MASK_BITS = 3 };
 size_t ssl4gie_bn_workspace_bytes(long long rows, int C);
-int ssl4gie_bn_fwd(const void* x, const float* gamma, const float* beta, const void* res, void* y,
-                   float* mean, float* rstd, float* running_mean, float* running_var,
-                   float momentum, float eps, int relu, int training, float* workspace, int dtype,
-                   long long rows, int C, void* stream);
-int ssl4gie_bn_bwd(const void* dy, const void* y, const void* x, const float* gamma,
-                   const float* mean, const float* rstd, void* dx, void* dres, float* dgamma,
-                   float* dbeta, int accumulate, int relu, float* workspace, int dtype,
-                   long long rows, int C, void* stream);
-/* The same backward for BatchNorm + ReLU WITHOUT a residual input (bn1 / bn2 of a torchvision Bottleneck, the
- * stem's bn1): the ReLU mask is rebuilt as x a + b > 0 from the forward's own coefficients (a = rstd gamma,
- * b = beta - mean a: gamma / beta must be the forward's) instead of read from the ReLU output — the two passes
- * stream 5 tensors instead of 7.  The results equal ssl4gie_bn_bwd(relu = 1, dres = NULL) exactly unless the
- * forward rounded a positive pre-activation below the operand type's smallest subnormal to zero. */
-int ssl4gie_bn_bwd_xmask(const void* dy, const void* x, const float* gamma, const float* beta,
-                         const float* mean, const float* rstd, void* dx, float* dgamma, float* dbeta,
-                         int accumulate, float* workspace, int dtype, long long rows, int C, void* stream);
-/* The ReLU mask of a BatchNorm (+ residual) + ReLU as a bit map instead of the ReLU output (bf16 maps): the forward
- * writes bit j of relu_bits[i] = (y[8 i + j] > 0) beside y (rows * C / 8 bytes), the backward's reduction pass reads
- * that byte stream instead of y — 1/16 of the bytes — and writes the masked gradient `dres` (required), which its
- * apply pass reads.  bn3 of a torchvision Bottleneck (its mask depends on the residual input too, so it cannot be
- * rebuilt from the BatchNorm input as ssl4gie_bn_bwd_xmask does).  Results equal ssl4gie_bn_bwd exactly. */
-int ssl4gie_bn_fwd_partials_bits(const void* x, const float* partial, int parts, const float* gamma,
-                                 const float* beta, const void* res, void* y, unsigned char* relu_bits,
-                                 float* mean, float* rstd, float* running_mean, float* running_var,
-                                 float momentum, float eps, float* workspace, int dtype, long long rows, int C,
-                                 void* stream);
-int ssl4gie_bn_bwd_bits(const void* dy, const unsigned char* relu_bits, const void* x, const float* gamma,
-                        const float* mean, const float* rstd, void* dx, void* dres, float* dgamma, float* dbeta,
-                        int accumulate, float* workspace, int dtype, long long rows, int C, void* stream);
-/* SyncBatchNorm (convert_sync_batchnorm: Depth_estimation/train_depth.py:225,
- * Models/moco_v3/main_moco.py:196) = the same kernels with the exchange step between them:
- *   forward : ssl4gie_bn_stats (LOCAL mean / biased var) -> caller combines over ranks ->
- *             ssl4gie_bn_fwd(training = 0) with the global mean / rstd;
- *   backward: ssl4gie_bn_bwd_reduce (LOCAL sum g, sum g xhat -> sums [2, C]; also dres = g) ->
- *             caller all-reduces sums -> ssl4gie_bn_bwd_apply with 1 / global row count. */
-int ssl4gie_bn_stats(const void* x, float* mean, float* var, float* workspace, int dtype,
-                     long long rows, int C, void* stream);
+int ssl4gie_bn_fwd(int source, const void* x, const float* partial, int parts, const float* gamma,
+                   const float* beta, const void* res, void* y, unsigned char* relu_bits, float* coef, float* mean,
+                   float* rstd, float* running_mean, float* running_var, float momentum, float eps, int relu,
+                   float* workspace, int dtype, long long rows, int C, void* stream);
+int ssl4gie_bn_stats(const void* x, const float* partial, int parts, float* mean, float* var, float* workspace,
+                     int dtype, long long rows, int C, void* stream);
+int ssl4gie_bn_bwd(const void* dy, int mask_kind, const void* mask, const void* x, const float* gamma,
+                   const float* beta, const float* mean, const float* rstd, void* dx, void* dres, float* dgamma,
+                   float* dbeta, int accumulate, float* workspace, int dtype, long long rows, int C, void* stream);
+int ssl4gie_bn_bwd_reduce(const void* dy, int mask_kind, const void* mask, const void* x, const float* gamma,
+                          const float* beta, const float* mean, const float* rstd, void* dres, float* sums,
+                          float* workspace, int dtype, long long rows, int C, void* stream);
+int ssl4gie_bn_bwd_apply(const void* dy, int mask_kind, const void* mask, const void* x, const float* gamma,
+                         const float* beta, const float* mean, const float* rstd, const float* sums, float inv_count,
+                         void* dx, float* workspace, int dtype, long long rows, int C, void* stream);
 /* The exchange's arithmetic as ONE launch: gathered [world][2C + 1] = every rank's (mean[C], biased var[C],
  * row count) -> pooled mean / rstd (ranks may hold different row counts), the total row count (device
  * scalar) and, if given, the running statistics (unbiased variance, momentum) — what torch.nn.SyncBatchNorm
@@ -525,68 +546,19 @@ int ssl4gie_bn_stats(const void* x, float* mean, float* var, float* workspace, i
 int ssl4gie_bn_combine_stats(const float* gathered, int world, int C, float eps, float momentum,
                              float* running_mean, float* running_var, float* mean, float* rstd, float* total,
                              void* stream);
-int ssl4gie_bn_bwd_reduce(const void* dy, const void* y, const void* x, const float* mean,
-                          const float* rstd, void* dres, float* sums, int relu, float* workspace,
-                          int dtype, long long rows, int C, void* stream);
-int ssl4gie_bn_bwd_apply(const void* dy, const void* y, const void* x, const float* gamma,
-                         const float* mean, const float* rstd, const float* sums, float inv_count,
-                         void* dx, int relu, float* workspace, int dtype, long long rows, int C,
-                         void* stream);
-/* The two SyncBatchNorm backward halves for BatchNorm + ReLU without a residual input, with the ReLU mask rebuilt
- * from x and the forward's coefficients (gamma, beta and the GLOBAL mean / rstd) as ssl4gie_bn_bwd_xmask does:
- * the ReLU output is read by neither pass. */
-int ssl4gie_bn_bwd_reduce_xmask(const void* dy, const void* x, const float* gamma, const float* beta,
-                                const float* mean, const float* rstd, float* sums, float* workspace, int dtype,
-                                long long rows, int C, void* stream);
-int ssl4gie_bn_bwd_apply_xmask(const void* dy, const void* x, const float* gamma, const float* beta,
-                               const float* mean, const float* rstd, const float* sums, float inv_count, void* dx,
-                               float* workspace, int dtype, long long rows, int C, void* stream);
-/* SyncBatchNorm with the single-process fusions (ABI 7): the GLOBAL statistics come back from the exchange, so the
- * fused consumers take them instead of computing their own.  coef_stats: (mean, rstd, gamma, beta) -> coef [2][C]
- * (y = x coef[0] + coef[1]) for ssl4gie_bn_maxpool3x3s2_fwd and the SSL4GIE_EPI_AFFINE_AUX_RELU epilogue; apply_bits:
- * y = relu(x coef[0] + coef[1] (+ res)) and the ReLU bit map of ssl4gie_bn_fwd_partials_bits (bf16); bwd_reduce_bits:
- * ssl4gie_bn_bwd_reduce with the mask read from that bit map (dres = the masked gradient, then ssl4gie_bn_bwd_apply
- * on dres with relu = 0).  Reference: torch.nn.SyncBatchNorm (convert_sync_batchnorm, Models/moco_v3/main_moco.py:196,
- * Depth_estimation/train_depth.py:225). */
-int ssl4gie_bn_coef_stats(const float* mean, const float* rstd, const float* gamma, const float* beta, float* coef,
-                          int C, void* stream);
-int ssl4gie_bn_apply_bits(const void* x, const float* coef, const void* res, void* y, unsigned char* relu_bits,
-                          int dtype, long long rows, int C, void* stream);
-int ssl4gie_bn_bwd_reduce_bits(const void* dy, const unsigned char* relu_bits, const void* x, const float* mean,
-                               const float* rstd, void* dres, float* sums, float* workspace, int dtype,
-                               long long rows, int C, void* stream);
 /* MoCo._update_momentum_encoder (moco/builder.py:57-61): dst = dst m + src (1 - m), fp32, over a
  * whole parameter-arena slice */
 int ssl4gie_ema_update(float* dst, const float* src, float m, long long n, void* stream);
 /* MaxPool2d(3, stride 2, pad 1) with the argmax window position saved (first maximum in row-major
  * scan order); backward in gather form.  Global average pool -> fp32 [B, C] and its gradient. */
-/* The same forward / SyncBatchNorm statistics with the batch statistics taken from per-128-row
- * partial sums `partial` [parts][2][C] written by the producing GEMM (ssl4gie_gemm_desc::colstats)
- * instead of a pass over x.  workspace: ssl4gie_bn_workspace_bytes(rows, C). */
-int ssl4gie_bn_fwd_partials(const void* x, const float* partial, int parts, const float* gamma,
-                            const float* beta, const void* res, void* y, float* mean, float* rstd,
-                            float* running_mean, float* running_var, float momentum, float eps,
-                            int relu, float* workspace, int dtype, long long rows, int C,
-                            void* stream);
-/* The statistics half of ssl4gie_bn_fwd_partials alone: mean / rstd / running statistics and coef [2][C] with
- * y = x coef[0][c] + coef[1][c], for a consumer that applies the normalisation itself — the
- * SSL4GIE_EPI_AFFINE_AUX_RELU epilogue of the 1x1 convolution recomputed after its statistics-only product
- * (torchvision Bottleneck conv3 + bn3 (+ identity, ReLU) and downsample under torch.no_grad(): MoCo's momentum
- * encoder, moco/builder.py:127-135). */
-int ssl4gie_bn_coef_partials(const float* partial, int parts, const float* gamma, const float* beta,
-                             float* mean, float* rstd, float* running_mean, float* running_var,
-                             float momentum, float eps, float* coef, float* workspace, long long rows, int C,
-                             void* stream);
-int ssl4gie_bn_stats_partials(const float* partial, int parts, float* mean, float* var,
-                              float* workspace, long long rows, int C, void* stream);
 int ssl4gie_maxpool3x3s2_fwd(const void* x, void* y, unsigned char* arg, int dtype, int B, int H,
                              int W, int C, void* stream);
 int ssl4gie_maxpool3x3s2_bwd(const void* dy, const unsigned char* arg, void* dx, int dtype, int B,
                              int H, int W, int C, void* stream);
-/* The same pool over act(x coef[0][c] + coef[1][c]), act = ReLU if `relu` (coef [2][C] as ssl4gie_bn_coef_partials
+/* The same pool over act(x coef[0][c] + coef[1][c]), act = ReLU if `relu` (coef [2][C] as the coefficients-only ssl4gie_bn_fwd
  * writes it): torchvision ResNet's bn1 -> relu -> maxpool behind the stem convolution in ONE pass over the
  * convolution's output — the normalised map is never written (the backward rebuilds its ReLU mask from the
- * convolution output: ssl4gie_bn_bwd_xmask).  Values and argmax equal ssl4gie_bn_fwd_partials followed by
+ * convolution output: ssl4gie_bn_bwd with MASK_X).  Values and argmax equal ssl4gie_bn_fwd (FROM_PARTIALS) followed by
  * ssl4gie_maxpool3x3s2_fwd bit for bit.  C % 8 == 0 (bf16) / C % 4 == 0 (fp32). */
 int ssl4gie_bn_maxpool3x3s2_fwd(const void* x, const float* coef, int relu, void* y, unsigned char* arg,
                                 int dtype, int B, int H, int W, int C, void* stream);

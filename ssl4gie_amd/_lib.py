@@ -12,7 +12,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libssl4gie_hip.so")
 # the one copy of the ABI revision on the Python side: build(), the tests and load() compare the
 # library's ssl4gie_abi_version() with it (include/ssl4gie_hip.h documents the history)
-ABI_VERSION = 11
+ABI_VERSION = 12
 
 PROF_KINDS = 7  # SSL4GIE_PROF_KINDS: entries of the launch profiler's arrays
 
@@ -20,6 +20,8 @@ F32, BF16 = 0, 1
 BWD_ACCUMULATE, BWD_DEFER_WGRAD, BWD_NO_JOIN = 1, 2, 4
 EPI_NONE, EPI_BIAS, EPI_BIAS_GELU, EPI_BIAS_RESIDUAL, EPI_DGELU, EPI_BIAS_GELU_GRAD, EPI_MUL_AUX, \
     EPI_RELU_MASK_AUX, EPI_ADD_AUX, EPI_AFFINE_AUX_RELU = range(10)
+BN_FROM_X, BN_FROM_PARTIALS, BN_FROM_STATS, BN_FROM_COEF = range(4)   # ssl4gie_bn_fwd: source of the normalisation
+BN_MASK_NONE, BN_MASK_Y, BN_MASK_X, BN_MASK_BITS = range(4)           # backward: source of the ReLU mask
 
 vp, i32, i64, f32, sz = C.c_void_p, C.c_int, C.c_longlong, C.c_float, C.c_size_t
 
@@ -124,30 +126,18 @@ PROTOTYPES = {
     "ssl4gie_stem_im2col7x7": (i32, [vp, vp, i32, i32, i32, i32, i64, vp]),
     "ssl4gie_subsample2": (i32, [vp, vp, i32, i32, i32, i32, i32, i32, vp]),
     "ssl4gie_bn_workspace_bytes": (sz, [i64, i32]),
-    "ssl4gie_bn_fwd": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, vp, f32, f32, i32, i32, vp, i32, i64, i32, vp]),
-    "ssl4gie_bn_bwd": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, vp, i32, i64, i32, vp]),
-    "ssl4gie_bn_stats": (i32, [vp, vp, vp, vp, i32, i64, i32, vp]),
-    "ssl4gie_bn_fwd_partials_bits": (i32, [vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, f32, f32, vp, i32, i64,
-                                           i32, vp]),
-    "ssl4gie_bn_bwd_bits": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, vp, i32, i64, i32, vp]),
-    "ssl4gie_bn_bwd_xmask": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, vp, i32, i64, i32, vp]),
-    "ssl4gie_bn_bwd_reduce_xmask": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, i32, i64, i32, vp]),
-    "ssl4gie_bn_bwd_apply_xmask": (i32, [vp, vp, vp, vp, vp, vp, vp, f32, vp, vp, i32, i64, i32, vp]),
-    "ssl4gie_bn_bwd_reduce": (i32, [vp, vp, vp, vp, vp, vp, vp, i32, vp, i32, i64, i32, vp]),
-    "ssl4gie_bn_coef_stats": (i32, [vp, vp, vp, vp, vp, i32, vp]),
-    "ssl4gie_bn_apply_bits": (i32, [vp, vp, vp, vp, vp, i32, i64, i32, vp]),
-    "ssl4gie_bn_bwd_reduce_bits": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, i32, i64, i32, vp]),
-    "ssl4gie_bn_bwd_apply": (i32, [vp, vp, vp, vp, vp, vp, vp, f32, vp, i32, vp, i32, i64, i32, vp]),
+    "ssl4gie_bn_fwd": (i32, [i32, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, f32, f32, i32, vp, i32, i64, i32,
+                             vp]),
+    "ssl4gie_bn_stats": (i32, [vp, vp, i32, vp, vp, vp, i32, i64, i32, vp]),
+    "ssl4gie_bn_bwd": (i32, [vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, vp, i32, i64, i32, vp]),
+    "ssl4gie_bn_bwd_reduce": (i32, [vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i64, i32, vp]),
+    "ssl4gie_bn_bwd_apply": (i32, [vp, i32, vp, vp, vp, vp, vp, vp, vp, f32, vp, vp, i32, i64, i32, vp]),
     "ssl4gie_ema_update": (i32, [vp, vp, f32, i64, vp]),
     "ssl4gie_maxpool3x3s2_fwd": (i32, [vp, vp, vp, i32, i32, i32, i32, i32, vp]),
     "ssl4gie_bn_maxpool3x3s2_fwd": (i32, [vp, vp, i32, vp, vp, i32, i32, i32, i32, i32, vp]),
     "ssl4gie_maxpool3x3s2_bwd": (i32, [vp, vp, vp, i32, i32, i32, i32, i32, vp]),
     "ssl4gie_avgpool_fwd": (i32, [vp, vp, i32, i32, i32, i32, vp]),
     "ssl4gie_avgpool_bwd": (i32, [vp, vp, i32, i32, i32, i32, vp]),
-    "ssl4gie_bn_coef_partials": (i32, [vp, i32, vp, vp, vp, vp, vp, vp, f32, f32, vp, vp, i64, i32, vp]),
-    "ssl4gie_bn_fwd_partials": (i32, [vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, f32, f32, i32, vp, i32, i64,
-                                      i32, vp]),
-    "ssl4gie_bn_stats_partials": (i32, [vp, i32, vp, vp, vp, i64, i32, vp]),
     "ssl4gie_adamw_arena": (i32, [vp, vp, vp, vp, vp, vp, vp, i32, f32, f32, f32, i32, i64, vp]),
     "ssl4gie_adamw_arena_lp": (i32, [vp, vp, vp, vp, vp, vp, vp, i32, f32, f32, f32, i32, i64, vp, vp]),
     "ssl4gie_adamw_arena_range": (i32, [vp, vp, vp, vp, vp, vp, vp, i32, f32, f32, f32, i32, i64, i64, vp, vp]),

@@ -736,7 +736,7 @@ static int launch_direct(const Geom& g, const void* x, const void* w2, const flo
     return 0;
 }
 
-// the same convolution over act(x in_coef[0][ci] + in_coef[1][ci]) (in_coef [2][Cin] as ssl4gie_bn_coef_partials
+// the same convolution over act(x in_coef[0][ci] + in_coef[1][ci]) (in_coef [2][Cin] as the coefficients-only ssl4gie_bn_fwd
 // writes it; act = ReLU if relu_in; zero padding of the NORMALISED map): Bottleneck bn1 -> relu -> conv2 with no
 // BatchNorm pass of its own
 extern "C" int ssl4gie_conv3x3_direct_fwd_affine(const void* x, const float* in_coef, const void* w2,

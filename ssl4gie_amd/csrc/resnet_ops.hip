@@ -6,7 +6,7 @@
 //
 //   stem_im2col7x7   fp32 NCHW image -> patch matrix of conv1 (7x7, stride 2, pad 3), K = 147 (+pad)
 //   subsample2       rows of a stride-2 1x1 convolution (downsample.0) and its gradient
-//   bn_stats         per-channel sum / sum of squares partials  (+ finalize: mean, rstd)
+//   bn_stats         per-channel sum / sum of squares partials  (+ tail: mean, rstd, coefficients)
 //   bn_apply         y = act((x - mean) rstd gamma + beta (+ residual))     act = ReLU | id
 //   bn_bwd_reduce    partials of sum(dy) and sum(dy * xhat) over the rows (dy already ReLU-masked)
 //   bn_bwd_apply     dx = gamma rstd (g - mean(g) - xhat mean(g xhat)); optional dres = g
@@ -213,26 +213,6 @@ __global__ __launch_bounds__(256) void bn_stats_kernel(const T* __restrict__ x,
             st4(p + m.c + j, f32x4{s[j], s[j + 1], s[j + 2], s[j + 3]});
             st4(p + C + m.c + j, f32x4{q[j], q[j + 1], q[j + 2], q[j + 3]});
         }
-    }
-}
-// sums [2][C] -> mean, rstd (biased variance, as F.batch_norm normalises with), and the running
-// statistics update of nn.BatchNorm2d (momentum, unbiased variance) when running_* are given
-__global__ void bn_finalize_kernel(const float* __restrict__ sums, const float* __restrict__ pivot,
-                                   float* __restrict__ mean, float* __restrict__ rstd,
-                                   float* __restrict__ running_mean, float* __restrict__ running_var,
-                                   float count, float eps, float momentum, int C) {
-    const int c = blockIdx.x * blockDim.x + threadIdx.x;
-    if (c >= C) return;
-    const float d = sums[c] / count;
-    float var = sums[C + c] / count - d * d;
-    var = var > 0.f ? var : 0.f;
-    const float m = pivot[c] + d;
-    mean[c] = m;
-    rstd[c] = rsqrtf(var + eps);
-    if (running_mean) {
-        const float unbiased = count > 1.f ? var * count / (count - 1.f) : var;
-        running_mean[c] = (1.f - momentum) * running_mean[c] + momentum * m;
-        running_var[c] = (1.f - momentum) * running_var[c] + momentum * unbiased;
     }
 }
 // per-channel affine of the normalisation: y = x * coef[c] + coef[C + c]
@@ -798,129 +778,6 @@ static int bn_fold(const float* partial, int parts, float* scratch, int C, hipSt
     *out = scratch; *nout = BN_FOLD;
     return 0;
 }
-extern "C" size_t ssl4gie_bn_workspace_bytes(long long rows, int C) {
-    size_t parts = (size_t)bn_parts(rows, C);
-    if (parts < 64) parts = 64;  // the partials paths fold into 64 x 2C floats of this workspace
-    // coef 3C, partials parts x 2C, sums 2C, pivot C (backward: mask coefficients, copy of mean), fold scratch 64 x 2C
-    return ((parts + 1) * 2 + 1 + 3 + 2 * BN_FOLD) * C * sizeof(float);
-}
-// forward: statistics over the rows of x [rows, C] (biased variance), optional running-stat update,
-// y = act(xhat gamma + beta (+ res)); mean / rstd [C] are kept for backward
-extern "C" int ssl4gie_bn_fwd(const void* x, const float* gamma, const float* beta, const void* res,
-                              void* y, float* mean, float* rstd, float* running_mean,
-                              float* running_var, float momentum, float eps, int relu,
-                              int training, float* workspace, int dtype, long long rows, int C,
-                              void* stream) {
-    REQUIRE(x && y && mean && rstd && workspace && rdt(dtype) && rows > 0 && C > 0 && C % 8 == 0);
-    hipStream_t st = (hipStream_t)stream;
-    float* coef = workspace;  // workspace: [coef 3C][partials parts x 2C][sums 2C][pivot C]
-    const long long total = rows * C;
-    // algorithmic bytes: (statistics pass: x) + apply: x (+ res) -> y
-    ProfScope prof(PROF_BN, (double)total * (dtype == SSL4GIE_BF16 ? 2 : 4) * ((training ? 1 : 0) + 2 + (res ? 1 : 0)), st);
-    if (!training) {  // evaluation: mean / rstd are INPUTS (running statistics prepared by the caller)
-        hipLaunchKernelGGL(bn_fwd_coef_kernel, dim3((C + 255) / 256), dim3(256), 0, st, mean, rstd,
-                           gamma, beta, coef, C);
-        LAUNCH_CHECK();
-        RN_LAUNCH(dtype, bn_apply_kernel, total / rvn(dtype), (const T*)x, coef, (const T*)res, (T*)y,
-                  relu, C, total, (unsigned char*)nullptr);
-        return 0;
-    }
-    const int parts = bn_parts(rows, C);
-    dim3 grid(bn_strips(C, dtype), parts), block(256);
-    float* partial = workspace + 3 * (size_t)C;
-    float* sums = partial + (size_t)parts * 2 * C;
-    float* pivot = sums + 2 * C;
-    if (dtype == SSL4GIE_BF16)
-        hipLaunchKernelGGL(bn_stats_kernel<bf16_t>, grid, block, 0, st, (const bf16_t*)x, partial,
-                           pivot, rows, C);
-    else
-        hipLaunchKernelGGL(bn_stats_kernel<float>, grid, block, 0, st, (const float*)x, partial,
-                           pivot, rows, C);
-    LAUNCH_CHECK();
-    hipLaunchKernelGGL(bn_fwd_tail_kernel, dim3((C + 63) / 64), bn_tail_block(parts), 0, st, partial, parts, pivot,
-                       gamma, beta, mean, rstd, running_mean, running_var, coef, (float)rows, eps,
-                       momentum, C);
-    LAUNCH_CHECK();
-    RN_LAUNCH(dtype, bn_apply_kernel, total / rvn(dtype), (const T*)x, coef, (const T*)res, (T*)y, relu,
-              C, total, (unsigned char*)nullptr);
-    return 0;
-}
-// backward: dgamma / dbeta (overwritten or accumulated), dx, and (optional) the residual gradient.
-// xmask: BatchNorm + ReLU without a residual input — the ReLU mask is rebuilt from x and the forward's
-// coefficients (gamma, beta, mean, rstd) instead of read from the ReLU output: 5 instead of 7 tensor passes.
-static int bn_bwd_impl(const void* dy, const void* y, const void* x, const float* gamma, const float* beta,
-                       const float* mean, const float* rstd, void* dx, void* dres, float* dgamma,
-                       float* dbeta, int accumulate, int relu, int xmask /* 0: mask from y, 1: from x, 2: y is the forward's bit map (bf16) */,
-                       float* workspace, int dtype, long long rows, int C, hipStream_t st) {
-    const int parts = bn_parts(rows, C);
-    dim3 grid(bn_strips(C, dtype), parts), block(256);
-    // algorithmic bytes: reduce reads dy, x (+ the ReLU output when the mask comes from it; the bit map is 1/16 of
-    // a tensor) and writes dres; apply reads the gradient, x (+ the ReLU output) and writes dx
-    const double bn_es = dtype == SSL4GIE_BF16 ? 2 : 4;
-    const bool bn_masked = relu && dres;
-    ProfScope prof(PROF_BN, (double)rows * C * bn_es * ((2 + ((relu && xmask == 0) ? 1 : 0) + (xmask == 2 ? 0.0625 : 0) + (dres ? 1 : 0)) +
-                                                       (2 + ((relu && xmask == 0 && !bn_masked) ? 1 : 0) + 1)), st);
-    float* coef = workspace;
-    float* partial = workspace + 3 * (size_t)C;
-    float* mcoef = xmask == 1 ? partial + (size_t)parts * 2 * C : nullptr;  // the forward's `sums` slot: free here
-#define BN_REDUCE(T_, XM_)                                                                              \
-    hipLaunchKernelGGL((bn_bwd_reduce_kernel<T_, XM_>), grid, block, 0, st, (const T_*)dy, (const T_*)y, \
-                       (const T_*)x, mean, rstd, (T_*)dres, partial, relu, rows, C, gamma, beta)
-    if (dtype == SSL4GIE_BF16) {
-        if (xmask == 1) BN_REDUCE(bf16_t, 1); else if (xmask == 2) BN_REDUCE(bf16_t, 2); else BN_REDUCE(bf16_t, 0);
-    } else {
-        if (xmask == 1) BN_REDUCE(float, 1); else BN_REDUCE(float, 0);
-    }
-#undef BN_REDUCE
-    LAUNCH_CHECK();
-    // dbeta = sum g, dgamma = sum g xhat, and the dx coefficients, in one launch.  No fold in front: bn_parts caps
-    // the partitions at 1024 <= BN_TAIL_WIDE, so the tail always sums the reduction's partials itself (the fold
-    // belongs to the statistics-from-partials entry points, whose producers hand over thousands of rows)
-    float* mu = partial + ((size_t)parts * 2 + 2) * C;  // the forward's `pivot` slot: free here
-    hipLaunchKernelGGL(bn_bwd_tail_kernel, dim3((C + 63) / 64), bn_tail_block(parts), 0, st, partial, parts, mean,
-                       rstd, gamma, 1.0f / (float)rows, coef, dgamma, dbeta, accumulate, C, beta, mcoef, mu);
-    LAUNCH_CHECK();
-    const long long total = rows * C;
-    // with a residual branch the reduction pass has just written dres = the MASKED gradient (dy or 0, no
-    // rounding): the apply pass reads that one tensor instead of dy and the ReLU output (6 -> 4 B/element
-    // read on the widest BatchNorm of a bottleneck)
-    const bool masked = relu && dres;
-    const void* gsrc = masked ? dres : dy;
-    const void* ysrc = masked ? nullptr : y;
-    const int relu_apply = masked ? 0 : relu;
-    RN_LAUNCH(dtype, bn_bwd_apply_kernel, total / rvn(dtype), (const T*)gsrc, (const T*)ysrc, (const T*)x,
-              coef, (T*)dx, relu_apply, C, total, (const float*)mcoef, (const float*)mu);
-    return 0;
-}
-extern "C" int ssl4gie_bn_bwd(const void* dy, const void* y, const void* x, const float* gamma,
-                              const float* mean, const float* rstd, void* dx, void* dres,
-                              float* dgamma, float* dbeta, int accumulate, int relu,
-                              float* workspace, int dtype, long long rows, int C, void* stream) {
-    REQUIRE(dy && x && mean && rstd && dx && workspace && rdt(dtype) && rows > 0 && C > 0 && C % 8 == 0);
-    REQUIRE(!relu || y);
-    return bn_bwd_impl(dy, y, x, gamma, nullptr, mean, rstd, dx, dres, dgamma, dbeta, accumulate, relu, 0,
-                       workspace, dtype, rows, C, (hipStream_t)stream);
-}
-// BatchNorm (+ residual) + ReLU backward with the ReLU mask from the bit map ssl4gie_bn_fwd_partials_bits wrote
-// (one byte per 8 elements) instead of the ReLU output: the reduction pass streams dy, x and 1/16 of a tensor
-// (bf16 maps only; `dres` is required: the apply pass reads the masked gradient the reduction wrote)
-extern "C" int ssl4gie_bn_bwd_bits(const void* dy, const unsigned char* relu_bits, const void* x,
-                                   const float* gamma, const float* mean, const float* rstd, void* dx,
-                                   void* dres, float* dgamma, float* dbeta, int accumulate, float* workspace,
-                                   int dtype, long long rows, int C, void* stream) {
-    REQUIRE(dy && relu_bits && x && mean && rstd && dx && dres && workspace && dtype == SSL4GIE_BF16 && rows > 0 &&
-            C > 0 && C % 8 == 0);
-    return bn_bwd_impl(dy, relu_bits, x, gamma, nullptr, mean, rstd, dx, dres, dgamma, dbeta, accumulate, 1, 2,
-                       workspace, dtype, rows, C, (hipStream_t)stream);
-}
-extern "C" int ssl4gie_bn_bwd_xmask(const void* dy, const void* x, const float* gamma, const float* beta,
-                                    const float* mean, const float* rstd, void* dx, float* dgamma,
-                                    float* dbeta, int accumulate, float* workspace, int dtype,
-                                    long long rows, int C, void* stream) {
-    REQUIRE(dy && x && mean && rstd && dx && workspace && rdt(dtype) && rows > 0 && C > 0 && C % 8 == 0);
-    return bn_bwd_impl(dy, nullptr, x, gamma, beta, mean, rstd, dx, nullptr, dgamma, dbeta, accumulate, 1, 1,
-                       workspace, dtype, rows, C, (hipStream_t)stream);
-}
 extern "C" int ssl4gie_maxpool3x3s2_fwd(const void* x, void* y, unsigned char* arg, int dtype, int B,
                                         int H, int W, int C, void* stream) {
     REQUIRE(x && y && arg && rdt(dtype) && B > 0 && H > 0 && W > 0 && C > 0);
@@ -936,7 +793,7 @@ extern "C" int ssl4gie_maxpool3x3s2_fwd(const void* x, void* y, unsigned char* a
     RN_LAUNCH(dtype, maxpool_fwd_kernel, total, (const T*)x, (T*)y, arg, H, W, C, Ho, Wo, total);
     return 0;
 }
-// MaxPool2d(3, 2, 1) over act(x coef[0][c] + coef[1][c]) (coef [2][C] from ssl4gie_bn_coef_partials): BatchNorm
+// MaxPool2d(3, 2, 1) over act(x coef[0][c] + coef[1][c]) (coef [2][C] from the coefficients-only ssl4gie_bn_fwd): BatchNorm
 // + ReLU + pool of the ResNet stem in one pass over the convolution's output
 extern "C" int ssl4gie_bn_maxpool3x3s2_fwd(const void* x, const float* coef, int relu, void* y,
                                            unsigned char* arg, int dtype, int B, int H, int W, int C,
@@ -1004,9 +861,7 @@ extern "C" int ssl4gie_ema_update(float* dst, const float* src, float m, long lo
     LAUNCH_CHECK();
     return 0;
 }
-// SyncBatchNorm, forward half: LOCAL batch statistics only (mean, biased var [C]); the caller
-// combines them across ranks (counts may differ) and then calls ssl4gie_bn_fwd(training = 0) with
-// the global mean / rstd.
+// sums [2][C] (about `pivot`, or about 0 without one) -> mean, biased var: the end of ssl4gie_bn_stats
 __global__ void bn_local_stats_kernel(const float* __restrict__ sums, const float* __restrict__ pivot,
                                       float* __restrict__ mean, float* __restrict__ var, float count,
                                       int C) {
@@ -1017,238 +872,257 @@ __global__ void bn_local_stats_kernel(const float* __restrict__ sums, const floa
     mean[c] = (pivot ? pivot[c] : 0.f) + d;
     var[c] = v > 0.f ? v : 0.f;
 }
-extern "C" int ssl4gie_bn_stats(const void* x, float* mean, float* var, float* workspace, int dtype,
-                                long long rows, int C, void* stream) {
-    REQUIRE(x && mean && var && workspace && rdt(dtype) && rows > 0 && C > 0 && C % 8 == 0);
-    hipStream_t st = (hipStream_t)stream;
-    const int parts = bn_parts(rows, C);
-    dim3 grid(bn_strips(C, dtype), parts), block(256);
-    float* partial = workspace + 3 * (size_t)C;
-    float* sums = partial + (size_t)parts * 2 * C;
-    float* pivot = sums + 2 * C;
-    if (dtype == SSL4GIE_BF16)
-        hipLaunchKernelGGL(bn_stats_kernel<bf16_t>, grid, block, 0, st, (const bf16_t*)x, partial,
-                           pivot, rows, C);
-    else
-        hipLaunchKernelGGL(bn_stats_kernel<float>, grid, block, 0, st, (const float*)x, partial,
-                           pivot, rows, C);
-    LAUNCH_CHECK();
-    int rc = ssl4gie_internal_reduce_partials(partial, sums, parts, 2 * C, (size_t)2 * C, 0, st);
-    if (rc) return rc;
-    hipLaunchKernelGGL(bn_local_stats_kernel, dim3((C + 255) / 256), dim3(256), 0, st, sums, pivot,
-                       mean, var, (float)rows, C);
-    LAUNCH_CHECK();
-    return 0;
-}
-// training-mode forward with the statistics taken from `partial` [parts][2][C] instead of a pass
-// over x; everything else as ssl4gie_bn_fwd.  workspace: ssl4gie_bn_workspace_bytes(rows, C).
-static int bn_fwd_partials_impl(const void* x, const float* partial, int parts, const float* gamma,
-                                const float* beta, const void* res, void* y, float* mean,
-                                float* rstd, float* running_mean, float* running_var,
-                                float momentum, float eps, int relu, float* workspace, int dtype,
-                                long long rows, int C, void* stream, unsigned char* relu_bits);
-extern "C" int ssl4gie_bn_fwd_partials(const void* x, const float* partial, int parts, const float* gamma,
-                                       const float* beta, const void* res, void* y, float* mean,
-                                       float* rstd, float* running_mean, float* running_var,
-                                       float momentum, float eps, int relu, float* workspace, int dtype,
-                                       long long rows, int C, void* stream) {
-    return bn_fwd_partials_impl(x, partial, parts, gamma, beta, res, y, mean, rstd, running_mean, running_var,
-                                momentum, eps, relu, workspace, dtype, rows, C, stream, nullptr);
-}
-// ... and relu_bits [rows * C / 8] bytes: bit j of byte i = (y[8 i + j] > 0), for ssl4gie_bn_bwd_bits (bf16 maps)
-extern "C" int ssl4gie_bn_fwd_partials_bits(const void* x, const float* partial, int parts, const float* gamma,
-                                            const float* beta, const void* res, void* y,
-                                            unsigned char* relu_bits, float* mean, float* rstd,
-                                            float* running_mean, float* running_var, float momentum, float eps,
-                                            float* workspace, int dtype, long long rows, int C, void* stream) {
-    REQUIRE(relu_bits && dtype == SSL4GIE_BF16);
-    return bn_fwd_partials_impl(x, partial, parts, gamma, beta, res, y, mean, rstd, running_mean, running_var,
-                                momentum, eps, 1, workspace, dtype, rows, C, stream, relu_bits);
-}
-static int bn_fwd_partials_impl(const void* x, const float* partial, int parts, const float* gamma,
-                                const float* beta, const void* res, void* y, float* mean,
-                                float* rstd, float* running_mean, float* running_var,
-                                float momentum, float eps, int relu, float* workspace, int dtype,
-                                long long rows, int C, void* stream, unsigned char* relu_bits) {
-    REQUIRE(x && partial && parts > 0 && y && mean && rstd && workspace && rdt(dtype) && rows > 0 &&
-            C > 0 && C % 8 == 0);
-    hipStream_t st = (hipStream_t)stream;
-    ProfScope prof(PROF_BN, (double)rows * C * (dtype == SSL4GIE_BF16 ? 2 : 4) * (2 + (res ? 1 : 0)), st);  // x (+ res) -> y
-    float* coef = workspace;
-    float* scratch = workspace + 3 * (size_t)C;  // >= BN_FOLD x 2C floats by construction of the size
-    const float* pp; int np;
-    int rc = bn_fold(partial, parts, scratch, C, st, &pp, &np);
-    if (rc) return rc;
-    hipLaunchKernelGGL(bn_fwd_tail_kernel, dim3((C + 63) / 64), bn_tail_block(np), 0, st, pp, np,
-                       (const float*)nullptr, gamma, beta, mean, rstd, running_mean, running_var, coef,
-                       (float)rows, eps, momentum, C);
-    LAUNCH_CHECK();
-    const long long total = rows * C;
-    RN_LAUNCH(dtype, bn_apply_kernel, total / rvn(dtype), (const T*)x, coef, (const T*)res, (T*)y, relu,
-              C, total, relu_bits);
-    return 0;
-}
-// the statistics half of ssl4gie_bn_fwd_partials alone: mean / rstd / running statistics and the normalisation
-// coefficients coef [2][C] (y = x coef[0][c] + coef[1][c]) for a consumer that applies them itself — the
-// SSL4GIE_EPI_AFFINE_AUX_RELU epilogue of the 1x1 convolution recomputed after its statistics-only product
-extern "C" int ssl4gie_bn_coef_partials(const float* partial, int parts, const float* gamma, const float* beta,
-                                        float* mean, float* rstd, float* running_mean, float* running_var,
-                                        float momentum, float eps, float* coef, float* workspace,
-                                        long long rows, int C, void* stream) {
-    REQUIRE(partial && parts > 0 && mean && rstd && coef && workspace && rows > 0 && C > 0 && C % 8 == 0);
-    hipStream_t st = (hipStream_t)stream;
-    float* scratch = workspace + 3 * (size_t)C;
-    const float* pp; int np;
-    int rc = bn_fold(partial, parts, scratch, C, st, &pp, &np);
-    if (rc) return rc;
-    hipLaunchKernelGGL(bn_fwd_tail_kernel, dim3((C + 63) / 64), bn_tail_block(np), 0, st, pp, np,
-                       (const float*)nullptr, gamma, beta, mean, rstd, running_mean, running_var, coef,
-                       (float)rows, eps, momentum, C);
-    LAUNCH_CHECK();
-    return 0;
-}
-// SyncBatchNorm's local (mean, biased var) from the same partials
-extern "C" int ssl4gie_bn_stats_partials(const float* partial, int parts, float* mean, float* var,
-                                         float* workspace, long long rows, int C, void* stream) {
-    REQUIRE(partial && parts > 0 && mean && var && workspace && rows > 0 && C > 0 && C % 8 == 0);
-    hipStream_t st = (hipStream_t)stream;
-    float* scratch = workspace + 3 * (size_t)C;
-    float* sums = scratch + (size_t)BN_FOLD * 2 * C;
-    const float* pp; int np;
-    int rc = bn_fold(partial, parts, scratch, C, st, &pp, &np);
-    if (rc) return rc;
-    rc = ssl4gie_internal_reduce_partials(pp, sums, np, 2 * C, (size_t)2 * C, 0, st);
-    if (rc) return rc;
-    hipLaunchKernelGGL(bn_local_stats_kernel, dim3((C + 255) / 256), dim3(256), 0, st, sums,
-                       (const float*)nullptr, mean, var, (float)rows, C);
-    LAUNCH_CHECK();
-    return 0;
-}
-// SyncBatchNorm, backward halves: sums[0][c] = sum g, sums[1][c] = sum g xhat over the LOCAL rows
-// (the caller all-reduces them), then dx with the GLOBAL sums and 1 / (global row count).
-extern "C" int ssl4gie_bn_bwd_reduce(const void* dy, const void* y, const void* x, const float* mean,
-                                     const float* rstd, void* dres, float* sums, int relu,
-                                     float* workspace, int dtype, long long rows, int C,
-                                     void* stream) {
-    REQUIRE(dy && x && mean && rstd && sums && workspace && rdt(dtype) && rows > 0 && C > 0 && C % 8 == 0);
-    REQUIRE(!relu || y);
-    hipStream_t st = (hipStream_t)stream;
-    const int parts = bn_parts(rows, C);
-    dim3 grid(bn_strips(C, dtype), parts), block(256);
-    float* partial = workspace + 3 * (size_t)C;
-    if (dtype == SSL4GIE_BF16)
-        hipLaunchKernelGGL((bn_bwd_reduce_kernel<bf16_t, 0>), grid, block, 0, st, (const bf16_t*)dy,
-                           (const bf16_t*)y, (const bf16_t*)x, mean, rstd, (bf16_t*)dres, partial,
-                           relu, rows, C, (const float*)nullptr, (const float*)nullptr);
-    else
-        hipLaunchKernelGGL((bn_bwd_reduce_kernel<float, 0>), grid, block, 0, st, (const float*)dy,
-                           (const float*)y, (const float*)x, mean, rstd, (float*)dres, partial, relu,
-                           rows, C, (const float*)nullptr, (const float*)nullptr);
-    LAUNCH_CHECK();
-    return ssl4gie_internal_reduce_partials(partial, sums, parts, 2 * C, (size_t)2 * C, 0, st);
-}
-// ... and for BatchNorm + ReLU without a residual input, with the mask rebuilt from x and the forward's
-// coefficients (as ssl4gie_bn_bwd_xmask; mean / rstd are the GLOBAL statistics the forward normalised with)
-extern "C" int ssl4gie_bn_bwd_reduce_xmask(const void* dy, const void* x, const float* gamma, const float* beta,
-                                           const float* mean, const float* rstd, float* sums,
-                                           float* workspace, int dtype, long long rows, int C, void* stream) {
-    REQUIRE(dy && x && mean && rstd && sums && workspace && rdt(dtype) && rows > 0 && C > 0 && C % 8 == 0);
-    hipStream_t st = (hipStream_t)stream;
-    const int parts = bn_parts(rows, C);
-    dim3 grid(bn_strips(C, dtype), parts), block(256);
-    float* partial = workspace + 3 * (size_t)C;
-    if (dtype == SSL4GIE_BF16)
-        hipLaunchKernelGGL((bn_bwd_reduce_kernel<bf16_t, 1>), grid, block, 0, st, (const bf16_t*)dy,
-                           (const bf16_t*)nullptr, (const bf16_t*)x, mean, rstd, (bf16_t*)nullptr, partial, 1,
-                           rows, C, gamma, beta);
-    else
-        hipLaunchKernelGGL((bn_bwd_reduce_kernel<float, 1>), grid, block, 0, st, (const float*)dy,
-                           (const float*)nullptr, (const float*)x, mean, rstd, (float*)nullptr, partial, 1, rows,
-                           C, gamma, beta);
-    LAUNCH_CHECK();
-    return ssl4gie_internal_reduce_partials(partial, sums, parts, 2 * C, (size_t)2 * C, 0, st);
-}
-extern "C" int ssl4gie_bn_bwd_apply_xmask(const void* dy, const void* x, const float* gamma, const float* beta,
-                                          const float* mean, const float* rstd, const float* sums,
-                                          float inv_count, void* dx, float* workspace, int dtype,
-                                          long long rows, int C, void* stream) {
-    REQUIRE(dy && x && mean && rstd && sums && dx && workspace && rdt(dtype) && rows > 0 && C > 0 &&
-            C % 8 == 0);
-    hipStream_t st = (hipStream_t)stream;
-    float* mcoef = workspace + 3 * (size_t)C;  // [2][C] behind the dx coefficients
-    float* mu = workspace + 5 * (size_t)C;     // ... and the aligned copy of mean behind them
-    hipLaunchKernelGGL(bn_bwd_coef_kernel, dim3((C + 255) / 256), dim3(256), 0, st, mean, rstd, gamma,
-                       sums, inv_count, workspace, C, mu);
-    LAUNCH_CHECK();
-    hipLaunchKernelGGL(bn_fwd_coef_kernel, dim3((C + 255) / 256), dim3(256), 0, st, mean, rstd, gamma, beta,
-                       mcoef, C);
-    LAUNCH_CHECK();
-    const long long total = rows * C;
-    RN_LAUNCH(dtype, bn_bwd_apply_kernel, total / rvn(dtype), (const T*)dy, (const T*)nullptr, (const T*)x,
-              workspace, (T*)dx, 1, C, total, (const float*)mcoef, (const float*)mu);
-    return 0;
-}
-extern "C" int ssl4gie_bn_bwd_apply(const void* dy, const void* y, const void* x, const float* gamma,
-                                    const float* mean, const float* rstd, const float* sums,
-                                    float inv_count, void* dx, int relu, float* workspace, int dtype,
-                                    long long rows, int C, void* stream) {
-    REQUIRE(dy && x && mean && rstd && sums && dx && workspace && rdt(dtype) && rows > 0 && C > 0 &&
-            C % 8 == 0);
-    REQUIRE(!relu || y);
-    hipStream_t st = (hipStream_t)stream;
-    float* mu = workspace + 5 * (size_t)C;  // aligned copy of mean behind the coefficients
-    hipLaunchKernelGGL(bn_bwd_coef_kernel, dim3((C + 255) / 256), dim3(256), 0, st, mean, rstd, gamma,
-                       sums, inv_count, workspace, C, mu);
-    LAUNCH_CHECK();
-    const long long total = rows * C;
-    RN_LAUNCH(dtype, bn_bwd_apply_kernel, total / rvn(dtype), (const T*)dy, (const T*)y, (const T*)x,
-              workspace, (T*)dx, relu, C, total, (const float*)nullptr, (const float*)mu);
-    return 0;
+// ---- BatchNorm entry points (ABI 12; the product they span is described in include/ssl4gie_hip.h) -----------------
+// The workspace, in floats: [coef 3C][partials parts x 2C][sums 2C][pivot C].  Caller-supplied partials are folded
+// into the partials region (BN_FOLD x 2C), the backward keeps the forward's mask coefficients in `sums` and its
+// aligned copy of mean in `pivot` (both free there), and the apply half, which has no partials, is the layout with
+// parts = 0.
+struct BnWs {
+    float *coef, *partial, *sums, *pivot;
+    BnWs(float* w, size_t parts, int C)
+        : coef(w), partial(w + 3 * (size_t)C), sums(partial + parts * 2 * C), pivot(sums + 2 * (size_t)C) {}
+    static size_t floats(size_t parts, int C) { return ((parts + 1) * 2 + 1 + 3 + 2 * BN_FOLD) * C; }
+};
+extern "C" size_t ssl4gie_bn_workspace_bytes(long long rows, int C) {
+    size_t parts = (size_t)bn_parts(rows, C);
+    if (parts < BN_FOLD) parts = BN_FOLD;  // the partials paths fold into BN_FOLD x 2C floats of this workspace
+    return BnWs::floats(parts, C) * sizeof(float);
 }
 
-// ---- SyncBatchNorm with the single-process fusions (round 6) ----------------------------------------------------
-// With world_size > 1 the statistics cross an exchange between the producing GEMM's partials and the apply, so the
-// fused forms take the GLOBAL (mean, rstd) the exchange returned instead of computing their own:
-//   ssl4gie_bn_coef_stats      (mean, rstd, gamma, beta) -> coef [2][C] for a consumer that applies it itself: the
-//                              bn1 -> relu -> maxpool pass of the stem (ssl4gie_bn_maxpool3x3s2_fwd) and the
-//                              SSL4GIE_EPI_AFFINE_AUX_RELU epilogue of the momentum encoder's widening 1x1 products;
-//   ssl4gie_bn_apply_bits      y = relu(x coef[0] + coef[1] (+ res)) and the ReLU bit map of ssl4gie_bn_fwd_partials_bits;
-//   ssl4gie_bn_bwd_reduce_bits the first backward half of ssl4gie_bn_bwd_reduce with the mask from that bit map
-//                              (dres = the masked gradient; the second half is ssl4gie_bn_bwd_apply on dres, relu 0).
-// Reference: torch.nn.SyncBatchNorm via convert_sync_batchnorm, Models/moco_v3/main_moco.py:196,
-// Depth_estimation/train_depth.py:225.
-extern "C" int ssl4gie_bn_coef_stats(const float* mean, const float* rstd, const float* gamma, const float* beta,
-                                     float* coef, int C, void* stream) {
-    REQUIRE(mean && rstd && coef && C > 0);
-    hipLaunchKernelGGL(bn_fwd_coef_kernel, dim3((C + 255) / 256), dim3(256), 0, (hipStream_t)stream, mean, rstd,
-                       gamma, beta, coef, C);
+// ---- argument validation: a combination no kernel serves is SSL4GIE_EARG
+static bool bn_map_ok(int dtype, long long rows, int C) { return rdt(dtype) && rows > 0 && C > 0 && C % 8 == 0; }
+static bool bn_fwd_ok(int source, const void* x, const float* partial, int parts, const float* gamma,
+                      const float* beta, const void* res, const void* y, const unsigned char* relu_bits,
+                      const float* coef, const float* mean, const float* rstd, const float* running_mean,
+                      const float* running_var, int relu, const float* workspace, int dtype, long long rows, int C) {
+    if (source < SSL4GIE_BN_FROM_X || source > SSL4GIE_BN_FROM_COEF) return false;
+    if ((source == SSL4GIE_BN_FROM_PARTIALS) != (partial != nullptr) || (partial && parts <= 0)) return false;
+    if (source == SSL4GIE_BN_FROM_STATS && (running_mean || running_var)) return false;  // nothing to update
+    if (source == SSL4GIE_BN_FROM_STATS && !y)  // coefficients of given statistics: no map, no workspace
+        return mean && rstd && coef && C > 0 && !x && !res && !relu_bits && !workspace;
+    if (rows <= 0 || C <= 0 || C % 8 != 0) return false;
+    if (source == SSL4GIE_BN_FROM_COEF)  // given coefficients: the apply pass with the bit map (bf16)
+        return x && coef && y && relu_bits && relu && dtype == SSL4GIE_BF16 && !gamma && !beta && !mean && !rstd &&
+               !running_mean && !running_var && !workspace;
+    if (!mean || !rstd || !workspace) return false;
+    if (!y)  // coefficients only, into the caller's [2][C]: from partials (a statistics pass over x always writes y)
+        return source == SSL4GIE_BN_FROM_PARTIALS && coef && !x && !res && !relu_bits;
+    if (!x || coef || !rdt(dtype)) return false;
+    return !relu_bits || (source == SSL4GIE_BN_FROM_PARTIALS && relu && dtype == SSL4GIE_BF16);
+}
+// what the three backward functions share; `dres` is NULL in the apply half
+static bool bn_bwd_ok(const void* dy, int mask_kind, const void* mask, const void* x, const float* beta,
+                      const float* mean, const float* rstd, const void* dres, const float* workspace, int dtype,
+                      long long rows, int C) {
+    if (!(dy && x && mean && rstd && workspace && bn_map_ok(dtype, rows, C))) return false;
+    switch (mask_kind) {
+    case SSL4GIE_BN_MASK_NONE: return !mask && !beta;
+    case SSL4GIE_BN_MASK_Y: return mask && !beta;
+    case SSL4GIE_BN_MASK_X: return !mask && !dres;  // BatchNorm + ReLU without a residual input
+    case SSL4GIE_BN_MASK_BITS: return mask && !beta && dres && dtype == SSL4GIE_BF16;  // dres = the masked gradient
+    }
+    return false;
+}
+
+// ---- launches
+static int bn_launch_stats(const void* x, const BnWs& ws, int parts, int dtype, long long rows, int C,
+                           hipStream_t st) {
+    dim3 grid(bn_strips(C, dtype), parts), block(256);
+    if (dtype == SSL4GIE_BF16)
+        hipLaunchKernelGGL(bn_stats_kernel<bf16_t>, grid, block, 0, st, (const bf16_t*)x, ws.partial, ws.pivot,
+                           rows, C);
+    else
+        hipLaunchKernelGGL(bn_stats_kernel<float>, grid, block, 0, st, (const float*)x, ws.partial, ws.pivot,
+                           rows, C);
     LAUNCH_CHECK();
     return 0;
 }
-extern "C" int ssl4gie_bn_apply_bits(const void* x, const float* coef, const void* res, void* y,
-                                     unsigned char* relu_bits, int dtype, long long rows, int C, void* stream) {
-    REQUIRE(x && coef && y && relu_bits && dtype == SSL4GIE_BF16 && rows > 0 && C > 0 && C % 8 == 0);
-    hipStream_t st = (hipStream_t)stream;
-    ProfScope prof(PROF_BN, (double)rows * C * 2 * (2 + (res ? 1 : 0)), st);
+static int bn_launch_apply(const void* x, const float* coef, const void* res, void* y, int relu,
+                           unsigned char* relu_bits, int dtype, long long rows, int C, hipStream_t st) {
     const long long total = rows * C;
-    RN_LAUNCH(dtype, bn_apply_kernel, total / rvn(dtype), (const T*)x, coef, (const T*)res, (T*)y, 1, C, total,
+    RN_LAUNCH(dtype, bn_apply_kernel, total / rvn(dtype), (const T*)x, coef, (const T*)res, (T*)y, relu, C, total,
               relu_bits);
     return 0;
 }
-extern "C" int ssl4gie_bn_bwd_reduce_bits(const void* dy, const unsigned char* relu_bits, const void* x,
-                                          const float* mean, const float* rstd, void* dres, float* sums,
-                                          float* workspace, int dtype, long long rows, int C, void* stream) {
-    REQUIRE(dy && relu_bits && x && mean && rstd && dres && sums && workspace && dtype == SSL4GIE_BF16 && rows > 0 &&
-            C > 0 && C % 8 == 0);
+template <typename T>
+static int bn_launch_reduce_t(const void* dy, int mask_kind, const void* mask, const void* x, const float* gamma,
+                              const float* beta, const float* mean, const float* rstd, void* dres, float* partial,
+                              dim3 grid, long long rows, int C, hipStream_t st) {
+    const int relu = mask_kind != SSL4GIE_BN_MASK_NONE;
+    auto launch = [&](auto kernel) {
+        hipLaunchKernelGGL(kernel, grid, dim3(256), 0, st, (const T*)dy, (const T*)mask, (const T*)x, mean, rstd,
+                           (T*)dres, partial, relu, rows, C, gamma, beta);
+    };
+    if (mask_kind == SSL4GIE_BN_MASK_X) {
+        launch(bn_bwd_reduce_kernel<T, 1>);
+    } else if (mask_kind == SSL4GIE_BN_MASK_BITS) {
+        if constexpr (sizeof(T) == 2) launch(bn_bwd_reduce_kernel<T, 2>);  // bf16 only (bn_bwd_ok)
+    } else {
+        launch(bn_bwd_reduce_kernel<T, 0>);
+    }
+    LAUNCH_CHECK();
+    return 0;
+}
+// partial[parts][2][C] = this rank's sums of g and g xhat (and dres = g, if given)
+static int bn_launch_reduce(const void* dy, int mask_kind, const void* mask, const void* x, const float* gamma,
+                            const float* beta, const float* mean, const float* rstd, void* dres, float* partial,
+                            int parts, int dtype, long long rows, int C, hipStream_t st) {
+    dim3 grid(bn_strips(C, dtype), parts);
+    return dtype == SSL4GIE_BF16
+               ? bn_launch_reduce_t<bf16_t>(dy, mask_kind, mask, x, gamma, beta, mean, rstd, dres, partial, grid, rows, C, st)
+               : bn_launch_reduce_t<float>(dy, mask_kind, mask, x, gamma, beta, mean, rstd, dres, partial, grid, rows, C, st);
+}
+static int bn_launch_bwd_apply(const void* g, const void* y, const void* x, const float* coef, void* dx, int relu,
+                               const float* mcoef, const float* mu, int dtype, long long rows, int C,
+                               hipStream_t st) {
+    const long long total = rows * C;
+    RN_LAUNCH(dtype, bn_bwd_apply_kernel, total / rvn(dtype), (const T*)g, (const T*)y, (const T*)x, coef, (T*)dx,
+              relu, C, total, mcoef, mu);
+    return 0;
+}
+
+// ---- forward
+// mean / rstd (+ running statistics) and the normalisation coefficients y = x coef[0][c] + coef[1][c] into `coef`
+// (the workspace's region for the forms that write y, the caller's [2][C] for the coefficients-only ones).  The
+// sums are finished by the tail kernel in its fixed wave order; FROM_STATS runs no reduction at all.
+static int bn_fwd_coef(int source, const void* x, const float* partial, int parts, const float* gamma,
+                       const float* beta, float* mean, float* rstd, float* running_mean, float* running_var,
+                       float momentum, float eps, float* coef, float* workspace, int dtype, long long rows, int C,
+                       hipStream_t st) {
+    if (source == SSL4GIE_BN_FROM_STATS) {
+        hipLaunchKernelGGL(bn_fwd_coef_kernel, dim3((C + 255) / 256), dim3(256), 0, st, mean, rstd, gamma, beta,
+                           coef, C);
+        LAUNCH_CHECK();
+        return 0;
+    }
+    const float *pp, *pivot = nullptr;
+    int np, rc;
+    if (source == SSL4GIE_BN_FROM_X) {  // sums about the pivot x[0, c]
+        np = bn_parts(rows, C);
+        const BnWs ws(workspace, np, C);
+        rc = bn_launch_stats(x, ws, np, dtype, rows, C, st);
+        pp = ws.partial;
+        pivot = ws.pivot;
+    } else {  // the producing GEMM's partials (sums about 0): thousands of rows are folded to BN_FOLD first
+        rc = bn_fold(partial, parts, BnWs(workspace, BN_FOLD, C).partial, C, st, &pp, &np);
+    }
+    if (rc) return rc;
+    hipLaunchKernelGGL(bn_fwd_tail_kernel, dim3((C + 63) / 64), bn_tail_block(np), 0, st, pp, np, pivot, gamma, beta,
+                       mean, rstd, running_mean, running_var, coef, (float)rows, eps, momentum, C);
+    LAUNCH_CHECK();
+    return 0;
+}
+extern "C" int ssl4gie_bn_fwd(int source, const void* x, const float* partial, int parts, const float* gamma,
+                              const float* beta, const void* res, void* y, unsigned char* relu_bits, float* coef,
+                              float* mean, float* rstd, float* running_mean, float* running_var, float momentum,
+                              float eps, int relu, float* workspace, int dtype, long long rows, int C,
+                              void* stream) {
+    REQUIRE(bn_fwd_ok(source, x, partial, parts, gamma, beta, res, y, relu_bits, coef, mean, rstd, running_mean,
+                      running_var, relu, workspace, dtype, rows, C));
+    hipStream_t st = (hipStream_t)stream;
+    if (!y)  // coefficients only
+        return bn_fwd_coef(source, x, partial, parts, gamma, beta, mean, rstd, running_mean, running_var, momentum,
+                           eps, coef, workspace, dtype, rows, C, st);
+    // algorithmic bytes: (statistics pass: x) + apply: x (+ res) -> y
+    ProfScope prof(PROF_BN, (double)(rows * C) * (dtype == SSL4GIE_BF16 ? 2 : 4) *
+                                ((source == SSL4GIE_BN_FROM_X ? 1 : 0) + 2 + (res ? 1 : 0)), st);
+    if (source != SSL4GIE_BN_FROM_COEF) {
+        coef = workspace;  // BnWs::coef
+        int rc = bn_fwd_coef(source, x, partial, parts, gamma, beta, mean, rstd, running_mean, running_var,
+                             momentum, eps, coef, workspace, dtype, rows, C, st);
+        if (rc) return rc;
+    }
+    return bn_launch_apply(x, coef, res, y, relu, relu_bits, dtype, rows, C, st);
+}
+// the LOCAL (mean, biased var) of SyncBatchNorm's forward.  The sums are finished by
+// ssl4gie_internal_reduce_partials, not by the tail kernel: the summation order differs.
+extern "C" int ssl4gie_bn_stats(const void* x, const float* partial, int parts, float* mean, float* var,
+                                float* workspace, int dtype, long long rows, int C, void* stream) {
+    REQUIRE(mean && var && workspace && rows > 0 && C > 0 && C % 8 == 0);
+    REQUIRE(partial ? (parts > 0 && !x) : (x && rdt(dtype)));
+    hipStream_t st = (hipStream_t)stream;
+    const int parts_x = partial ? BN_FOLD : bn_parts(rows, C);
+    const BnWs ws(workspace, parts_x, C);
+    const float *pp = ws.partial, *pivot = partial ? nullptr : ws.pivot;
+    int np = parts_x;
+    int rc = partial ? bn_fold(partial, parts, ws.partial, C, st, &pp, &np)
+                     : bn_launch_stats(x, ws, np, dtype, rows, C, st);
+    if (rc) return rc;
+    rc = ssl4gie_internal_reduce_partials(pp, ws.sums, np, 2 * C, (size_t)2 * C, 0, st);
+    if (rc) return rc;
+    hipLaunchKernelGGL(bn_local_stats_kernel, dim3((C + 255) / 256), dim3(256), 0, st, ws.sums, pivot, mean, var,
+                       (float)rows, C);
+    LAUNCH_CHECK();
+    return 0;
+}
+
+// ---- backward
+// fused: dgamma / dbeta (overwritten or accumulated), dx and (optional) the residual gradient dres
+extern "C" int ssl4gie_bn_bwd(const void* dy, int mask_kind, const void* mask, const void* x, const float* gamma,
+                              const float* beta, const float* mean, const float* rstd, void* dx, void* dres,
+                              float* dgamma, float* dbeta, int accumulate, float* workspace, int dtype,
+                              long long rows, int C, void* stream) {
+    REQUIRE(dx && bn_bwd_ok(dy, mask_kind, mask, x, beta, mean, rstd, dres, workspace, dtype, rows, C));
+    hipStream_t st = (hipStream_t)stream;
+    const int parts = bn_parts(rows, C), relu = mask_kind != SSL4GIE_BN_MASK_NONE;
+    const bool from_y = mask_kind == SSL4GIE_BN_MASK_Y;
+    // with a residual branch the reduction pass writes dres = the MASKED gradient (dy or 0, no rounding): the apply
+    // pass reads that one tensor instead of dy and the ReLU output (6 -> 4 B/element read on the widest BatchNorm
+    // of a bottleneck)
+    const bool masked = relu && dres;
+    // algorithmic bytes: reduce reads dy, x (+ the ReLU output when the mask comes from it; the bit map is 1/16 of
+    // a tensor) and writes dres; apply reads the gradient, x (+ the ReLU output) and writes dx
+    ProfScope prof(PROF_BN, (double)rows * C * (dtype == SSL4GIE_BF16 ? 2 : 4) *
+                                ((2 + (from_y ? 1 : 0) + (mask_kind == SSL4GIE_BN_MASK_BITS ? 0.0625 : 0) + (dres ? 1 : 0)) +
+                                 (2 + ((from_y && !masked) ? 1 : 0) + 1)), st);
+    const BnWs ws(workspace, parts, C);
+    float* mcoef = mask_kind == SSL4GIE_BN_MASK_X ? ws.sums : nullptr;  // the forward's y = x a + b, for the apply pass
+    int rc = bn_launch_reduce(dy, mask_kind, mask, x, gamma, beta, mean, rstd, dres, ws.partial, parts, dtype, rows,
+                              C, st);
+    if (rc) return rc;
+    // dbeta = sum g, dgamma = sum g xhat, and the dx coefficients, in one launch.  No fold in front: bn_parts caps
+    // the partitions at 1024 <= BN_TAIL_WIDE, so the tail always sums the reduction's partials itself
+    hipLaunchKernelGGL(bn_bwd_tail_kernel, dim3((C + 63) / 64), bn_tail_block(parts), 0, st, ws.partial, parts, mean,
+                       rstd, gamma, 1.0f / (float)rows, ws.coef, dgamma, dbeta, accumulate, C, beta, mcoef, ws.pivot);
+    LAUNCH_CHECK();
+    return bn_launch_bwd_apply(masked ? dres : dy, masked ? nullptr : mask, x, ws.coef, dx, masked ? 0 : relu, mcoef,
+                               ws.pivot, dtype, rows, C, st);
+}
+// SyncBatchNorm's halves: sums[0][c] = sum g, sums[1][c] = sum g xhat over the LOCAL rows (the caller all-reduces
+// them), then dx with the GLOBAL sums and 1 / (global row count)
+extern "C" int ssl4gie_bn_bwd_reduce(const void* dy, int mask_kind, const void* mask, const void* x,
+                                     const float* gamma, const float* beta, const float* mean, const float* rstd,
+                                     void* dres, float* sums, float* workspace, int dtype, long long rows, int C,
+                                     void* stream) {
+    REQUIRE(sums && bn_bwd_ok(dy, mask_kind, mask, x, beta, mean, rstd, dres, workspace, dtype, rows, C));
+    REQUIRE(mask_kind == SSL4GIE_BN_MASK_X || !gamma);  // gamma / beta only rebuild the mask here
     hipStream_t st = (hipStream_t)stream;
     const int parts = bn_parts(rows, C);
-    dim3 grid(bn_strips(C, dtype), parts), block(256);
-    float* partial = workspace + 3 * (size_t)C;
-    hipLaunchKernelGGL((bn_bwd_reduce_kernel<bf16_t, 2>), grid, block, 0, st, (const bf16_t*)dy,
-                       (const bf16_t*)relu_bits, (const bf16_t*)x, mean, rstd, (bf16_t*)dres, partial, 1, rows, C,
-                       (const float*)nullptr, (const float*)nullptr);
+    const BnWs ws(workspace, parts, C);
+    int rc = bn_launch_reduce(dy, mask_kind, mask, x, gamma, beta, mean, rstd, dres, ws.partial, parts, dtype, rows,
+                              C, st);
+    if (rc) return rc;
+    return ssl4gie_internal_reduce_partials(ws.partial, sums, parts, 2 * C, (size_t)2 * C, 0, st);
+}
+extern "C" int ssl4gie_bn_bwd_apply(const void* dy, int mask_kind, const void* mask, const void* x,
+                                    const float* gamma, const float* beta, const float* mean, const float* rstd,
+                                    const float* sums, float inv_count, void* dx, float* workspace, int dtype,
+                                    long long rows, int C, void* stream) {
+    REQUIRE(sums && dx && mask_kind != SSL4GIE_BN_MASK_BITS &&  // the caller applies on the reduce half's dres, no mask
+            bn_bwd_ok(dy, mask_kind, mask, x, beta, mean, rstd, nullptr, workspace, dtype, rows, C));
+    hipStream_t st = (hipStream_t)stream;
+    const BnWs ws(workspace, 0, C);  // no partials: [dx coefficients 3C][mask coefficients 2C][copy of mean C]
+    float* mcoef = mask_kind == SSL4GIE_BN_MASK_X ? ws.sums : nullptr;
+    hipLaunchKernelGGL(bn_bwd_coef_kernel, dim3((C + 255) / 256), dim3(256), 0, st, mean, rstd, gamma, sums,
+                       inv_count, ws.coef, C, ws.pivot);
     LAUNCH_CHECK();
-    return ssl4gie_internal_reduce_partials(partial, sums, parts, 2 * C, (size_t)2 * C, 0, st);
+    if (mcoef) {
+        hipLaunchKernelGGL(bn_fwd_coef_kernel, dim3((C + 255) / 256), dim3(256), 0, st, mean, rstd, gamma, beta, mcoef,
+                           C);
+        LAUNCH_CHECK();
+    }
+    return bn_launch_bwd_apply(dy, mask, x, ws.coef, dx, mask_kind != SSL4GIE_BN_MASK_NONE, mcoef, ws.pivot, dtype,
+                               rows, C, st);
 }
 
 // ---- SyncBatchNorm: pooled statistics out of the gathered per-rank records ----------------------------

@@ -210,19 +210,9 @@ def linear_affine_fwd(x2d, w, scale, shift, aux=None, relu=False):
 
 def bn_coef_partials(partials, rows, gamma, beta, running_mean, running_var, momentum, eps):
     """training-mode BatchNorm statistics from GEMM-epilogue partials -> (coef [2, C]: y = x coef[0] + coef[1],
-    mean, rstd); running statistics updated (ssl4gie_bn_coef_partials)"""
-    _dev(partials, gamma, beta, running_mean, running_var)
-    C = partials.shape[2]
-    assert partials.dtype == torch.float32 and partials.shape[1] == 2 and partials.is_contiguous()
-    L = _lib.load()
-    dev = partials.device
-    mean = torch.empty(C, dtype=torch.float32, device=dev)
-    rstd = torch.empty(C, dtype=torch.float32, device=dev)
-    coef = torch.empty(2, C, dtype=torch.float32, device=dev)
-    ws = torch.empty(L.ssl4gie_bn_workspace_bytes(rows, C), dtype=torch.uint8, device=dev)
-    _lib.check(L.ssl4gie_bn_coef_partials(ptr(partials), partials.shape[0], ptr(gamma), ptr(beta), ptr(mean),
-                                          ptr(rstd), ptr(running_mean), ptr(running_var), float(momentum),
-                                          float(eps), ptr(coef), ptr(ws), rows, C, stream()), "bn_coef_partials")
+    mean, rstd); running statistics updated"""
+    _, _, coef, mean, rstd = _bn_fwd(_lib.BN_FROM_PARTIALS, None, rows, partials.shape[2], partials, gamma, beta,
+                                     running=(running_mean, running_var), momentum=momentum, eps=eps)
     return coef, mean, rstd
 
 
@@ -1048,92 +1038,156 @@ def subsample2_bwd(dy, H, W):
     return dx
 
 
+# ------------------------------------------------------------------ BatchNorm: one binder per C entry point
+# (workspace, outputs, pointers and the error tag live here; the public wrappers below only choose the source of the
+# normalisation / of the ReLU mask)
+def _bn_ws(rows, C, dev):
+    return torch.empty(_lib.load().ssl4gie_bn_workspace_bytes(rows, C), dtype=torch.uint8, device=dev)
+
+
+def _bn_fwd(source, x2d, rows, C, partials=None, gamma=None, beta=None, res=None, mean=None, rstd=None,
+            running=(None, None), momentum=0.0, eps=0.0, relu=False, coef=None, want_bits=False):
+    """ssl4gie_bn_fwd -> (y, bits, coef, mean, rstd).  x2d None: the coefficients-only forms (coef is the output);
+    mean / rstd are allocated unless given (FROM_STATS) or unused (FROM_COEF)"""
+    _dev(x2d, partials, gamma, beta, res, mean, rstd, coef, *running)
+    dev = (x2d if x2d is not None else partials if partials is not None else mean).device
+    y = bits = ws = None
+    parts = 0
+    if partials is not None:
+        assert partials.dtype == torch.float32 and partials.shape[1:] == (2, C) and partials.is_contiguous()
+        parts = partials.shape[0]
+    if source in (_lib.BN_FROM_X, _lib.BN_FROM_PARTIALS):
+        mean = torch.empty(C, dtype=torch.float32, device=dev)
+        rstd = torch.empty(C, dtype=torch.float32, device=dev)
+    if x2d is not None:
+        y = torch.empty_like(x2d)
+    else:
+        coef = torch.empty(2, C, dtype=torch.float32, device=dev)
+    if want_bits:
+        assert x2d.dtype == torch.bfloat16
+        bits = torch.empty(rows * C // 8, dtype=torch.uint8, device=dev)
+    if source != _lib.BN_FROM_COEF and not (source == _lib.BN_FROM_STATS and x2d is None):
+        ws = _bn_ws(rows, C, dev)
+    _lib.check(_lib.load().ssl4gie_bn_fwd(
+        source, ptr(x2d), ptr(partials), parts, ptr(gamma), ptr(beta), ptr(res), ptr(y), ptr(bits), ptr(coef),
+        ptr(mean), ptr(rstd), ptr(running[0]), ptr(running[1]), float(momentum), float(eps), int(relu), ptr(ws),
+        code(x2d.dtype) if x2d is not None else F32, rows, C, stream()), "bn_fwd")
+    return y, bits, coef, mean, rstd
+
+
+def _bn_stats(x2d, partials, rows, C):
+    _dev(x2d, partials)
+    dev = (x2d if x2d is not None else partials).device
+    parts = 0
+    if partials is not None:
+        assert partials.dtype == torch.float32 and partials.shape[1:] == (2, C) and partials.is_contiguous()
+        parts = partials.shape[0]
+    mean = torch.empty(C, dtype=torch.float32, device=dev)
+    var = torch.empty(C, dtype=torch.float32, device=dev)
+    _lib.check(_lib.load().ssl4gie_bn_stats(ptr(x2d), ptr(partials), parts, ptr(mean), ptr(var),
+                                            ptr(_bn_ws(rows, C, dev)), code(x2d.dtype) if x2d is not None else F32,
+                                            rows, C, stream()), "bn_stats")
+    return mean, var
+
+
+def _bn_mask(kind, mask, x2d):
+    _dev(mask)
+    if kind == _lib.BN_MASK_BITS:
+        assert mask.dtype == torch.uint8 and mask.numel() == x2d.numel() // 8
+    return ptr(mask)
+
+
+def _bn_bwd(dy2d, kind, mask, x2d, gamma, beta, mean, rstd, want_dres, dgamma, dbeta, accumulate):
+    """ssl4gie_bn_bwd -> (dx, dres)"""
+    _dev(dy2d, x2d, gamma, beta, mean, rstd, dgamma, dbeta)
+    rows, C = x2d.shape
+    dx = torch.empty_like(x2d)
+    dres = torch.empty_like(x2d) if want_dres else None
+    _lib.check(_lib.load().ssl4gie_bn_bwd(
+        ptr(dy2d), kind, _bn_mask(kind, mask, x2d), ptr(x2d), ptr(gamma), ptr(beta), ptr(mean), ptr(rstd), ptr(dx),
+        ptr(dres), ptr(dgamma), ptr(dbeta), int(accumulate), ptr(_bn_ws(rows, C, x2d.device)), code(x2d.dtype), rows,
+        C, stream()), "bn_bwd")
+    return dx, dres
+
+
+def _bn_bwd_reduce(dy2d, kind, mask, x2d, gamma, beta, mean, rstd, want_dres):
+    """ssl4gie_bn_bwd_reduce -> (LOCAL sums [2, C], dres)"""
+    _dev(dy2d, x2d, gamma, beta, mean, rstd)
+    rows, C = x2d.shape
+    sums = torch.empty(2, C, dtype=torch.float32, device=x2d.device)
+    dres = torch.empty_like(x2d) if want_dres else None
+    _lib.check(_lib.load().ssl4gie_bn_bwd_reduce(
+        ptr(dy2d), kind, _bn_mask(kind, mask, x2d), ptr(x2d), ptr(gamma), ptr(beta), ptr(mean), ptr(rstd), ptr(dres),
+        ptr(sums), ptr(_bn_ws(rows, C, x2d.device)), code(x2d.dtype), rows, C, stream()), "bn_bwd_reduce")
+    return sums, dres
+
+
+def _bn_bwd_apply(dy2d, kind, mask, x2d, gamma, beta, mean, rstd, sums, inv_count):
+    """ssl4gie_bn_bwd_apply -> dx from the GLOBAL sums and 1 / (global row count)"""
+    _dev(dy2d, x2d, gamma, beta, mean, rstd, sums)
+    rows, C = x2d.shape
+    dx = torch.empty_like(x2d)
+    _lib.check(_lib.load().ssl4gie_bn_bwd_apply(
+        ptr(dy2d), kind, _bn_mask(kind, mask, x2d), ptr(x2d), ptr(gamma), ptr(beta), ptr(mean), ptr(rstd), ptr(sums),
+        float(inv_count), ptr(dx), ptr(_bn_ws(rows, C, x2d.device)), code(x2d.dtype), rows, C, stream()),
+        "bn_bwd_apply")
+    return dx
+
+
+def _relu_mask(relu, y2d):
+    return (_lib.BN_MASK_Y, y2d) if relu else (_lib.BN_MASK_NONE, None)
+
+
 def bn_fwd(x2d, gamma, beta, res, running_mean, running_var, momentum, eps, relu, training,
            mean=None, rstd=None, partials=None):
     """`partials` [parts, 2, C]: training-mode statistics from the producing GEMM's epilogue
-    (linear_fwd / conv3x3_fwd with colstats=True) instead of a pass over x2d"""
-    _dev(x2d, gamma, beta, res, running_mean, running_var, mean, rstd, partials)
+    (linear_fwd / conv3x3_fwd with colstats=True) instead of a pass over x2d; not training: mean / rstd are inputs"""
     rows, C = x2d.shape
-    L = _lib.load()
-    y = torch.empty_like(x2d)
-    if training:
-        mean = torch.empty(C, dtype=torch.float32, device=x2d.device)
-        rstd = torch.empty(C, dtype=torch.float32, device=x2d.device)
-    ws = torch.empty(L.ssl4gie_bn_workspace_bytes(rows, C), dtype=torch.uint8, device=x2d.device)
-    if training and partials is not None:
-        assert partials.dtype == torch.float32 and partials.shape[1:] == (2, C) and partials.is_contiguous()
-        _lib.check(L.ssl4gie_bn_fwd_partials(ptr(x2d), ptr(partials), partials.shape[0], ptr(gamma),
-                                             ptr(beta), ptr(res), ptr(y), ptr(mean), ptr(rstd),
-                                             ptr(running_mean), ptr(running_var), float(momentum),
-                                             float(eps), int(relu), ptr(ws), code(x2d.dtype), rows, C,
-                                             stream()), "bn_fwd_partials")
+    if not training:
+        y = _bn_fwd(_lib.BN_FROM_STATS, x2d, rows, C, None, gamma, beta, res, mean, rstd, eps=eps, relu=relu)[0]
         return y, mean, rstd
-    _lib.check(L.ssl4gie_bn_fwd(ptr(x2d), ptr(gamma), ptr(beta), ptr(res), ptr(y), ptr(mean), ptr(rstd),
-                                ptr(running_mean), ptr(running_var), float(momentum), float(eps),
-                                int(relu), int(training), ptr(ws), code(x2d.dtype), rows, C, stream()),
-               "bn_fwd")
+    y, _, _, mean, rstd = _bn_fwd(_lib.BN_FROM_X if partials is None else _lib.BN_FROM_PARTIALS, x2d, rows, C,
+                                  partials, gamma, beta, res, running=(running_mean, running_var),
+                                  momentum=momentum, eps=eps, relu=relu)
     return y, mean, rstd
-
-
-def bn_bwd(dy2d, y2d, x2d, gamma, mean, rstd, relu, want_dres, dgamma, dbeta, accumulate):
-    _dev(dy2d, y2d, x2d, gamma, mean, rstd, dgamma, dbeta)
-    rows, C = x2d.shape
-    L = _lib.load()
-    dx = torch.empty_like(x2d)
-    dres = torch.empty_like(x2d) if want_dres else None
-    ws = torch.empty(L.ssl4gie_bn_workspace_bytes(rows, C), dtype=torch.uint8, device=x2d.device)
-    _lib.check(L.ssl4gie_bn_bwd(ptr(dy2d), ptr(y2d), ptr(x2d), ptr(gamma), ptr(mean), ptr(rstd), ptr(dx),
-                                ptr(dres), ptr(dgamma), ptr(dbeta), int(accumulate), int(relu), ptr(ws),
-                                code(x2d.dtype), rows, C, stream()), "bn_bwd")
-    return dx, dres
 
 
 def bn_fwd_bits(x2d, gamma, beta, res, running_mean, running_var, momentum, eps, partials):
     """training-mode BatchNorm (+ residual) + ReLU from GEMM-epilogue partials that also writes the ReLU mask as
-    a bit map [rows * C / 8] (bf16): -> (y, bits, mean, rstd) (ssl4gie_bn_fwd_partials_bits)"""
-    _dev(x2d, gamma, beta, res, running_mean, running_var, partials)
-    rows, C = x2d.shape
-    assert x2d.dtype == torch.bfloat16 and partials.dtype == torch.float32 and partials.shape[1:] == (2, C)
-    L = _lib.load()
-    y = torch.empty_like(x2d)
-    bits = torch.empty(rows * C // 8, dtype=torch.uint8, device=x2d.device)
-    mean = torch.empty(C, dtype=torch.float32, device=x2d.device)
-    rstd = torch.empty(C, dtype=torch.float32, device=x2d.device)
-    ws = torch.empty(L.ssl4gie_bn_workspace_bytes(rows, C), dtype=torch.uint8, device=x2d.device)
-    _lib.check(L.ssl4gie_bn_fwd_partials_bits(ptr(x2d), ptr(partials), partials.shape[0], ptr(gamma), ptr(beta),
-                                              ptr(res), ptr(y), ptr(bits), ptr(mean), ptr(rstd), ptr(running_mean),
-                                              ptr(running_var), float(momentum), float(eps), ptr(ws),
-                                              code(x2d.dtype), rows, C, stream()), "bn_fwd_partials_bits")
+    a bit map [rows * C / 8] (bf16): -> (y, bits, mean, rstd)"""
+    y, bits, _, mean, rstd = _bn_fwd(_lib.BN_FROM_PARTIALS, x2d, *x2d.shape, partials, gamma, beta, res,
+                                     running=(running_mean, running_var), momentum=momentum, eps=eps, relu=True,
+                                     want_bits=True)
     return y, bits, mean, rstd
 
 
-def bn_bwd_bits(dy2d, bits, x2d, gamma, mean, rstd, dgamma, dbeta, accumulate):
-    """backward of bn_fwd_bits: -> (dx, dres = the masked gradient) (ssl4gie_bn_bwd_bits)"""
-    _dev(dy2d, bits, x2d, gamma, mean, rstd, dgamma, dbeta)
+def bn_coef_stats(mean, rstd, gamma, beta):
+    """coef [2, C] (y = x coef[0] + coef[1]) of a BatchNorm whose statistics are given — the GLOBAL ones a
+    SyncBatchNorm exchange returned"""
+    return _bn_fwd(_lib.BN_FROM_STATS, None, 0, mean.numel(), None, gamma, beta, None, mean, rstd)[2]
+
+
+def bn_apply_bits(x2d, coef, res):
+    """relu(x coef[0] + coef[1] (+ res)) + the ReLU bit map (bf16): the apply half of bn_fwd_bits with given
+    coefficients -> (y, bits)"""
     rows, C = x2d.shape
-    assert bits.dtype == torch.uint8 and bits.numel() == rows * C // 8
-    L = _lib.load()
-    dx = torch.empty_like(x2d)
-    dres = torch.empty_like(x2d)
-    ws = torch.empty(L.ssl4gie_bn_workspace_bytes(rows, C), dtype=torch.uint8, device=x2d.device)
-    _lib.check(L.ssl4gie_bn_bwd_bits(ptr(dy2d), ptr(bits), ptr(x2d), ptr(gamma), ptr(mean), ptr(rstd), ptr(dx),
-                                     ptr(dres), ptr(dgamma), ptr(dbeta), int(accumulate), ptr(ws), code(x2d.dtype),
-                                     rows, C, stream()), "bn_bwd_bits")
-    return dx, dres
+    assert coef.shape == (2, C) and coef.is_contiguous()
+    return _bn_fwd(_lib.BN_FROM_COEF, x2d, rows, C, res=res, relu=True, coef=coef, want_bits=True)[:2]
+
+
+def bn_bwd(dy2d, y2d, x2d, gamma, mean, rstd, relu, want_dres, dgamma, dbeta, accumulate):
+    return _bn_bwd(dy2d, *_relu_mask(relu, y2d), x2d, gamma, None, mean, rstd, want_dres, dgamma, dbeta, accumulate)
+
+
+def bn_bwd_bits(dy2d, bits, x2d, gamma, mean, rstd, dgamma, dbeta, accumulate):
+    """backward of bn_fwd_bits: -> (dx, dres = the masked gradient)"""
+    return _bn_bwd(dy2d, _lib.BN_MASK_BITS, bits, x2d, gamma, None, mean, rstd, True, dgamma, dbeta, accumulate)
 
 
 def bn_bwd_xmask(dy2d, x2d, gamma, beta, mean, rstd, dgamma, dbeta, accumulate):
     """BatchNorm + ReLU without a residual input: the mask is rebuilt from x and the forward's coefficients, the
-    ReLU output is not read (ssl4gie_bn_bwd_xmask)"""
-    _dev(dy2d, x2d, gamma, beta, mean, rstd, dgamma, dbeta)
-    rows, C = x2d.shape
-    L = _lib.load()
-    dx = torch.empty_like(x2d)
-    ws = torch.empty(L.ssl4gie_bn_workspace_bytes(rows, C), dtype=torch.uint8, device=x2d.device)
-    _lib.check(L.ssl4gie_bn_bwd_xmask(ptr(dy2d), ptr(x2d), ptr(gamma), ptr(beta), ptr(mean), ptr(rstd), ptr(dx),
-                                      ptr(dgamma), ptr(dbeta), int(accumulate), ptr(ws), code(x2d.dtype),
-                                      rows, C, stream()), "bn_bwd_xmask")
-    return dx
+    ReLU output is not read"""
+    return _bn_bwd(dy2d, _lib.BN_MASK_X, None, x2d, gamma, beta, mean, rstd, False, dgamma, dbeta, accumulate)[0]
 
 
 def maxpool3x3s2_fwd(x, coef=None, relu=False):
@@ -1184,125 +1238,37 @@ def avgpool_bwd(dy, H, W, dtype):
 def bn_stats(x2d, partials=None):
     """local batch statistics (mean, biased variance) of the rows of x2d, fp32 [C] each; from the
     producing GEMM's `partials` [parts, 2, C] when given"""
-    _dev(x2d, partials)
-    rows, C = x2d.shape
-    L = _lib.load()
-    mean = torch.empty(C, dtype=torch.float32, device=x2d.device)
-    var = torch.empty(C, dtype=torch.float32, device=x2d.device)
-    ws = torch.empty(L.ssl4gie_bn_workspace_bytes(rows, C), dtype=torch.uint8, device=x2d.device)
-    if partials is not None:
-        assert partials.dtype == torch.float32 and partials.shape[1:] == (2, C) and partials.is_contiguous()
-        _lib.check(L.ssl4gie_bn_stats_partials(ptr(partials), partials.shape[0], ptr(mean), ptr(var),
-                                               ptr(ws), rows, C, stream()), "bn_stats_partials")
-        return mean, var
-    _lib.check(L.ssl4gie_bn_stats(ptr(x2d), ptr(mean), ptr(var), ptr(ws), code(x2d.dtype), rows, C,
-                                  stream()), "bn_stats")
-    return mean, var
+    return _bn_stats(x2d if partials is None else None, partials, *x2d.shape)
 
 
 def bn_stats_from_partials(partials, rows):
     """local (mean, biased variance) of a map known only through its producer's partials [parts, 2, C] (the
     statistics-only product of linear_colstats_only: the map itself is never written)"""
-    _dev(partials)
-    C = partials.shape[2]
-    assert partials.dtype == torch.float32 and partials.shape[1] == 2 and partials.is_contiguous()
-    L = _lib.load()
-    mean = torch.empty(C, dtype=torch.float32, device=partials.device)
-    var = torch.empty(C, dtype=torch.float32, device=partials.device)
-    ws = torch.empty(L.ssl4gie_bn_workspace_bytes(rows, C), dtype=torch.uint8, device=partials.device)
-    _lib.check(L.ssl4gie_bn_stats_partials(ptr(partials), partials.shape[0], ptr(mean), ptr(var), ptr(ws), rows, C,
-                                           stream()), "bn_stats_partials")
-    return mean, var
+    return _bn_stats(None, partials, rows, partials.shape[2])
 
 
 def bn_bwd_reduce(dy2d, y2d, x2d, mean, rstd, relu, want_dres):
-    _dev(dy2d, y2d, x2d, mean, rstd)
-    rows, C = x2d.shape
-    L = _lib.load()
-    sums = torch.empty(2, C, dtype=torch.float32, device=x2d.device)
-    dres = torch.empty_like(x2d) if want_dres else None
-    ws = torch.empty(L.ssl4gie_bn_workspace_bytes(rows, C), dtype=torch.uint8, device=x2d.device)
-    _lib.check(L.ssl4gie_bn_bwd_reduce(ptr(dy2d), ptr(y2d), ptr(x2d), ptr(mean), ptr(rstd), ptr(dres),
-                                       ptr(sums), int(relu), ptr(ws), code(x2d.dtype), rows, C,
-                                       stream()), "bn_bwd_reduce")
-    return sums, dres
-
-
-def bn_coef_stats(mean, rstd, gamma, beta):
-    """coef [2, C] (y = x coef[0] + coef[1]) of a BatchNorm whose statistics are given — the GLOBAL ones a
-    SyncBatchNorm exchange returned (ssl4gie_bn_coef_stats)"""
-    _dev(mean, rstd, gamma, beta)
-    C = mean.numel()
-    coef = torch.empty(2, C, dtype=torch.float32, device=mean.device)
-    _lib.check(_lib.load().ssl4gie_bn_coef_stats(ptr(mean), ptr(rstd), ptr(gamma), ptr(beta), ptr(coef), C, stream()),
-               "bn_coef_stats")
-    return coef
-
-
-def bn_apply_bits(x2d, coef, res):
-    """relu(x coef[0] + coef[1] (+ res)) + the ReLU bit map (bf16): the apply half of bn_fwd_bits with given
-    coefficients (ssl4gie_bn_apply_bits) -> (y, bits)"""
-    _dev(x2d, coef, res)
-    rows, C = x2d.shape
-    assert x2d.dtype == torch.bfloat16 and coef.shape == (2, C) and coef.is_contiguous()
-    y = torch.empty_like(x2d)
-    bits = torch.empty(rows * C // 8, dtype=torch.uint8, device=x2d.device)
-    _lib.check(_lib.load().ssl4gie_bn_apply_bits(ptr(x2d), ptr(coef), ptr(res), ptr(y), ptr(bits), code(x2d.dtype),
-                                                 rows, C, stream()), "bn_apply_bits")
-    return y, bits
+    return _bn_bwd_reduce(dy2d, *_relu_mask(relu, y2d), x2d, None, None, mean, rstd, want_dres)
 
 
 def bn_bwd_reduce_bits(dy2d, bits, x2d, mean, rstd):
     """SyncBatchNorm + residual + ReLU backward, first half with the mask from the forward's bit map:
-    -> (LOCAL sums [2, C], dres = the masked gradient) (ssl4gie_bn_bwd_reduce_bits)"""
-    _dev(dy2d, bits, x2d, mean, rstd)
-    rows, C = x2d.shape
-    assert bits.dtype == torch.uint8 and bits.numel() == rows * C // 8
-    L = _lib.load()
-    sums = torch.empty(2, C, dtype=torch.float32, device=x2d.device)
-    dres = torch.empty_like(x2d)
-    ws = torch.empty(L.ssl4gie_bn_workspace_bytes(rows, C), dtype=torch.uint8, device=x2d.device)
-    _lib.check(L.ssl4gie_bn_bwd_reduce_bits(ptr(dy2d), ptr(bits), ptr(x2d), ptr(mean), ptr(rstd), ptr(dres), ptr(sums),
-                                            ptr(ws), code(x2d.dtype), rows, C, stream()), "bn_bwd_reduce_bits")
-    return sums, dres
+    -> (LOCAL sums [2, C], dres = the masked gradient)"""
+    return _bn_bwd_reduce(dy2d, _lib.BN_MASK_BITS, bits, x2d, None, None, mean, rstd, True)
 
 
 def bn_bwd_reduce_xmask(dy2d, x2d, gamma, beta, mean, rstd):
     """SyncBatchNorm + ReLU (no residual) backward, first half with the mask rebuilt from x: LOCAL sums [2, C]"""
-    _dev(dy2d, x2d, gamma, beta, mean, rstd)
-    rows, C = x2d.shape
-    L = _lib.load()
-    sums = torch.empty(2, C, dtype=torch.float32, device=x2d.device)
-    ws = torch.empty(L.ssl4gie_bn_workspace_bytes(rows, C), dtype=torch.uint8, device=x2d.device)
-    _lib.check(L.ssl4gie_bn_bwd_reduce_xmask(ptr(dy2d), ptr(x2d), ptr(gamma), ptr(beta), ptr(mean), ptr(rstd),
-                                             ptr(sums), ptr(ws), code(x2d.dtype), rows, C, stream()),
-               "bn_bwd_reduce_xmask")
-    return sums
+    return _bn_bwd_reduce(dy2d, _lib.BN_MASK_X, None, x2d, gamma, beta, mean, rstd, False)[0]
 
 
 def bn_bwd_apply_xmask(dy2d, x2d, gamma, beta, mean, rstd, sums, inv_count):
     """... second half: dx from the GLOBAL sums and 1 / (global row count)"""
-    _dev(dy2d, x2d, gamma, beta, mean, rstd, sums)
-    rows, C = x2d.shape
-    dx = torch.empty_like(x2d)
-    L = _lib.load()
-    ws = torch.empty(L.ssl4gie_bn_workspace_bytes(rows, C), dtype=torch.uint8, device=x2d.device)
-    _lib.check(L.ssl4gie_bn_bwd_apply_xmask(ptr(dy2d), ptr(x2d), ptr(gamma), ptr(beta), ptr(mean), ptr(rstd),
-                                            ptr(sums), float(inv_count), ptr(dx), ptr(ws), code(x2d.dtype), rows, C,
-                                            stream()), "bn_bwd_apply_xmask")
-    return dx
+    return _bn_bwd_apply(dy2d, _lib.BN_MASK_X, None, x2d, gamma, beta, mean, rstd, sums, inv_count)
 
 
 def bn_bwd_apply(dy2d, y2d, x2d, gamma, mean, rstd, sums, inv_count, relu):
-    _dev(dy2d, y2d, x2d, gamma, mean, rstd, sums)
-    rows, C = x2d.shape
-    dx = torch.empty_like(x2d)
-    L = _lib.load()
-    ws = torch.empty(L.ssl4gie_bn_workspace_bytes(rows, C), dtype=torch.uint8, device=x2d.device)
-    _lib.check(L.ssl4gie_bn_bwd_apply(ptr(dy2d), ptr(y2d), ptr(x2d), ptr(gamma), ptr(mean), ptr(rstd),
-                                      ptr(sums), float(inv_count), ptr(dx), int(relu), ptr(ws),
-                                      code(x2d.dtype), rows, C, stream()), "bn_bwd_apply")
-    return dx
+    return _bn_bwd_apply(dy2d, *_relu_mask(relu, y2d), x2d, gamma, None, mean, rstd, sums, inv_count)
 
 
 def ema_update(dst, src, m):

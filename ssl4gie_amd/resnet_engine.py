@@ -325,6 +325,43 @@ def _bn_params_moved(epoch, gamma, beta):
     return any(p is not None and id(p) in moved for p in (gamma, beta))
 
 
+def _bn_backward(dy2, x2, mask, gamma, beta, mean, rstd, want_dres, targets, acc, sync=False, group=None, total=None):
+    """BatchNorm (+ residual) (+ ReLU) backward -> (dx, dres).  mask = (kind, tensor): where the ReLU mask comes from —
+    "none", "y" (the ReLU output), "x" (rebuilt from x and the forward's gamma / beta: no residual input), "bits" (the
+    forward's bit map).  targets = (dgamma, dbeta) to overwrite or (acc) add to.  One rank: the fused call.  sync: local
+    reduction -> parameter gradients from the LOCAL sums (DDP averages them) -> sums over the ranks / `total` rows ->
+    apply; with a residual input and a ReLU the apply half reads the masked gradient `dres` and no mask."""
+    kind, m = mask
+    tg, tb = targets
+    gd = gamma.detach() if gamma is not None else None
+    bd = beta.detach() if beta is not None else None
+    if not sync:
+        if kind == "bits":
+            return ops.bn_bwd_bits(dy2, m, x2, gd, mean, rstd, tg, tb, acc)
+        if kind == "x":
+            return ops.bn_bwd_xmask(dy2, x2, gd, bd, mean, rstd, tg, tb, acc), None
+        return ops.bn_bwd(dy2, m, x2, gd, mean, rstd, kind == "y", want_dres, tg, tb, acc)
+    if kind == "bits":
+        sums, dres = ops.bn_bwd_reduce_bits(dy2, m, x2, mean, rstd)
+    elif kind == "x":
+        sums, dres = ops.bn_bwd_reduce_xmask(dy2, x2, gd, bd, mean, rstd), None
+    else:
+        sums, dres = ops.bn_bwd_reduce(dy2, m, x2, mean, rstd, kind == "y", want_dres)
+    for tgt, row in ((tb, 0), (tg, 1)):
+        if tgt is not None:
+            if acc:
+                tgt.add_(sums[row])
+            else:
+                tgt.copy_(sums[row])
+    gsums = sync_sum(sums, group)
+    gsums /= total  # the 1 / count of the dx formula, folded into the sums on the device
+    if kind == "x":
+        return ops.bn_bwd_apply_xmask(dy2, x2, gd, bd, mean, rstd, gsums, 1.0), None
+    if kind != "none" and dres is not None:
+        return ops.bn_bwd_apply(dres, None, x2, gd, mean, rstd, gsums, 1.0, False), dres
+    return ops.bn_bwd_apply(dy2, m, x2, gd, mean, rstd, gsums, 1.0, kind == "y"), dres
+
+
 class BatchNormFn(torch.autograd.Function):
     """nn.BatchNorm2d / BatchNorm1d / SyncBatchNorm over the rows of a [..., C] tensor, (+ residual)
     (+ ReLU).  With an nn.SyncBatchNorm holder and world_size > 1 the statistics are global: local
@@ -375,62 +412,33 @@ class BatchNormFn(torch.autograd.Function):
         # the mask-from-x backward rebuilds the ReLU mask from gamma / beta as they are AT BACKWARD TIME: it is only
         # valid while no optimizer has stepped since this forward — checked there against this stamp;
         # that path never reads the ReLU output, so it is not saved for it either
-        xmask = relu and res is None and _XMASK and bits is None
+        if bits is not None:
+            kind, m = "bits", bits
+        elif relu and res is None and _XMASK:
+            kind, m = "x", None
+        else:
+            kind, m = ("y", y) if relu else ("none", None)
         ctx.wepoch = weights_epoch()
-        ctx.save_for_backward(x2, bits if bits is not None else (y if (relu and not xmask) else None), gamma, beta,
-                              mean, rstd)
-        ctx.cfg = (shp, relu, res is not None, sink, training, sync, group, total)
+        ctx.save_for_backward(x2, m, gamma, beta, mean, rstd)
+        ctx.cfg = (shp, kind, res is not None, sink, training, sync, group, total)
         return y.view(shp)
 
     @staticmethod
     def backward(ctx, dy):
-        x2, y, gamma, beta, mean, rstd = ctx.saved_tensors
-        shp, relu, has_res, sink, training, sync, group, total = ctx.cfg
+        x2, m, gamma, beta, mean, rstd = ctx.saved_tensors
+        shp, kind, has_res, sink, training, sync, group, total = ctx.cfg
         if not training:
             raise NotImplementedError("backward through BatchNorm in eval mode (frozen statistics) is "
                                       "not built: the reference freezes trunks under no_grad")
-        C = shp[-1]
-        (tg, tb), acc, rets = sink.plan([gamma, beta])
-        dy2 = dy.contiguous().view(-1, C)
-        gd = gamma.detach() if gamma is not None else None
-        if not sync and relu and has_res and y is not None and y.dtype == torch.uint8:
-            dx, dres = ops.bn_bwd_bits(dy2, y, x2, gd, mean, rstd, tg, tb, acc)   # `y` holds the forward's bit map
-        elif not sync and relu and not has_res and _XMASK:
-            # the ReLU mask from x and the forward's coefficients: the ReLU output is not read again
-            if _bn_params_moved(ctx.wepoch, gamma, beta):
-                raise RuntimeError("BatchNorm parameters were updated between this forward and its backward: the "
-                                   "ReLU mask rebuilt from them would disagree with the forward (set SSL4GIE_BN_XMASK=0)")
-            dx, dres = ops.bn_bwd_xmask(dy2, x2, gd, beta.detach() if beta is not None else None, mean, rstd,
-                                        tg, tb, acc), None
-        elif not sync:
-            dx, dres = ops.bn_bwd(dy2, y, x2, gd, mean, rstd, relu, has_res, tg, tb, acc)
-        else:
-            import torch.distributed as dist
-            xm = relu and not has_res and _XMASK   # mask rebuilt from x and the (global) forward coefficients
-            if xm and _bn_params_moved(ctx.wepoch, gamma, beta):
+        targets, acc, rets = sink.plan([gamma, beta])
+        if kind == "x" and _bn_params_moved(ctx.wepoch, gamma, beta):
+            if sync:
                 raise RuntimeError("BatchNorm parameters were updated between this forward and its backward "
                                    "(set SSL4GIE_BN_XMASK=0)")
-            bd = beta.detach() if beta is not None else None
-            if xm:
-                sums, dres = ops.bn_bwd_reduce_xmask(dy2, x2, gd, bd, mean, rstd), None
-            elif relu and has_res and y is not None and y.dtype == torch.uint8:   # `y` holds the forward's bit map
-                sums, dres = ops.bn_bwd_reduce_bits(dy2, y, x2, mean, rstd)
-            else:
-                sums, dres = ops.bn_bwd_reduce(dy2, y, x2, mean, rstd, relu, has_res)
-            for tgt, row in ((tb, 0), (tg, 1)):  # parameter gradients are the LOCAL sums
-                if tgt is not None:
-                    if acc:
-                        tgt.add_(sums[row])
-                    else:
-                        tgt.copy_(sums[row])
-            gsums = sync_sum(sums, group)
-            gsums /= total  # the 1 / count of the dx formula, folded into the sums on the device
-            if xm:
-                dx = ops.bn_bwd_apply_xmask(dy2, x2, gd, bd, mean, rstd, gsums, 1.0)
-            elif relu and has_res:   # dres is the masked gradient: one tensor instead of dy and the ReLU output
-                dx = ops.bn_bwd_apply(dres, None, x2, gd, mean, rstd, gsums, 1.0, False)
-            else:
-                dx = ops.bn_bwd_apply(dy2, y, x2, gd, mean, rstd, gsums, 1.0, relu)
+            raise RuntimeError("BatchNorm parameters were updated between this forward and its backward: the "
+                               "ReLU mask rebuilt from them would disagree with the forward (set SSL4GIE_BN_XMASK=0)")
+        dx, dres = _bn_backward(dy.contiguous().view(-1, shp[-1]), x2, (kind, m), gamma, beta, mean, rstd, has_res,
+                                targets, acc, sync, group, total)
         gres = dres.view(shp) if has_res else None
         if gres is not None and ctx.join is not None:
             ctx.join.deposit(gres)  # joined in the data-gradient GEMM of the block's first convolution
@@ -490,24 +498,9 @@ class BnReluMaxPoolFn(torch.autograd.Function):
                                "mask rebuilt from them would disagree with the forward (set SSL4GIE_STEM_POOL_FUSED=0)")
         B, H, W, C = x.shape
         dz = ops.maxpool3x3s2_bwd(dy.contiguous(), arg, H, W)
-        (tg, tb), acc, rets = ctx.sink.plan([gamma, beta])
-        gd = gamma.detach() if gamma is not None else None
-        bd = beta.detach() if beta is not None else None
-        sync, group, total = ctx.sync
-        if not sync:
-            dx = ops.bn_bwd_xmask(dz.view(-1, C), x.contiguous().view(-1, C), gd, bd, mean, rstd, tg, tb, acc)
-            return dx.view(B, H, W, C), rets[0], rets[1], None, None, None
-        dz2, x2 = dz.view(-1, C), x.contiguous().view(-1, C)
-        sums = ops.bn_bwd_reduce_xmask(dz2, x2, gd, bd, mean, rstd)
-        for tgt, row in ((tb, 0), (tg, 1)):  # parameter gradients are the LOCAL sums (DDP averages them)
-            if tgt is not None:
-                if acc:
-                    tgt.add_(sums[row])
-                else:
-                    tgt.copy_(sums[row])
-        gsums = sync_sum(sums, group)
-        gsums /= total
-        dx = ops.bn_bwd_apply_xmask(dz2, x2, gd, bd, mean, rstd, gsums, 1.0)
+        targets, acc, rets = ctx.sink.plan([gamma, beta])
+        dx, _ = _bn_backward(dz.view(-1, C), x.contiguous().view(-1, C), ("x", None), gamma, beta, mean, rstd, False,
+                             targets, acc, *ctx.sync)
         return dx.view(B, H, W, C), rets[0], rets[1], None, None, None
 
 
@@ -579,8 +572,8 @@ class BnReluConv3x3Fn(torch.autograd.Function):
         if ctx.needs_input_grad[0]:
             wdd = _derived(lp, weight, "c3dd", dt, lambda w: ops.conv3x3_weight_pack(w, dt, 1), recipe=(1, None))
             dz = ops.conv3x3_direct_fwd(dy.view(B, H, W, Cout), wdd, None)   # gradient at the ReLU's output
-            dx = ops.bn_bwd_xmask(dz.view(-1, Cin), x.view(-1, Cin), gamma.detach() if gamma is not None else None,
-                                  beta.detach() if beta is not None else None, mean, rstd, tg, tb, acc).view(B, H, W, Cin)
+            dx = _bn_backward(dz.view(-1, Cin), x.view(-1, Cin), ("x", None), gamma, beta, mean, rstd, False, (tg, tb),
+                              acc)[0].view(B, H, W, Cin)
         return dx, rets[1], rets[2], None, None, rets[0], None, None, None
 
 
