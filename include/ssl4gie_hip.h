@@ -14,7 +14,8 @@
  *   - returns 0 on success, SSL4GIE_EARG (1000) for an invalid argument, otherwise a hipError_t;
  *   - callable from any host thread; the only mutable process-wide settings are the execution
  *     options ssl4gie_set_wgrad_stream / ssl4gie_set_compute_cus and the profiler;
- *   - ssl4gie_abi_version() = 12 (11: before the sixteen BatchNorm entry points that had grown one per fusion (ssl4gie_bn_fwd / _fwd_partials / _fwd_partials_bits /
+ *   - ssl4gie_abi_version() = 12 (ssl4gie_view_sample_u8 joined revision 12 without a new number: one more symbol, nothing
+ *     existing changed, so a caller built against the earlier 12 runs unchanged; 11: before the sixteen BatchNorm entry points that had grown one per fusion (ssl4gie_bn_fwd / _fwd_partials / _fwd_partials_bits /
  *     _coef_partials / _coef_stats / _apply_bits, _stats / _stats_partials, _bwd / _bwd_xmask / _bwd_bits, _bwd_reduce / _reduce_xmask / _reduce_bits,
  *     _bwd_apply / _apply_xmask) were REPLACED by five with a source and a mask kind — the same launches, new signatures; 10: before the diagnostics entry point that read the 256x256 NT kernel's in-kernel
  *     time stamps was REMOVED with the debug build of the library — the one removal in this history; 9: before ssl4gie_infonce_{workspace_bytes,loss} / ssl4gie_cross_entropy{_workspace_bytes,} /
@@ -636,6 +637,25 @@ int ssl4gie_lars_arena(float* p, const float* g, float* mu, const long long* seg
  * mean / std are HOST arrays of 3 floats; H*W % 4 == 0. */
 int ssl4gie_normalize_u8(const unsigned char* img, float* out, const float* mean, const float* std,
                          int B, int H, int W, void* stream);
+/* transforms.RandomResizedCrop(S, scale, interpolation=3) + RandomHorizontalFlip + ToTensor + Normalize
+ * (Models/mae/main_pretrain.py:123-127; with SSL4GIE_FILTER_BILINEAR the geometric part of
+ * Models/moco_v3/main_moco.py:263,275) out of a uint8 image bank that lives on the device, with the boxes and
+ * flips already drawn: sample b is image index[b] of bank [n, Hs, Ws, 3], cropped to box[b] = (top, left,
+ * height, width), resampled to S x S by PIL's rule (separable, antialiased: the filter widens by
+ * max(1, length / S); taps never leave the box; Keys cubic a = -0.5 or the triangle), mirrored left-right where
+ * flip[b] != 0 (flip == NULL: never), clamped to [0, 255] and written as fp32 NCHW out[b] = (v / 255 - mean) /
+ * std.  Values are NOT rounded to integer levels between the passes as PIL's 8-bit images are.
+ * index / box / flip are DEVICE arrays, so they are checked by the kernel: a sample whose index is outside
+ * [0, n) or whose box is not inside the image (height < 1, width < 1, top < 0, left < 0, top + height > Hs,
+ * left + width > Ws) comes out all NaN, and no address is formed from its values.  mean / std are HOST arrays
+ * of 3 floats.  SSL4GIE_EARG: a null pointer, S % 4 != 0, std <= 0, an unknown filter, or an (Hs, Ws, S) whose
+ * whole-image box does not fit one CU's LDS (Hs, Ws <= 1024 at S = 224 do).  fp32 accumulation in a fixed
+ * order: bit-identical from run to run. */
+#define SSL4GIE_FILTER_BILINEAR 0
+#define SSL4GIE_FILTER_BICUBIC 1
+int ssl4gie_view_sample_u8(const unsigned char* bank, long long n, int Hs, int Ws, const long long* index,
+                           const int* box, const unsigned char* flip, float* out, int B, int S, int filter,
+                           const float* mean, const float* std, void* stream);
 
 /* ---------------------------------------------------------------- detection pyramid glue (channels-last)
  * ViTDet_FPN (Models/models.py:213-259) around its GEMM-shaped convolutions:

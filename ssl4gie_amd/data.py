@@ -1,0 +1,190 @@
+"""On-device input pipeline: a uint8 image bank resident in HBM, crop boxes drawn with device-side torch ops, and
+one HIP kernel (ops.view_sample_u8) that crops, resamples (PIL's antialiased bicubic / bilinear), flips, clamps and
+normalises into the fp32 NCHW batch the models consume.  It stands in for the reference's
+
+    ImageFolder -> RandomResizedCrop(224, scale=(0.2, 1.0), interpolation=3) -> RandomHorizontalFlip -> ToTensor
+    -> Normalize  in DataLoader workers, then one host-to-device copy per batch    (Models/mae/main_pretrain.py:123-153)
+
+with no host image work and no image copy: per batch the host sends `batch_size` int64 indices and nothing else.
+The geometric part of MoCo-v3's two-view augmentation (Models/moco_v3/main_moco.py:263,275: RandomResizedCrop with
+bilinear resampling + flip) is `RandomResizedCropFlip(interpolation="bilinear", scale=(crop_min, 1), views=2)`; its
+colour transforms (ColorJitter, RandomGrayscale, GaussianBlur, Solarize) are NOT covered — `mean=(0, 0, 0),
+std=(1, 1, 1)` yields [0, 1] images for a later colour stage.
+
+    bank = DeviceImageBank.from_npy("train_256.npy", "cuda")           # tools/pack_images.py wrote it, once
+    sampler = torch.utils.data.DistributedSampler(bank, num_replicas=world, rank=rank, shuffle=True)
+    loader = DeviceLoader(bank, 256, sampler=sampler, transform=RandomResizedCropFlip(224))
+    for epoch in ...:
+        loader.sampler.set_epoch(epoch)
+        for it, (samples, _) in enumerate(loader):                      # engine_pretrain.py:39-45, as written
+            samples = samples.to(device, non_blocking=True)             # already there: returns itself
+"""
+from __future__ import annotations
+
+import functools
+import math
+
+import numpy as np
+import torch
+
+from . import ops
+from .ops import IMAGENET_MEAN, IMAGENET_STD
+
+
+class DeviceImageBank:
+    """[n, Hs, Ws, 3] uint8 images (one stored size) on a device, with optional integer labels.  A map-style
+    dataset whose items are (index, label): torch's own samplers (RandomSampler, DistributedSampler and its
+    set_epoch) work on it unchanged, and what they hand out is what DeviceLoader sends to the device."""
+
+    def __init__(self, images_u8, labels=None):
+        if not (torch.is_tensor(images_u8) and images_u8.dtype == torch.uint8 and images_u8.dim() == 4
+                and images_u8.shape[3] == 3 and images_u8.is_contiguous() and images_u8.shape[0] >= 1):
+            raise ValueError("DeviceImageBank needs a contiguous uint8 tensor [n, Hs, Ws, 3], n >= 1")
+        self.images = images_u8
+        n = images_u8.shape[0]
+        if labels is None:
+            self._labels_host = None
+            self.labels = torch.zeros(n, dtype=torch.int64, device=images_u8.device)
+        else:
+            host = torch.as_tensor(np.asarray(labels.cpu() if torch.is_tensor(labels) else labels)).to(torch.int64)
+            if tuple(host.shape) != (n,):
+                raise ValueError(f"labels must have shape ({n},), got {tuple(host.shape)}")
+            self._labels_host = host.tolist()
+            self.labels = host.to(images_u8.device)
+
+    device = property(lambda self: self.images.device)
+    stored_size = property(lambda self: (int(self.images.shape[1]), int(self.images.shape[2])))
+
+    def __len__(self):
+        return int(self.images.shape[0])
+
+    def __getitem__(self, i):
+        i = int(i)
+        if not 0 <= i < len(self):
+            raise IndexError(i)
+        return i, (0 if self._labels_host is None else self._labels_host[i])
+
+    @classmethod
+    def from_uint8(cls, array_or_tensor, device, labels=None):
+        t = array_or_tensor if torch.is_tensor(array_or_tensor) else torch.from_numpy(np.ascontiguousarray(array_or_tensor))
+        return cls(t.contiguous().to(device), labels)
+
+    @classmethod
+    def from_npy(cls, path, device, labels=None, chunk_bytes=256 << 20):
+        """`path` is a .npy of [n, Hs, Ws, 3] uint8 (tools/pack_images.py).  The file is memory-mapped and
+        copied chunk by chunk, so the host never holds a second copy of it."""
+        arr = np.load(path, mmap_mode="r")
+        if arr.dtype != np.uint8 or arr.ndim != 4 or arr.shape[3] != 3:
+            raise ValueError(f"{path}: expected uint8 [n, Hs, Ws, 3], got {arr.dtype} {arr.shape}")
+        n = arr.shape[0]
+        dst = torch.empty(arr.shape, dtype=torch.uint8, device=device)
+        step = max(1, int(chunk_bytes) // max(1, int(np.prod(arr.shape[1:]))))
+        for a in range(0, n, step):
+            dst[a:a + step].copy_(torch.from_numpy(np.array(arr[a:a + step])))
+        if isinstance(labels, str):
+            labels = np.load(labels)
+        return cls(dst, labels)
+
+
+@functools.lru_cache(maxsize=64)
+def _fallback_box(Hs, Ws, ratio, device):
+    """get_params' box when none of the 10 tries fits: centred, of the nearest allowed aspect.  A constant of
+    (stored size, ratio): built once per device, so that no draw carries a host-to-device copy."""
+    in_ratio = Ws / Hs
+    if in_ratio < min(ratio):
+        fw, fh = Ws, int(round(Ws / min(ratio)))
+    elif in_ratio > max(ratio):
+        fh, fw = Hs, int(round(Hs * max(ratio)))
+    else:
+        fw, fh = Ws, Hs
+    return torch.tensor([(Hs - fh) // 2, (Ws - fw) // 2, fh, fw], dtype=torch.float64, device=device)
+
+
+def rrc_boxes(u, Hs, Ws, scale=(0.2, 1.0), ratio=(3.0 / 4.0, 4.0 / 3.0)):
+    """transforms.RandomResizedCrop.get_params as a pure function of uniforms u [B, 10, 4] in [0, 1): per try
+    (area fraction, log-aspect, top, left).  float64 on u's device, vectorised, no host read-back.  Returns int32
+    [B, 4] = (top, left, height, width).  torchvision draws its scalars one at a time, so its random SEQUENCE
+    is not reproduced; its distribution is."""
+    assert u.dim() == 3 and tuple(u.shape[1:]) == (10, 4)
+    u = u.to(torch.float64)
+    area = float(Hs * Ws)
+    l0, l1 = math.log(ratio[0]), math.log(ratio[1])
+    target = area * (scale[0] + u[..., 0] * (scale[1] - scale[0]))
+    aspect = torch.exp(l0 + u[..., 1] * (l1 - l0))
+    w = torch.round(torch.sqrt(target * aspect))          # round half to even, as Python's round()
+    h = torch.round(torch.sqrt(target / aspect))
+    ok = (w > 0) & (w <= Ws) & (h > 0) & (h <= Hs)
+    top = torch.minimum(torch.floor(u[..., 2] * (Hs - h + 1)), Hs - h)   # (u < 1: the minimum never binds)
+    left = torch.minimum(torch.floor(u[..., 3] * (Ws - w + 1)), Ws - w)
+    first = torch.argmax(ok.to(torch.uint8), dim=1)       # the first try that fits (argmax returns the first maximum)
+    tries = torch.stack([top, left, h, w], dim=2)         # [B, 10, 4]
+    won = tries.gather(1, first.view(-1, 1, 1).expand(-1, 1, 4)).squeeze(1)
+    fallback = _fallback_box(int(Hs), int(Ws), (float(ratio[0]), float(ratio[1])), u.device)
+    return torch.where(ok.any(dim=1, keepdim=True), won, fallback).to(torch.int32)
+
+
+class RandomResizedCropFlip:
+    """RandomResizedCrop(size, scale, ratio, interpolation) + RandomHorizontalFlip(flip_p) + ToTensor +
+    Normalize(mean, std), drawn and computed on the bank's device.  __call__(bank, index) -> [B, 3, size, size]
+    fp32, or a list of `views` independently drawn such batches when views > 1."""
+
+    def __init__(self, size=224, scale=(0.2, 1.0), ratio=(3.0 / 4.0, 4.0 / 3.0), interpolation="bicubic", flip_p=0.5,
+                 views=1, mean=IMAGENET_MEAN, std=IMAGENET_STD, generator=None):
+        if interpolation not in ("bicubic", "bilinear"):
+            raise ValueError(f"interpolation must be 'bicubic' or 'bilinear', got {interpolation!r}")
+        if size % 4 or views < 1:
+            raise ValueError("size must be a multiple of 4 and views >= 1")
+        self.size, self.scale, self.ratio, self.interpolation = int(size), tuple(scale), tuple(ratio), interpolation
+        self.flip_p, self.views, self.mean, self.std, self.generator = float(flip_p), int(views), tuple(mean), tuple(std), generator
+
+    def draw(self, B, Hs, Ws, device):
+        """one view's boxes int32 [B, 4] and flips uint8 [B] (advances the generator)"""
+        u = torch.rand(B, 10, 4, dtype=torch.float64, device=device, generator=self.generator)
+        v = torch.rand(B, dtype=torch.float64, device=device, generator=self.generator)
+        return rrc_boxes(u, Hs, Ws, self.scale, self.ratio), (v < self.flip_p).to(torch.uint8)
+
+    def _view(self, bank, index):
+        Hs, Ws = bank.stored_size
+        box, flip = self.draw(index.shape[0], Hs, Ws, index.device)
+        return ops.view_sample_u8(bank.images, index, box, flip, self.size, self.interpolation, self.mean, self.std)
+
+    def __call__(self, bank, index):
+        if self.views == 1:
+            return self._view(bank, index)
+        return [self._view(bank, index) for _ in range(self.views)]
+
+
+class DeviceLoader:
+    """What the reference's DataLoader is to its training loops, over a DeviceImageBank: len(), iteration that
+    yields (samples, labels) — ([view1, view2], labels) for a two-view transform — and `.sampler` for
+    set_epoch.  Per batch the host takes `batch_size` plain ints from the sampler and sends them as one int64
+    tensor (pinned, non_blocking); the transform does the rest on the device.  Nothing synchronises."""
+
+    def __init__(self, bank, batch_size, sampler=None, drop_last=True, transform=None):
+        if batch_size < 1:
+            raise ValueError("batch_size must be >= 1")
+        self.bank, self.batch_size, self.drop_last = bank, int(batch_size), bool(drop_last)
+        self.sampler = sampler if sampler is not None else torch.utils.data.RandomSampler(bank)
+        self.transform = transform if transform is not None else RandomResizedCropFlip()
+
+    def __len__(self):
+        n = len(self.sampler)
+        return n // self.batch_size if self.drop_last else (n + self.batch_size - 1) // self.batch_size
+
+    def _batch(self, idx):
+        host = torch.tensor(idx, dtype=torch.int64)
+        dev = self.bank.device
+        if dev.type != "cpu":
+            host = host.pin_memory()
+        index = host.to(dev, non_blocking=True)
+        return self.transform(self.bank, index), self.bank.labels[index]
+
+    def __iter__(self):
+        idx = []
+        for i in self.sampler:
+            idx.append(int(i))
+            if len(idx) == self.batch_size:
+                yield self._batch(idx)
+                idx = []
+        if idx and not self.drop_last:
+            yield self._batch(idx)

@@ -1352,3 +1352,31 @@ def normalize_u8(img_u8, mean=IMAGENET_MEAN, std=IMAGENET_STD):
     s = (C.c_float * 3)(*std)
     _lib.check(_lib.load().ssl4gie_normalize_u8(ptr(img_u8), ptr(out), m, s, B, H, W, stream()), "normalize_u8")
     return out
+
+
+_FILTERS = {"bilinear": _lib.FILTER_BILINEAR, "bicubic": _lib.FILTER_BICUBIC}
+
+
+def view_sample_u8(bank, index, box, flip, S, filter="bicubic", mean=IMAGENET_MEAN, std=IMAGENET_STD):
+    """Random-resized-crop views out of a uint8 image bank [n, Hs, Ws, 3] on the device -> fp32 NCHW [B, 3, S, S]:
+    sample b is image index[b] (int64 [B]) cropped to box[b] = (top, left, height, width) (int32 [B, 4]), resampled
+    to S x S with PIL's antialiased `filter`, mirrored where flip[b] != 0 (uint8 [B] or None), clamped to
+    [0, 255], (v / 255 - mean) / std  (RandomResizedCrop + RandomHorizontalFlip + ToTensor + Normalize of
+    main_pretrain.py:123-127 once the boxes are drawn).  An index or box that does not lie inside the bank
+    gives an all-NaN sample; `filter` may also be the C ABI's integer code."""
+    _dev(bank, index, box, flip)
+    assert bank.dtype == torch.uint8 and bank.dim() == 4 and bank.shape[3] == 3
+    assert index.dtype == torch.int64 and index.dim() == 1
+    B = index.shape[0]
+    assert box.dtype == torch.int32 and tuple(box.shape) == (B, 4)
+    assert flip is None or (flip.dtype == torch.uint8 and tuple(flip.shape) == (B,))
+    n, Hs, Ws, _ = bank.shape
+    f = _FILTERS[filter] if isinstance(filter, str) else int(filter)
+    out = torch.empty(B, 3, S, S, dtype=torch.float32, device=bank.device)
+    if B == 0:
+        return out
+    m = (C.c_float * 3)(*mean)
+    s = (C.c_float * 3)(*std)
+    _lib.check(_lib.load().ssl4gie_view_sample_u8(ptr(bank), n, Hs, Ws, ptr(index), ptr(box), ptr(flip), ptr(out),
+                                                  B, S, f, m, s, stream()), "view_sample_u8")
+    return out
