@@ -14,8 +14,8 @@
  *   - returns 0 on success, SSL4GIE_EARG (1000) for an invalid argument, otherwise a hipError_t;
  *   - callable from any host thread; the only mutable process-wide settings are the execution
  *     options ssl4gie_set_wgrad_stream / ssl4gie_set_compute_cus and the profiler;
- *   - ssl4gie_abi_version() = 12 (ssl4gie_view_sample_u8 joined revision 12 without a new number: one more symbol, nothing
- *     existing changed, so a caller built against the earlier 12 runs unchanged; 11: before the sixteen BatchNorm entry points that had grown one per fusion (ssl4gie_bn_fwd / _fwd_partials / _fwd_partials_bits /
+ *   - ssl4gie_abi_version() = 12 (ssl4gie_view_sample_u8, and after it ssl4gie_color_augment{_workspace_bytes,}, joined revision 12
+ *     without a new number: added symbols, nothing existing changed, so a caller built against the earlier 12 runs unchanged; 11: before the sixteen BatchNorm entry points that had grown one per fusion (ssl4gie_bn_fwd / _fwd_partials / _fwd_partials_bits /
  *     _coef_partials / _coef_stats / _apply_bits, _stats / _stats_partials, _bwd / _bwd_xmask / _bwd_bits, _bwd_reduce / _reduce_xmask / _reduce_bits,
  *     _bwd_apply / _apply_xmask) were REPLACED by five with a source and a mask kind — the same launches, new signatures; 10: before the diagnostics entry point that read the 256x256 NT kernel's in-kernel
  *     time stamps was REMOVED with the debug build of the library — the one removal in this history; 9: before ssl4gie_infonce_{workspace_bytes,loss} / ssl4gie_cross_entropy{_workspace_bytes,} /
@@ -656,6 +656,40 @@ int ssl4gie_normalize_u8(const unsigned char* img, float* out, const float* mean
 int ssl4gie_view_sample_u8(const unsigned char* bank, long long n, int Hs, int Ws, const long long* index,
                            const int* box, const unsigned char* flip, float* out, int B, int S, int filter,
                            const float* mean, const float* std, void* stream);
+/* The colour half of MoCo-v3's two-view augmentation (Models/moco_v3/main_moco.py:262-285, moco/loader.py:26-42:
+ * RandomApply(ColorJitter) -> RandomGrayscale -> GaussianBlur -> Solarize -> Normalize) with the per-sample
+ * parameters already drawn: x fp32 [B, 3, S, S] in [0, 1] (ssl4gie_view_sample_u8 with mean 0, std 1) -> out, the
+ * normalised fp32 [B, 3, S, S].  Crop and flip have happened before; every op here is pointwise or a symmetric
+ * stencil, so flipping first equals the reference's flipping last.  The rule, per sample b, on clamp(x, 0, 1):
+ *   1. jitter: order[b][0..3] are op ids applied left to right, an id at most once, 255 = skip;
+ *      blend(a, d, f) = clamp(f a + (1 - f) d, 0, 1), gray(x) = 0.299 r + 0.587 g + 0.114 b (PIL's "L"),
+ *      f = factors[b][id] (factors [B, 4] = brightness, contrast, saturation, hue):
+ *        0 brightness blend(x, 0, f);  1 contrast blend(x, m, f), m = the mean of gray over the sample's whole image
+ *        after the ops that precede contrast in its order;  2 saturation blend(x, gray(x), f);
+ *        3 hue: rgb -> hsv, h <- (h + f) mod 1, hsv -> rgb by the colorsys formulas in floating point
+ *        (torchvision's tensor path), p, q, t clamped to [0, 1]; a pixel with max == min keeps its value;
+ *   2. flags[b] & 1: all three channels <- gray(x);
+ *   3. sigma[b] > 0: separable true Gaussian, R = ceil(3 sigma) (supported: R <= 6, sigma <= 2), weights
+ *      exp(-k^2 / 2 sigma^2), k in [-R, R], over their sum; horizontal pass, then vertical; symmetric edges
+ *      (index -1 - i reads i, S + i reads S - 1 - i).  PIL's GaussianBlur(radius = sigma) is a three-pass box
+ *      approximation of this kernel;
+ *   4. flags[b] & 2: x >= 128 / 255 -> 1 - x (ImageOps.solarize, threshold 128);
+ *   5. (x - mean[c]) / std[c].
+ * Values are NOT rounded to integer levels between the ops, as PIL's 8-bit images are.
+ * factors / order / flags / sigma are DEVICE arrays, so the host cannot check them: the kernel treats an op id
+ * above 3 as a skip and clamps R to 6 (a larger sigma gives a truncated Gaussian; NaN or sigma <= 0: no blur).
+ * mean / std are HOST arrays of 3 floats.  workspace: ssl4gie_color_augment_workspace_bytes(B, S) bytes on the
+ * device (per-sample partial sums of the contrast mean; 0 for a (B, S) the entry point refuses).
+ * SSL4GIE_EARG, before anything is launched: a null pointer, B < 1, S < 8, S % 4 != 0, a std entry equal to 0,
+ * out == x (the stencil reads its neighbours' inputs), x or out not 16-byte aligned, a workspace smaller than the
+ * query says.
+ * Two launches, no atomics, sums in a fixed order: bit-identical from run to run, and a sample's result does not
+ * depend on its place in the batch. */
+size_t ssl4gie_color_augment_workspace_bytes(int B, int S);
+int ssl4gie_color_augment(const float* x, float* out, int B, int S, const float* factors,
+                          const unsigned char* order, const unsigned char* flags, const float* sigma,
+                          const float* mean, const float* std, void* workspace, size_t workspace_bytes,
+                          void* stream);
 
 /* ---------------------------------------------------------------- detection pyramid glue (channels-last)
  * ViTDet_FPN (Models/models.py:213-259) around its GEMM-shaped convolutions:

@@ -152,6 +152,9 @@ PROTOTYPES = {
     "ssl4gie_normalize_u8": (i32, [vp, vp, C.POINTER(C.c_float), C.POINTER(C.c_float), i32, i32, i32, vp]),
     "ssl4gie_view_sample_u8": (i32, [vp, i64, i32, i32, vp, vp, vp, vp, i32, i32, i32, C.POINTER(C.c_float),
                                      C.POINTER(C.c_float), vp]),
+    "ssl4gie_color_augment_workspace_bytes": (sz, [i32, i32]),
+    "ssl4gie_color_augment": (i32, [vp, vp, i32, i32, vp, vp, vp, vp, C.POINTER(C.c_float), C.POINTER(C.c_float), vp, sz,
+                                    vp]),
     "ssl4gie_maxpool2x2_fwd": (i32, [vp, vp, i32, i32, i32, i32, i32, vp]),
     "ssl4gie_maxpool2x2_bwd": (i32, [vp, vp, vp, i32, i32, i32, i32, i32, vp]),
     "ssl4gie_gelu_map": (i32, [vp, vp, vp, i32, i64, vp]),

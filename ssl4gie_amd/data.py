@@ -7,9 +7,16 @@ normalises into the fp32 NCHW batch the models consume.  It stands in for the re
 
 with no host image work and no image copy: per batch the host sends `batch_size` int64 indices and nothing else.
 The geometric part of MoCo-v3's two-view augmentation (Models/moco_v3/main_moco.py:263,275: RandomResizedCrop with
-bilinear resampling + flip) is `RandomResizedCropFlip(interpolation="bilinear", scale=(crop_min, 1), views=2)`; its
-colour transforms (ColorJitter, RandomGrayscale, GaussianBlur, Solarize) are NOT covered — `mean=(0, 0, 0),
-std=(1, 1, 1)` yields [0, 1] images for a later colour stage.
+bilinear resampling + flip) is `RandomResizedCropFlip(interpolation="bilinear", scale=(crop_min, 1), mean=(0, 0, 0),
+std=(1, 1, 1))`, which yields [0, 1] images; its colour transforms (main_moco.py:264-268,276-281: ColorJitter,
+RandomGrayscale, GaussianBlur, Solarize) and the Normalize are `ColorAugment`, a second HIP launch pair
+(ops.color_augment) on parameters drawn on the device.  `MoCoV3Views` is the two of them per view, with the two
+views' recipes:
+
+    loader = DeviceLoader(bank, 256, sampler=sampler, transform=MoCoV3Views(224, crop_min=0.08))
+    for i, (images, _) in enumerate(loader):                            # main_moco.py:311-323, as written
+        images[0] = images[0].cuda(gpu, non_blocking=True)              # already there
+        images[1] = images[1].cuda(gpu, non_blocking=True)
 
     bank = DeviceImageBank.from_npy("train_256.npy", "cuda")           # tools/pack_images.py wrote it, once
     sampler = torch.utils.data.DistributedSampler(bank, num_replicas=world, rank=rank, shuffle=True)
@@ -152,6 +159,75 @@ class RandomResizedCropFlip:
         if self.views == 1:
             return self._view(bank, index)
         return [self._view(bank, index) for _ in range(self.views)]
+
+
+class ColorAugment:
+    """RandomApply([ColorJitter(brightness, contrast, saturation, hue)], jitter_p) + RandomGrayscale(gray_p) +
+    RandomApply([GaussianBlur(blur_sigma)], blur_p) + RandomApply([Solarize()], solarize_p) + Normalize(mean, std)
+    (Models/moco_v3/main_moco.py:264-271) on a device batch x fp32 [B, 3, S, S] in [0, 1], one parameter set per
+    sample drawn on x's device.  The defaults are MoCo-v3's first view.  The blur is a true Gaussian of radius
+    ceil(3 sigma) <= 6 pixels, hence blur_sigma[1] <= 2 (the reference's range)."""
+
+    def __init__(self, brightness=0.4, contrast=0.4, saturation=0.2, hue=0.1, jitter_p=0.8, gray_p=0.2, blur_p=1.0,
+                 blur_sigma=(0.1, 2.0), solarize_p=0.0, mean=IMAGENET_MEAN, std=IMAGENET_STD, generator=None):
+        if min(brightness, contrast, saturation, hue) < 0:
+            raise ValueError("brightness, contrast, saturation and hue must be >= 0")
+        if hue > 0.5:
+            raise ValueError(f"hue must be <= 0.5, got {hue}")
+        if not 0 <= blur_sigma[0] <= blur_sigma[1]:
+            raise ValueError(f"blur_sigma must be 0 <= lo <= hi, got {tuple(blur_sigma)}")
+        if blur_sigma[1] > 2.0:
+            raise ValueError(f"blur_sigma[1] must be <= 2.0 (a radius of 6 pixels), got {blur_sigma[1]}")
+        if not all(0.0 <= p <= 1.0 for p in (jitter_p, gray_p, blur_p, solarize_p)):
+            raise ValueError("probabilities must lie in [0, 1]")
+        self.jitter = (float(brightness), float(contrast), float(saturation), float(hue))
+        self.jitter_p, self.gray_p, self.blur_p, self.solarize_p = float(jitter_p), float(gray_p), float(blur_p), float(solarize_p)
+        self.blur_sigma = (float(blur_sigma[0]), float(blur_sigma[1]))
+        self.mean, self.std, self.generator = tuple(mean), tuple(std), generator
+
+    def ranges(self):
+        """[(lo, hi)] of the brightness, contrast, saturation and hue factors (ColorJitter._check_input)"""
+        b, c, s, h = self.jitter
+        return [(max(0.0, 1.0 - v), 1.0 + v) for v in (b, c, s)] + [(-h, h)]
+
+    def draw(self, B, device):
+        """factors fp32 [B, 4], order uint8 [B, 4], flags uint8 [B], sigma fp32 [B] (advances the generator).
+        ColorJitter.get_params: a uniform random permutation of the four ops (argsort of uniforms) and one uniform
+        factor each; an op whose range is a point (value 0) is left out, as torchvision leaves it out.  Vectorised
+        on the device, no host read-back; torchvision's random SEQUENCE is not reproduced, its distribution is."""
+        u = torch.rand(B, 13, dtype=torch.float64, device=device, generator=self.generator)
+        on = (u[:, 8] < self.jitter_p).unsqueeze(1)
+        order = torch.argsort(u[:, 0:4], dim=1).to(torch.uint8)
+        cols = []
+        for k, (lo, hi) in enumerate(self.ranges()):
+            cols.append(lo + u[:, 4 + k] * (hi - lo))
+            if self.jitter[k] == 0.0:
+                order = order.masked_fill(order == k, 255)
+        factors = torch.stack([torch.where(on[:, 0], c, 1.0 if k < 3 else 0.0) for k, c in enumerate(cols)], dim=1)
+        order = order.masked_fill(~on, 255)
+        flags = (u[:, 9] < self.gray_p).to(torch.uint8) + 2 * (u[:, 11] < self.solarize_p).to(torch.uint8)
+        lo, hi = self.blur_sigma
+        sigma = torch.where(u[:, 10] < self.blur_p, lo + u[:, 12] * (hi - lo), 0.0)
+        return factors.to(torch.float32).contiguous(), order.contiguous(), flags, sigma.to(torch.float32)
+
+    def __call__(self, x):
+        return ops.color_augment(x, *self.draw(x.shape[0], x.device), self.mean, self.std)
+
+
+class MoCoV3Views:
+    """MoCo-v3's two-view transform (Models/moco_v3/main_moco.py:262-285) for DeviceLoader: per view a
+    RandomResizedCropFlip(size, scale=(crop_min, 1), bilinear) into [0, 1] and that view's ColorAugment — view 1
+    always blurred, view 2 blurred with p = 0.1 and solarized with p = 0.2.  __call__(bank, index) -> [view1, view2],
+    as the MoCo loop indexes them.  The one generator is drawn from in the order crop 1, colour 1, crop 2, colour 2."""
+
+    def __init__(self, size=224, crop_min=0.08, mean=IMAGENET_MEAN, std=IMAGENET_STD, generator=None):
+        self.crops = [RandomResizedCropFlip(size, scale=(crop_min, 1.0), interpolation="bilinear", mean=(0.0, 0.0, 0.0),
+                                            std=(1.0, 1.0, 1.0), generator=generator) for _ in range(2)]
+        self.colors = [ColorAugment(blur_p=1.0, solarize_p=0.0, mean=mean, std=std, generator=generator),
+                       ColorAugment(blur_p=0.1, solarize_p=0.2, mean=mean, std=std, generator=generator)]
+
+    def __call__(self, bank, index):
+        return [color(crop(bank, index)) for crop, color in zip(self.crops, self.colors)]
 
 
 class DeviceLoader:

@@ -1380,3 +1380,44 @@ def view_sample_u8(bank, index, box, flip, S, filter="bicubic", mean=IMAGENET_ME
     _lib.check(_lib.load().ssl4gie_view_sample_u8(ptr(bank), n, Hs, Ws, ptr(index), ptr(box), ptr(flip), ptr(out),
                                                   B, S, f, m, s, stream()), "view_sample_u8")
     return out
+
+
+def color_augment(x, factors, order, flags, sigma, mean=IMAGENET_MEAN, std=IMAGENET_STD, out=None):
+    """The colour half of MoCo-v3's augmentation on fp32 [B, 3, S, S] images in [0, 1] (view_sample_u8 with
+    mean 0, std 1), per-sample parameters given as device arrays (data.ColorAugment draws them): colour jitter —
+    order uint8 [B, 4] holds the op ids 0 brightness, 1 contrast, 2 saturation, 3 hue in the order they apply, 255 =
+    skip; factors fp32 [B, 4] = (b, c, s, h) —, grayscale where flags[b] & 1, a true Gaussian blur of sigma[b]
+    (fp32 [B]; 0 = none, R = ceil(3 sigma) <= 6, symmetric edges), solarize at 128 / 255 where flags[b] & 2
+    (flags uint8 [B]), then (x - mean) / std.  The rule is spelled out in include/ssl4gie_hip.h.  Returns the new
+    fp32 [B, 3, S, S]; `out`, if given, must not share memory with x (the blur reads its neighbours' inputs)."""
+    _dev(x, factors, order, flags, sigma, out)
+    _f32(x, factors, sigma, out)
+    if x.dim() != 4 or x.shape[1] != 3 or x.shape[2] != x.shape[3]:
+        raise ValueError(f"color_augment needs x [B, 3, S, S], got {tuple(x.shape)}")
+    B, _, S, _ = x.shape
+    if S < 8 or S % 4:
+        raise ValueError(f"color_augment needs S >= 8 and a multiple of 4, got {S}")
+    if order.dtype != torch.uint8 or flags.dtype != torch.uint8:
+        raise TypeError(f"order and flags must be uint8, got {order.dtype} and {flags.dtype}")
+    if tuple(factors.shape) != (B, 4) or tuple(order.shape) != (B, 4) or tuple(flags.shape) != (B,) \
+            or tuple(sigma.shape) != (B,):
+        raise ValueError("color_augment needs factors [B, 4], order [B, 4], flags [B], sigma [B]")
+    if any(t.device != x.device for t in (factors, order, flags, sigma)):
+        raise ValueError("color_augment needs all its tensors on one device")
+    if out is None:
+        out = torch.empty_like(x)
+    else:
+        if out.shape != x.shape or out.device != x.device:
+            raise ValueError("out must have x's shape and device")
+        nbytes = x.numel() * 4
+        if out.data_ptr() < x.data_ptr() + nbytes and x.data_ptr() < out.data_ptr() + nbytes:
+            raise ValueError("color_augment cannot run in place: out shares memory with x")
+    if B == 0:
+        return out
+    L = _lib.load()
+    ws = torch.empty(L.ssl4gie_color_augment_workspace_bytes(B, S), dtype=torch.uint8, device=x.device)
+    m = (C.c_float * 3)(*mean)
+    s = (C.c_float * 3)(*std)
+    _lib.check(L.ssl4gie_color_augment(ptr(x), ptr(out), B, S, ptr(factors), ptr(order), ptr(flags), ptr(sigma), m, s,
+                                       ptr(ws), ws.numel(), stream()), "color_augment")
+    return out
