@@ -14,7 +14,7 @@
  *   - returns 0 on success, SSL4GIE_EARG (1000) for an invalid argument, otherwise a hipError_t;
  *   - callable from any host thread; the only mutable process-wide settings are the execution
  *     options ssl4gie_set_wgrad_stream / ssl4gie_set_compute_cus and the profiler;
- *   - ssl4gie_abi_version() = 12 (ssl4gie_view_sample_u8, and after it ssl4gie_color_augment{_workspace_bytes,}, joined revision 12
+ *   - ssl4gie_abi_version() = 12 (ssl4gie_view_sample_u8, after it ssl4gie_color_augment{_workspace_bytes,}, and after those ssl4gie_color_augment_ft / ssl4gie_paired_warp, joined revision 12
  *     without a new number: added symbols, nothing existing changed, so a caller built against the earlier 12 runs unchanged; 11: before the sixteen BatchNorm entry points that had grown one per fusion (ssl4gie_bn_fwd / _fwd_partials / _fwd_partials_bits /
  *     _coef_partials / _coef_stats / _apply_bits, _stats / _stats_partials, _bwd / _bwd_xmask / _bwd_bits, _bwd_reduce / _reduce_xmask / _reduce_bits,
  *     _bwd_apply / _apply_xmask) were REPLACED by five with a source and a mask kind — the same launches, new signatures; 10: before the diagnostics entry point that read the 256x256 NT kernel's in-kernel
@@ -690,6 +690,45 @@ int ssl4gie_color_augment(const float* x, float* out, int B, int S, const float*
                           const unsigned char* order, const unsigned char* flags, const float* sigma,
                           const float* mean, const float* std, void* workspace, size_t workspace_bytes,
                           void* stream);
+/* The colour stage of the finetune loaders (Binary_segmentation/Data/dataloaders.py:62-71, Classification/Data/
+ * dataloaders.py:62-66: ColorJitter -> GaussianBlur((25, 25), sigma) -> ToTensor -> Normalize).  Arguments, workspace
+ * query, steps 1, 2, 4 and 5, guarantees and refusals are ssl4gie_color_augment's; step 3 is
+ *   3'. sigma[b] > 0: separable 25-tap Gaussian, k in [-12, 12], weights exp(-k^2 / 2 sigma^2) (sigma the fp32 value it
+ *       is) over their sum; horizontal pass, then vertical; reflect edges (index -i reads i, S - 1 + i reads
+ *       S - 1 - i): transforms.GaussianBlur((25, 25)) on its tensor path (reflect pad + depthwise conv2d).  The tap
+ *       loop stops at ceil(6 sigma) rounded up to even: the taps left out sum to less than 4e-9 of the total weight.
+ *       NaN or sigma <= 0: no blur.  At sigma <= 0.05 every weight but the centre's is 0 in fp32 and the result is
+ *       the un-blurred one bit for bit (the reference's lower end, 0.001, is such a sigma).
+ * SSL4GIE_EARG in addition: S < 16 (a reflect halo of 12 needs S > 12). */
+int ssl4gie_color_augment_ft(const float* x, float* out, int B, int S, const float* factors,
+                             const unsigned char* order, const unsigned char* flags, const float* sigma,
+                             const float* mean, const float* std, void* workspace, size_t workspace_bytes,
+                             void* stream);
+/* The geometric stage of the finetune loaders (Binary_segmentation/Data/dataset.py:46-63: hflip, vflip, TF.affine on
+ * the normalised tensor and its mask; Depth_estimation/Data/dataset.py:47-70: the flips; Classification/Data/
+ * dataloaders.py:67-69: flips + RandomRotation) with the parameters already drawn, image and target through the same
+ * nearest-neighbour map in one launch.  img / img_out fp32 [B, 3, S, S]; the target of sample b is
+ * tgt_bank[index[b]] of a bank [n, S, S] of tgt_dtype (u8 -> v / 255, u16 -> v / 65535, fp32 as it is), written to
+ * tgt_out fp32 [B, 1, S, S]; tgt_bank, index and tgt_out are all given or all NULL.  Output pixel (i, j) of sample
+ * b, with c = (S - 1) / 2, xo = j - c, yo = i - c and m = matrix[b] (fp32 [B, 6], torchvision's inverse affine
+ * matrix; NULL = identity):
+ *   sx = m0 xo + m1 yo + m2 + c,  sy = m3 xo + m4 yo + m5 + c,  ix = rint(sx), iy = rint(sy) (half to even) —
+ *   F.grid_sample(mode = "nearest", align_corners = False) on torchvision's _gen_affine_grid;
+ *   (ix, iy) outside [0, S)^2: fill_img[ch] / fill_tgt;  otherwise ix <- S - 1 - ix where flip[b] & 1, iy <- S - 1 -
+ *   iy where flip[b] & 2 (flip uint8 [B] or NULL; the reference flips before the affine, so the source is mirrored),
+ *   and the pixel is the source pixel.
+ * sx, sy are evaluated in fp32: a source coordinate within 1e-4 of a half-integer may round to either neighbour.
+ * index / matrix / flip are DEVICE arrays: an index outside [0, n) gives an all-NaN target sample, a NaN or
+ * out-of-range coordinate is the fill, and no address is formed from either.  fill_img is a HOST array of 3 floats.
+ * SSL4GIE_EARG, before anything is launched: a null img / img_out / fill_img, S < 4, S % 4 != 0, img_out overlapping
+ * img (a gather cannot run in place), a pointer not 16-byte aligned, a target given in part (tgt_out without
+ * tgt_bank, ...), an unknown tgt_dtype, n < 1.  A pure gather: bit-identical from run to run. */
+#define SSL4GIE_TGT_U8 0
+#define SSL4GIE_TGT_U16 1
+#define SSL4GIE_TGT_F32 2
+int ssl4gie_paired_warp(const float* img, float* img_out, const void* tgt_bank, int tgt_dtype, long n,
+                        const int64_t* index, float* tgt_out, const float* matrix, const uint8_t* flip,
+                        const float fill_img[3], float fill_tgt, int B, int S, void* stream);
 
 /* ---------------------------------------------------------------- detection pyramid glue (channels-last)
  * ViTDet_FPN (Models/models.py:213-259) around its GEMM-shaped convolutions:

@@ -22,6 +22,7 @@ EPI_NONE, EPI_BIAS, EPI_BIAS_GELU, EPI_BIAS_RESIDUAL, EPI_DGELU, EPI_BIAS_GELU_G
     EPI_RELU_MASK_AUX, EPI_ADD_AUX, EPI_AFFINE_AUX_RELU = range(10)
 BN_FROM_X, BN_FROM_PARTIALS, BN_FROM_STATS, BN_FROM_COEF = range(4)   # ssl4gie_bn_fwd: source of the normalisation
 FILTER_BILINEAR, FILTER_BICUBIC = 0, 1                                # ssl4gie_view_sample_u8: resampling filter
+TGT_U8, TGT_U16, TGT_F32 = range(3)                                   # ssl4gie_paired_warp: element type of the target bank
 BN_MASK_NONE, BN_MASK_Y, BN_MASK_X, BN_MASK_BITS = range(4)           # backward: source of the ReLU mask
 
 vp, i32, i64, f32, sz = C.c_void_p, C.c_int, C.c_longlong, C.c_float, C.c_size_t
@@ -155,6 +156,9 @@ PROTOTYPES = {
     "ssl4gie_color_augment_workspace_bytes": (sz, [i32, i32]),
     "ssl4gie_color_augment": (i32, [vp, vp, i32, i32, vp, vp, vp, vp, C.POINTER(C.c_float), C.POINTER(C.c_float), vp, sz,
                                     vp]),
+    "ssl4gie_color_augment_ft": (i32, [vp, vp, i32, i32, vp, vp, vp, vp, C.POINTER(C.c_float), C.POINTER(C.c_float), vp,
+                                       sz, vp]),
+    "ssl4gie_paired_warp": (i32, [vp, vp, vp, i32, C.c_long, vp, vp, vp, vp, C.POINTER(C.c_float), f32, i32, i32, vp]),
     "ssl4gie_maxpool2x2_fwd": (i32, [vp, vp, i32, i32, i32, i32, i32, vp]),
     "ssl4gie_maxpool2x2_bwd": (i32, [vp, vp, vp, i32, i32, i32, i32, i32, vp]),
     "ssl4gie_gelu_map": (i32, [vp, vp, vp, i32, i64, vp]),

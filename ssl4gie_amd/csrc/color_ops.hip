@@ -22,6 +22,17 @@
 //   5. (x - mean[c]) / std[c]
 // No rounding to integer levels between the ops.
 //
+// ssl4gie_color_augment_ft is the colour stage of the finetune loaders (Binary_segmentation/Data/dataloaders.py:62-71,
+// Classification/Data/dataloaders.py:62-66: ColorJitter -> GaussianBlur((25, 25), sigma) -> ToTensor -> Normalize):
+// the same rule with step 3 replaced by
+//   3'. sigma[b] > 0: separable 25-tap Gaussian, k in [-12, 12], weights exp(-k^2 / 2 sigma^2) over the sum of all 25;
+//       horizontal pass, then vertical pass; reflect edges (index -i reads i, S - 1 + i reads S - 1 - i) — what
+//       transforms.GaussianBlur((25, 25)) computes on its tensor path.  The tap loop stops at R = ceil(6 sigma)
+//       rounded up to even, at most 12: a dropped tap weighs less than exp(-18) = 1.6e-8 of the centre's, and all of
+//       them together less than 4e-9 of the sum, a fifteenth of an fp32 ulp of the [0, 1] result.  sigma < 1 / 16: every
+//       weight but the centre's is 0 in fp32, and the sample takes the no-blur path.
+// It is the same two kernels: color_apply_kernel is a template over (largest radius, edge rule, radius rule).
+//
 // Two launches:
 //   color_stats_kernel  sample x chunk of the image.  A sample without a contrast op exits at once; otherwise the
 //       workgroup applies the ops that precede contrast, sums gray (per lane, wave shuffles, LDS, one lane in wave
@@ -35,7 +46,8 @@
 //       stores 16 bytes per lane.  The image is read once (the halo out of L2) and written once.
 // Tile geometry: CA_TILE_H rows x 56 columns at S = 224 (48 / 56 / 64 columns, whichever pads S least), 512 threads;
 // LDS for R = 6 is 3 (CA_TILE_H + 12) (2 W + 16) floats = 67.6 KB at 32 x 56: two workgroups per CU (what it was
-// measured against: the note at CA_TILE_H).
+// measured against: the note at CA_TILE_H).  The finetune rule's R = 12: 3 (CA_FT_TILE_H + 24) (2 W + 24) floats =
+// 91.4 KB at 32 x 56, one workgroup per CU (the note at CA_FT_TILE_H).
 #include "common.h"
 #include "ssl4gie_hip.h"
 
@@ -49,6 +61,15 @@
 // 104 — the third workgroup per CU does not pay for the doubled halo share; 32 it is.
 #ifndef CA_TILE_H
 #define CA_TILE_H 32
+#endif
+#define CA_FT_RMAX 12  // the 25-tap blur of the finetune loaders; a multiple of 4 already
+// Rows of a tile of the finetune rule (halo of up to 12 rows).  Measured on an MI355X at B = 128, S = 224
+// (tools/time_finetune_augment.py --part ab, medians of 50): 32 x 56 tiles (91.4 KB of LDS, one workgroup per CU, 24
+// halo rows on 32 at R = 12) against 16 x 56 (65.3 KB, two per CU, 24 on 16): segmentation recipe 235 against 302 us,
+// sigma = 2 on every sample 277 against 378 — the second workgroup per CU does not pay for the doubled halo share
+// (the jitter is recomputed on the halo); 32 it is.
+#ifndef CA_FT_TILE_H
+#define CA_FT_TILE_H 32
 #endif
 #define CA_SKIP 255
 
@@ -156,6 +177,7 @@ DEVI f32x4 ca_finish4(f32x4 v, bool solarize, float sc, float sh) {
     return v;
 }
 DEVI int ca_mirror(int i, int S) { return i < 0 ? -1 - i : i >= S ? 2 * S - 1 - i : i; }
+DEVI int ca_reflect(int i, int S) { return i < 0 ? -i : i >= S ? 2 * S - 2 - i : i; }
 
 static int ca_chunks(int S) {  // of the statistics pass: about a thousand 4-pixel groups each, S alone decides
     const long long G = (long long)S * S / 4;
@@ -248,13 +270,17 @@ DEVI void ca_blur_store(const float* A, float* T, const float* wl, int AH, int A
     }
 }
 
+// FT = false: the MoCo rule (R = ceil(3 sigma) <= 6, weights over the sum of the taps kept, symmetric edges);
+// FT = true: the finetune rule (25 taps, weights over the sum of all 25, reflect edges).
+template <bool FT>
 __global__ __launch_bounds__(CA_THREADS) void color_apply_kernel(
     const float* __restrict__ x, float* __restrict__ out, const float* __restrict__ factors,
     const unsigned char* __restrict__ order, const unsigned char* __restrict__ flags,
     const float* __restrict__ sigma, const float* __restrict__ partial, int S, int chunks, int TW, int TH,
     int tiles_x, int tiles, f32x4 nscale, f32x4 nshift) {
+    constexpr int RMAX = FT ? CA_FT_RMAX : CA_RMAX, RPAD = FT ? CA_FT_RMAX : CA_RPAD;
     extern __shared__ __attribute__((aligned(16))) float ca_lds[];
-    __shared__ float wl[CA_RMAX + 1];
+    __shared__ float wl[RMAX + 1];
     const int t = threadIdx.x;
     const int b = blockIdx.x / tiles, tile = blockIdx.x - b * tiles;
     const int ty = tile / tiles_x, y0 = ty * TH, x0 = (tile - ty * tiles_x) * TW;
@@ -271,7 +297,9 @@ __global__ __launch_bounds__(CA_THREADS) void color_apply_kernel(
     }
     const bool solarize = (s.flags & 2) != 0;
 
-    if (!(s.sigma > 0.f)) {  // (uniform) no halo, no LDS
+    // (uniform) no halo, no LDS.  Under the finetune rule a sigma below 1 / 16 is no blur either: every weight but the
+    // centre's is below exp(-128) of it, 0 in fp32 (the reference's range starts at 0.001)
+    if (!(s.sigma > (FT ? 0.0625f : 0.f))) {
         for (int i = t; i < nro * ng; i += CA_THREADS) {
             const int g = i % ng, orow = i / ng;
             const size_t o = (size_t)(y0 + orow) * S + x0 + 4 * g;
@@ -286,22 +314,23 @@ __global__ __launch_bounds__(CA_THREADS) void color_apply_kernel(
     }
 
     // ceil(3 sigma) in fp64: the product is exact there, in fp32 it can round down onto an integer
-    const double r3 = ceil(3.0 * (double)s.sigma);
-    const int R = r3 < (double)CA_RMAX ? (int)r3 : CA_RMAX;  // >= 1; +inf clamps
+    const double r3 = ceil((FT ? 6.0 : 3.0) * (double)s.sigma);
+    int R = r3 < (double)RMAX ? (int)r3 : RMAX;  // >= 1; +inf clamps
+    if (FT) R = (R + 1) & ~1;                    // even radii only: half the instantiations, a tap of weight ~0 more
     const int RP = (R + 3) & ~3;
-    if (t <= CA_RMAX) {
+    if (t <= RMAX) {
         const double inv2 = 0.5 / ((double)s.sigma * (double)s.sigma);
         double sum = 1.0;
-        for (int k = 1; k <= R; ++k) sum += 2.0 * exp(-(double)(k * k) * inv2);
+        for (int k = 1; k <= (FT ? RMAX : R); ++k) sum += 2.0 * exp(-(double)(k * k) * inv2);
         wl[t] = t <= R ? (float)(exp(-(double)(t * t) * inv2) / sum) : 0.f;
     }
-    const int AH = TH + 2 * CA_RMAX, AW = TW + 2 * CA_RPAD;
+    const int AH = TH + 2 * RMAX, AW = TW + 2 * RPAD;
     float* A = ca_lds;                   // [3][AH][AW]
     float* T = A + (size_t)3 * AH * AW;  // [3][AH][TW]
     const int nra = nro + 2 * R, nga = (nco + 2 * RP) >> 2;
     for (int i = t; i < nra * nga; i += CA_THREADS) {
         const int ag = i % nga, ar = i / nga;
-        const int y = ca_mirror(y0 - R + ar, S), c0 = x0 - RP + 4 * ag;
+        const int y = FT ? ca_reflect(y0 - R + ar, S) : ca_mirror(y0 - R + ar, S), c0 = x0 - RP + 4 * ag;
         const float* p = src + (size_t)y * S;
         f32x4 r, gg, bb;
         if (c0 >= 0 && c0 < S) {  // S and c0 are multiples of 4: a group is inside the row or outside it
@@ -309,7 +338,8 @@ __global__ __launch_bounds__(CA_THREADS) void color_apply_kernel(
         } else {
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
-                const int c = ca_mirror(c0 + j, S);  // |c0 + j| overshoots by at most 8 <= S
+                // c0 + j overshoots by at most 8 <= S (symmetric), by at most 12 < S (reflect)
+                const int c = FT ? ca_reflect(c0 + j, S) : ca_mirror(c0 + j, S);
                 r[j] = p[c], gg[j] = p[plane + c], bb[j] = p[2 * plane + c];
             }
         }
@@ -320,6 +350,17 @@ __global__ __launch_bounds__(CA_THREADS) void color_apply_kernel(
         st4(a + (size_t)2 * AH * AW, bb);
     }
     __syncthreads();
+    if (FT) {
+        switch (R) {  // (uniform)
+        case 2: ca_blur_store<2>(A, T, wl, AH, AW, TW, nro, nco, dst, S, solarize, nscale, nshift); break;
+        case 4: ca_blur_store<4>(A, T, wl, AH, AW, TW, nro, nco, dst, S, solarize, nscale, nshift); break;
+        case 6: ca_blur_store<6>(A, T, wl, AH, AW, TW, nro, nco, dst, S, solarize, nscale, nshift); break;
+        case 8: ca_blur_store<8>(A, T, wl, AH, AW, TW, nro, nco, dst, S, solarize, nscale, nshift); break;
+        case 10: ca_blur_store<10>(A, T, wl, AH, AW, TW, nro, nco, dst, S, solarize, nscale, nshift); break;
+        default: ca_blur_store<12>(A, T, wl, AH, AW, TW, nro, nco, dst, S, solarize, nscale, nshift); break;
+        }
+        return;
+    }
     switch (R) {  // (uniform)
     case 1: ca_blur_store<1>(A, T, wl, AH, AW, TW, nro, nco, dst, S, solarize, nscale, nshift); break;
     case 2: ca_blur_store<2>(A, T, wl, AH, AW, TW, nro, nco, dst, S, solarize, nscale, nshift); break;
@@ -337,27 +378,30 @@ extern "C" size_t ssl4gie_color_augment_workspace_bytes(int B, int S) {
     return sizeof(float) * (size_t)B * ca_chunks(S);
 }
 
-extern "C" int ssl4gie_color_augment(const float* x, float* out, int B, int S, const float* factors,
-                                     const unsigned char* order, const unsigned char* flags, const float* sigma,
-                                     const float* mean, const float* std, void* workspace, size_t workspace_bytes,
-                                     void* stream) {
+template <bool FT>
+static int ca_launch(const float* x, float* out, int B, int S, const float* factors, const unsigned char* order,
+                     const unsigned char* flags, const float* sigma, const float* mean, const float* std,
+                     void* workspace, size_t workspace_bytes, void* stream) {
+    constexpr int RMAX = FT ? CA_FT_RMAX : CA_RMAX, RPAD = FT ? CA_FT_RMAX : CA_RPAD;
+    constexpr int TILE_H = FT ? CA_FT_TILE_H : CA_TILE_H;
     REQUIRE(x && out && factors && order && flags && sigma && mean && std && workspace);
     REQUIRE(ca_shape_ok(B, S));
+    if (FT) REQUIRE(S >= 16);  // a reflect halo of 12 needs S > 12
     for (int c = 0; c < 3; ++c) REQUIRE(std[c] != 0.f);
     REQUIRE((const void*)x != (const void*)out);  // the stencil reads its neighbours' inputs
     REQUIRE(((uintptr_t)x | (uintptr_t)out) % 16 == 0);  // 16-byte loads and stores
     REQUIRE(workspace_bytes >= ssl4gie_color_augment_workspace_bytes(B, S));
     const int chunks = ca_chunks(S);
     const int G = (int)((long long)S * S / 4), per_chunk = (G + chunks - 1) / chunks;
-    const int TW = ca_tile_w(S), TH = S < CA_TILE_H ? S : CA_TILE_H;
+    const int TW = ca_tile_w(S), TH = S < TILE_H ? S : TILE_H;
     const int tiles_x = (S + TW - 1) / TW, tiles = tiles_x * ((S + TH - 1) / TH);
     REQUIRE((long long)S * S <= 0x7fffffffLL && (long long)B * tiles <= 0x7fffffffLL &&
             (long long)B * chunks <= 0x7fffffffLL);
-    const size_t lds = sizeof(float) * 3 * (size_t)(TH + 2 * CA_RMAX) * (size_t)(2 * TW + 2 * CA_RPAD);
-    static bool attr = false;
+    const size_t lds = sizeof(float) * 3 * (size_t)(TH + 2 * RMAX) * (size_t)(2 * TW + 2 * RPAD);
+    static bool attr = false;  // one per instantiation
     if (!attr) {
-        HIP_RET(hipFuncSetAttribute((const void*)color_apply_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                    (int)(sizeof(float) * 3 * (CA_TILE_H + 2 * CA_RMAX) * (2 * 64 + 2 * CA_RPAD))));
+        HIP_RET(hipFuncSetAttribute((const void*)color_apply_kernel<FT>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                    (int)(sizeof(float) * 3 * (TILE_H + 2 * RMAX) * (2 * 64 + 2 * RPAD))));
         attr = true;
     }
     hipLaunchKernelGGL(color_stats_kernel, dim3((unsigned)(B * chunks)), dim3(CA_STAT_THREADS), 0,
@@ -365,9 +409,23 @@ extern "C" int ssl4gie_color_augment(const float* x, float* out, int B, int S, c
     LAUNCH_CHECK();
     const f32x4 nscale = {1.f / std[0], 1.f / std[1], 1.f / std[2], 0.f};
     const f32x4 nshift = {-mean[0] / std[0], -mean[1] / std[1], -mean[2] / std[2], 0.f};
-    hipLaunchKernelGGL(color_apply_kernel, dim3((unsigned)(B * tiles)), dim3(CA_THREADS), lds, (hipStream_t)stream, x,
-                       out, factors, order, flags, sigma, (const float*)workspace, S, chunks, TW, TH, tiles_x, tiles,
-                       nscale, nshift);
+    hipLaunchKernelGGL(color_apply_kernel<FT>, dim3((unsigned)(B * tiles)), dim3(CA_THREADS), lds,
+                       (hipStream_t)stream, x, out, factors, order, flags, sigma, (const float*)workspace, S, chunks,
+                       TW, TH, tiles_x, tiles, nscale, nshift);
     LAUNCH_CHECK();
     return 0;
+}
+
+extern "C" int ssl4gie_color_augment(const float* x, float* out, int B, int S, const float* factors,
+                                     const unsigned char* order, const unsigned char* flags, const float* sigma,
+                                     const float* mean, const float* std, void* workspace, size_t workspace_bytes,
+                                     void* stream) {
+    return ca_launch<false>(x, out, B, S, factors, order, flags, sigma, mean, std, workspace, workspace_bytes, stream);
+}
+
+extern "C" int ssl4gie_color_augment_ft(const float* x, float* out, int B, int S, const float* factors,
+                                        const unsigned char* order, const unsigned char* flags, const float* sigma,
+                                        const float* mean, const float* std, void* workspace, size_t workspace_bytes,
+                                        void* stream) {
+    return ca_launch<true>(x, out, B, S, factors, order, flags, sigma, mean, std, workspace, workspace_bytes, stream);
 }

@@ -25,6 +25,15 @@ views' recipes:
         loader.sampler.set_epoch(epoch)
         for it, (samples, _) in enumerate(loader):                      # engine_pretrain.py:39-45, as written
             samples = samples.to(device, non_blocking=True)             # already there: returns itself
+
+The finetune loaders (Binary_segmentation / Depth_estimation / Classification `Data/dataloaders.py`: ColorJitter, a
+25-tap GaussianBlur, Normalize, two flips, a nearest-neighbour affine or rotation, the mask or depth map through the
+same flips and affine) are `FinetuneAugment`: ops.color_augment_ft, then ops.paired_warp on image and target at once.
+
+    bank = DeviceImageBank.from_npy("train_224.npy", "cuda", targets="train_224_masks.npy")
+    loader = DeviceLoader(bank, 16, transform=FinetuneAugment.segmentation())
+    for batch_idx, (data, target) in enumerate(loader):                 # Binary_segmentation/train.py, as written
+        data, target = data.to(device), target.to(device)               # already there
 """
 from __future__ import annotations
 
@@ -39,11 +48,15 @@ from .ops import IMAGENET_MEAN, IMAGENET_STD
 
 
 class DeviceImageBank:
-    """[n, Hs, Ws, 3] uint8 images (one stored size) on a device, with optional integer labels.  A map-style
-    dataset whose items are (index, label): torch's own samplers (RandomSampler, DistributedSampler and its
-    set_epoch) work on it unchanged, and what they hand out is what DeviceLoader sends to the device."""
+    """[n, Hs, Ws, 3] uint8 images (one stored size) on a device, with optional integer labels and optional
+    per-pixel targets [n, Hs, Ws] (masks: uint8, v / 255; depth maps: uint16 — or the same bits in int16 storage —,
+    v / 65535; or fp32 as it is).  A map-style dataset whose items are (index, label): torch's own samplers
+    (RandomSampler, DistributedSampler and its set_epoch) work on it unchanged, and what they hand out is what
+    DeviceLoader sends to the device."""
 
-    def __init__(self, images_u8, labels=None):
+    TARGET_DTYPES = (torch.uint8, torch.uint16, torch.int16, torch.float32)
+
+    def __init__(self, images_u8, labels=None, targets=None):
         if not (torch.is_tensor(images_u8) and images_u8.dtype == torch.uint8 and images_u8.dim() == 4
                 and images_u8.shape[3] == 3 and images_u8.is_contiguous() and images_u8.shape[0] >= 1):
             raise ValueError("DeviceImageBank needs a contiguous uint8 tensor [n, Hs, Ws, 3], n >= 1")
@@ -58,6 +71,12 @@ class DeviceImageBank:
                 raise ValueError(f"labels must have shape ({n},), got {tuple(host.shape)}")
             self._labels_host = host.tolist()
             self.labels = host.to(images_u8.device)
+        if targets is not None and not (
+                torch.is_tensor(targets) and targets.dtype in self.TARGET_DTYPES and targets.is_contiguous()
+                and tuple(targets.shape) == tuple(images_u8.shape[:3]) and targets.device == images_u8.device):
+            raise ValueError(f"targets must be a contiguous uint8, uint16, int16 or float32 tensor "
+                             f"{tuple(images_u8.shape[:3])} on the images' device")
+        self.targets = targets
 
     device = property(lambda self: self.images.device)
     stored_size = property(lambda self: (int(self.images.shape[1]), int(self.images.shape[2])))
@@ -72,25 +91,36 @@ class DeviceImageBank:
         return i, (0 if self._labels_host is None else self._labels_host[i])
 
     @classmethod
-    def from_uint8(cls, array_or_tensor, device, labels=None):
-        t = array_or_tensor if torch.is_tensor(array_or_tensor) else torch.from_numpy(np.ascontiguousarray(array_or_tensor))
-        return cls(t.contiguous().to(device), labels)
+    def from_uint8(cls, array_or_tensor, device, labels=None, targets=None):
+        as_tensor = lambda a: a if torch.is_tensor(a) else torch.from_numpy(np.ascontiguousarray(a))
+        t = as_tensor(array_or_tensor)
+        if targets is not None:
+            targets = as_tensor(targets).contiguous().to(device)
+        return cls(t.contiguous().to(device), labels, targets)
 
     @classmethod
-    def from_npy(cls, path, device, labels=None, chunk_bytes=256 << 20):
-        """`path` is a .npy of [n, Hs, Ws, 3] uint8 (tools/pack_images.py).  The file is memory-mapped and
-        copied chunk by chunk, so the host never holds a second copy of it."""
+    def from_npy(cls, path, device, labels=None, chunk_bytes=256 << 20, targets=None):
+        """`path` is a .npy of [n, Hs, Ws, 3] uint8, `targets` (optional) one of [n, Hs, Ws] uint8, uint16 or float32
+        (tools/pack_images.py writes both).  The files are memory-mapped and copied chunk by chunk, so the host never
+        holds a second copy of them."""
+        def to_device(arr):
+            dst = torch.empty(arr.shape, dtype=getattr(torch, arr.dtype.name), device=device)
+            step = max(1, int(chunk_bytes) // max(1, int(np.prod(arr.shape[1:])) * arr.dtype.itemsize))
+            for a in range(0, arr.shape[0], step):
+                dst[a:a + step].copy_(torch.from_numpy(np.array(arr[a:a + step])))
+            return dst
+
         arr = np.load(path, mmap_mode="r")
         if arr.dtype != np.uint8 or arr.ndim != 4 or arr.shape[3] != 3:
             raise ValueError(f"{path}: expected uint8 [n, Hs, Ws, 3], got {arr.dtype} {arr.shape}")
-        n = arr.shape[0]
-        dst = torch.empty(arr.shape, dtype=torch.uint8, device=device)
-        step = max(1, int(chunk_bytes) // max(1, int(np.prod(arr.shape[1:]))))
-        for a in range(0, n, step):
-            dst[a:a + step].copy_(torch.from_numpy(np.array(arr[a:a + step])))
+        if targets is not None:
+            tgt = np.load(targets, mmap_mode="r")
+            if tgt.dtype not in (np.uint8, np.uint16, np.float32) or tgt.shape != arr.shape[:3]:
+                raise ValueError(f"{targets}: expected uint8, uint16 or float32 {arr.shape[:3]}, got {tgt.dtype} {tgt.shape}")
+            targets = to_device(tgt)
         if isinstance(labels, str):
             labels = np.load(labels)
-        return cls(dst, labels)
+        return cls(to_device(arr), labels, targets)
 
 
 @functools.lru_cache(maxsize=64)
@@ -230,9 +260,115 @@ class MoCoV3Views:
         return [color(crop(bank, index)) for crop, color in zip(self.crops, self.colors)]
 
 
+def affine_matrices(angle, translate=None, scale=None, shear=None, dtype=torch.float32):
+    """torchvision's _get_inverse_affine_matrix(center=(0, 0), angle, translate, scale, shear=(shear, 0)) — the matrix
+    TF.affine hands its tensor path — for a batch: angle [B] and shear [B] in degrees, translate [B, 2] = (tx, ty) in
+    pixels, scale [B]; None = 0, (0, 0), 1, 0.  float64 on angle's device, vectorised, no host read-back.  Returns
+    [B, 6] in `dtype` (fp32 is what the kernel takes): the map from centred OUTPUT coordinates to centred source coordinates that ops.paired_warp takes.
+    TF.rotate(angle) is affine_matrices(-angle)."""
+    rot = torch.deg2rad(angle.to(torch.float64))
+    sx = torch.zeros_like(rot) if shear is None else torch.deg2rad(shear.to(torch.float64))
+    sc = torch.ones_like(rot) if scale is None else scale.to(torch.float64)
+    t = torch.zeros(rot.shape[0], 2, dtype=torch.float64, device=rot.device) if translate is None else translate.to(torch.float64)
+    # with sy = 0: a = cos(rot), c = sin(rot)
+    a, c = torch.cos(rot), torch.sin(rot)
+    b = -torch.cos(rot) * torch.tan(sx) - torch.sin(rot)
+    d = -torch.sin(rot) * torch.tan(sx) + torch.cos(rot)
+    m0, m1, m3, m4 = d / sc, -b / sc, -c / sc, a / sc
+    m2 = m0 * -t[:, 0] + m1 * -t[:, 1]
+    m5 = m3 * -t[:, 0] + m4 * -t[:, 1]
+    return torch.stack([m0, m1, m2, m3, m4, m5], dim=1).to(dtype).contiguous()
+
+
+class FinetuneAugment:
+    """The train-time augmentation of the reference's finetune loaders for DeviceLoader, drawn and computed on the
+    bank's device: ColorJitter(brightness, contrast, saturation, hue) (always applied) -> GaussianBlur((25, 25),
+    blur_sigma) (None: no blur) -> ToTensor -> Normalize(mean, std) -> horizontal and vertical flip, each when a
+    uniform draw exceeds 0.5 -> TF.affine(angle U(-a, a), translate U(-t size, t size)^2, scale U(lo, hi), shear
+    U(-s, s)), nearest, the image filled with `fill` (a number in normalised space, or "black" = the normalised value
+    of a black pixel) and the target with 0.  `affine` is None or a dict with any of angle, translate (a fraction of
+    the size), scale (lo, hi), shear; keys left out are not drawn (a dict with angle alone is RandomRotation: its range
+    is symmetric, so TF.rotate's opposite sign convention draws the same distribution).
+    __call__(bank, index) -> images fp32 [B, 3, size, size], or (images, targets fp32 [B, 1, size, size]) for a bank
+    with targets, which go through the same flips and affine.  The bank's stored size must be `size`: the reference
+    resizes to 224 when it loads a file, tools/pack_images.py does that once."""
+
+    def __init__(self, size=224, brightness=0.4, contrast=0.5, saturation=0.25, hue=0.01, blur_sigma=(0.001, 2.0),
+                 hflip=True, vflip=True, affine=None, fill=-1.0, mean=IMAGENET_MEAN, std=IMAGENET_STD, generator=None):
+        if size < 16 or size % 4:
+            raise ValueError(f"size must be >= 16 and a multiple of 4, got {size}")
+        if blur_sigma is not None and not 0 < blur_sigma[0] <= blur_sigma[1]:
+            raise ValueError(f"blur_sigma must be None or 0 < lo <= hi, got {tuple(blur_sigma)}")
+        affine = None if affine is None else dict(affine)
+        if affine is not None and set(affine) - {"angle", "translate", "scale", "shear"}:
+            raise ValueError(f"affine takes angle, translate, scale and shear, got {sorted(affine)}")
+        if fill != "black" and isinstance(fill, str):
+            raise ValueError(f"fill must be a number or 'black', got {fill!r}")
+        self.size, self.hflip, self.vflip, self.affine = int(size), bool(hflip), bool(vflip), affine
+        self.blur_sigma = None if blur_sigma is None else (float(blur_sigma[0]), float(blur_sigma[1]))
+        self.mean, self.std, self.generator = tuple(mean), tuple(std), generator
+        self.fill = tuple((0.0 - m) / s for m, s in zip(self.mean, self.std)) if fill == "black" else (float(fill),) * 3
+        # the jitter parameters are ColorAugment's draw with nothing else switched on
+        self.color = ColorAugment(brightness, contrast, saturation, hue, jitter_p=1.0, gray_p=0.0, blur_p=0.0,
+                                  solarize_p=0.0, mean=mean, std=std, generator=generator)
+
+    @classmethod
+    def segmentation(cls, size=224, **kw):
+        """Binary_segmentation/Data/dataloaders.py:62-87, dataset.py:46-63"""
+        kw.setdefault("affine", dict(angle=180.0, translate=1.0 / 8.0, scale=(0.5, 1.5), shear=22.5))
+        return cls(size, **kw)
+
+    @classmethod
+    def depth(cls, size=224, **kw):
+        """Depth_estimation/Data/dataloaders.py:55-65, dataset.py:47-70: jitter and the two flips"""
+        kw.setdefault("blur_sigma", None)
+        return cls(size, **kw)
+
+    @classmethod
+    def classification(cls, size=224, **kw):
+        """Classification/Data/dataloaders.py:62-72: jitter, blur, flips, RandomRotation(180) with black fill"""
+        kw.setdefault("affine", dict(angle=180.0))
+        kw.setdefault("fill", "black")
+        return cls(size, **kw)
+
+    def draw(self, B, device):
+        """(factors fp32 [B, 4], order uint8 [B, 4], flags uint8 [B], sigma fp32 [B], flip uint8 [B], matrix fp32
+        [B, 6]); advances the generator.  No blur: sigma = 0; no affine: identity matrices."""
+        factors, order, flags, _ = self.color.draw(B, device)
+        u = torch.rand(B, 8, dtype=torch.float64, device=device, generator=self.generator)
+        if self.blur_sigma is None:
+            sigma = torch.zeros(B, dtype=torch.float32, device=device)
+        else:
+            lo, hi = self.blur_sigma
+            sigma = (lo + u[:, 0] * (hi - lo)).to(torch.float32)
+        flip = ((u[:, 1] > 0.5) & self.hflip).to(torch.uint8) + 2 * ((u[:, 2] > 0.5) & self.vflip).to(torch.uint8)
+        spread = lambda col, half: (2.0 * u[:, col] - 1.0) * half
+        a = self.affine or {}
+        angle = spread(3, float(a.get("angle", 0.0)))
+        t = float(a.get("translate", 0.0)) * self.size
+        lo, hi = a.get("scale", (1.0, 1.0))
+        matrix = affine_matrices(angle, torch.stack([spread(4, t), spread(5, t)], dim=1), lo + u[:, 6] * (hi - lo),
+                                 spread(7, float(a.get("shear", 0.0))))
+        return factors, order, flags, sigma, flip, matrix
+
+    def __call__(self, bank, index):
+        if bank.stored_size != (self.size, self.size):
+            raise ValueError(f"FinetuneAugment({self.size}) needs a bank stored at {self.size} x {self.size}, got "
+                             f"{bank.stored_size}: pack it at that size (tools/pack_images.py --size)")
+        factors, order, flags, sigma, flip, matrix = self.draw(index.shape[0], index.device)
+        # [0, 1] images: ToTensor.  (view_sample_u8 with the whole image as its box gives these very bits and would
+        # save the gathered copy; both multiply by fp32 1 / 255, which is not v / 255 for 126 of the 256 levels.)
+        x = ops.normalize_u8(bank.images[index], (0.0, 0.0, 0.0), (1.0, 1.0, 1.0))
+        x = ops.color_augment_ft(x, factors, order, flags, sigma, self.mean, self.std)
+        if bank.targets is None:
+            return ops.paired_warp(x, matrix, flip, self.fill)
+        return ops.paired_warp(x, matrix, flip, self.fill, bank.targets, index, 0.0)
+
+
 class DeviceLoader:
     """What the reference's DataLoader is to its training loops, over a DeviceImageBank: len(), iteration that
-    yields (samples, labels) — ([view1, view2], labels) for a two-view transform — and `.sampler` for
+    yields (samples, labels) — ([view1, view2], labels) for a two-view transform; (samples, targets) for a bank
+    with per-pixel targets, whose transform must return that pair (FinetuneAugment) — and `.sampler` for
     set_epoch.  Per batch the host takes `batch_size` plain ints from the sampler and sends them as one int64
     tensor (pinned, non_blocking); the transform does the rest on the device.  Nothing synchronises."""
 
@@ -253,7 +389,12 @@ class DeviceLoader:
         if dev.type != "cpu":
             host = host.pin_memory()
         index = host.to(dev, non_blocking=True)
-        return self.transform(self.bank, index), self.bank.labels[index]
+        out = self.transform(self.bank, index)
+        if self.bank.targets is None:
+            return out, self.bank.labels[index]
+        if not (isinstance(out, tuple) and len(out) == 2):
+            raise TypeError("a bank with targets needs a transform that returns (images, targets), such as FinetuneAugment")
+        return out
 
     def __iter__(self):
         idx = []

@@ -1390,20 +1390,32 @@ def color_augment(x, factors, order, flags, sigma, mean=IMAGENET_MEAN, std=IMAGE
     (fp32 [B]; 0 = none, R = ceil(3 sigma) <= 6, symmetric edges), solarize at 128 / 255 where flags[b] & 2
     (flags uint8 [B]), then (x - mean) / std.  The rule is spelled out in include/ssl4gie_hip.h.  Returns the new
     fp32 [B, 3, S, S]; `out`, if given, must not share memory with x (the blur reads its neighbours' inputs)."""
+    return _color_stage("color_augment", 8, x, factors, order, flags, sigma, mean, std, out)
+
+
+def color_augment_ft(x, factors, order, flags, sigma, mean=IMAGENET_MEAN, std=IMAGENET_STD, out=None):
+    """The colour stage of the finetune loaders (ColorJitter -> GaussianBlur((25, 25), sigma) -> Normalize): the
+    arguments and rule of color_augment, but the blur is torchvision's tensor-path one — 25 taps, k in [-12, 12],
+    weights exp(-k^2 / 2 sigma^2) over their sum, REFLECT edges (index -i reads i) — hence S >= 16.  sigma[b] = 0: none.
+    `out`, if given, must not share memory with x."""
+    return _color_stage("color_augment_ft", 16, x, factors, order, flags, sigma, mean, std, out)
+
+
+def _color_stage(name, s_min, x, factors, order, flags, sigma, mean, std, out):
     _dev(x, factors, order, flags, sigma, out)
     _f32(x, factors, sigma, out)
     if x.dim() != 4 or x.shape[1] != 3 or x.shape[2] != x.shape[3]:
-        raise ValueError(f"color_augment needs x [B, 3, S, S], got {tuple(x.shape)}")
+        raise ValueError(f"{name} needs x [B, 3, S, S], got {tuple(x.shape)}")
     B, _, S, _ = x.shape
-    if S < 8 or S % 4:
-        raise ValueError(f"color_augment needs S >= 8 and a multiple of 4, got {S}")
+    if S < s_min or S % 4:
+        raise ValueError(f"{name} needs S >= {s_min} and a multiple of 4, got {S}")
     if order.dtype != torch.uint8 or flags.dtype != torch.uint8:
         raise TypeError(f"order and flags must be uint8, got {order.dtype} and {flags.dtype}")
     if tuple(factors.shape) != (B, 4) or tuple(order.shape) != (B, 4) or tuple(flags.shape) != (B,) \
             or tuple(sigma.shape) != (B,):
-        raise ValueError("color_augment needs factors [B, 4], order [B, 4], flags [B], sigma [B]")
+        raise ValueError(f"{name} needs factors [B, 4], order [B, 4], flags [B], sigma [B]")
     if any(t.device != x.device for t in (factors, order, flags, sigma)):
-        raise ValueError("color_augment needs all its tensors on one device")
+        raise ValueError(f"{name} needs all its tensors on one device")
     if out is None:
         out = torch.empty_like(x)
     else:
@@ -1411,13 +1423,61 @@ def color_augment(x, factors, order, flags, sigma, mean=IMAGENET_MEAN, std=IMAGE
             raise ValueError("out must have x's shape and device")
         nbytes = x.numel() * 4
         if out.data_ptr() < x.data_ptr() + nbytes and x.data_ptr() < out.data_ptr() + nbytes:
-            raise ValueError("color_augment cannot run in place: out shares memory with x")
+            raise ValueError(f"{name} cannot run in place: out shares memory with x")
     if B == 0:
         return out
     L = _lib.load()
     ws = torch.empty(L.ssl4gie_color_augment_workspace_bytes(B, S), dtype=torch.uint8, device=x.device)
     m = (C.c_float * 3)(*mean)
     s = (C.c_float * 3)(*std)
-    _lib.check(L.ssl4gie_color_augment(ptr(x), ptr(out), B, S, ptr(factors), ptr(order), ptr(flags), ptr(sigma), m, s,
-                                       ptr(ws), ws.numel(), stream()), "color_augment")
+    _lib.check(getattr(L, "ssl4gie_" + name)(ptr(x), ptr(out), B, S, ptr(factors), ptr(order), ptr(flags), ptr(sigma), m, s,
+                                              ptr(ws), ws.numel(), stream()), name)
     return out
+
+
+_TGT_CODES = {torch.uint8: _lib.TGT_U8, torch.uint16: _lib.TGT_U16, torch.int16: _lib.TGT_U16,
+              torch.float32: _lib.TGT_F32}
+
+
+def paired_warp(img, matrix, flip, fill_img, tgt_bank=None, index=None, fill_tgt=0.0):
+    """Flips + nearest-neighbour affine of the finetune loaders on a device batch and, through the same map in the
+    same launch, on its targets.  img fp32 [B, 3, S, S]; matrix fp32 [B, 6] (data.affine_matrices: torchvision's
+    inverse matrix) or None = identity; flip uint8 [B] (bit 0 horizontal, bit 1 vertical) or None; fill_img three
+    floats, the value of the image where the map leaves it.  With tgt_bank ([n, S, S] uint8, uint16 — int16 storage
+    is read as uint16 — or fp32) and index (int64 [B]) the target of sample b is tgt_bank[index[b]] scaled by 1 / 255,
+    1 / 65535 or 1, filled with fill_tgt; an index outside the bank gives an all-NaN target.  The rule is spelled
+    out in include/ssl4gie_hip.h.  Returns img_out, or (img_out, tgt_out fp32 [B, 1, S, S])."""
+    _dev(img, matrix, flip, tgt_bank, index)
+    _f32(img, matrix)
+    if img.dim() != 4 or img.shape[1] != 3 or img.shape[2] != img.shape[3]:
+        raise ValueError(f"paired_warp needs img [B, 3, S, S], got {tuple(img.shape)}")
+    B, _, S, _ = img.shape
+    if S < 4 or S % 4:
+        raise ValueError(f"paired_warp needs S >= 4 and a multiple of 4, got {S}")
+    if matrix is not None and tuple(matrix.shape) != (B, 6):
+        raise ValueError(f"matrix must be [{B}, 6], got {tuple(matrix.shape)}")
+    if flip is not None and (flip.dtype != torch.uint8 or tuple(flip.shape) != (B,)):
+        raise ValueError(f"flip must be uint8 [{B}]")
+    if len(fill_img) != 3:
+        raise ValueError("fill_img must hold three values")
+    if (tgt_bank is None) != (index is None):
+        raise ValueError("tgt_bank and index come together")
+    tgt_out, dtype, n = None, 0, 0
+    if tgt_bank is not None:
+        if tgt_bank.dtype not in _TGT_CODES:
+            raise TypeError(f"tgt_bank must be uint8, uint16, int16 or float32, got {tgt_bank.dtype}")
+        if tgt_bank.dim() != 3 or tuple(tgt_bank.shape[1:]) != (S, S) or tgt_bank.shape[0] < 1:
+            raise ValueError(f"tgt_bank must be [n, {S}, {S}], got {tuple(tgt_bank.shape)}")
+        if index.dtype != torch.int64 or tuple(index.shape) != (B,):
+            raise ValueError(f"index must be int64 [{B}]")
+        dtype, n = _TGT_CODES[tgt_bank.dtype], tgt_bank.shape[0]
+        tgt_out = torch.empty(B, 1, S, S, dtype=torch.float32, device=img.device)
+    if any(t is not None and t.device != img.device for t in (matrix, flip, tgt_bank, index)):
+        raise ValueError("paired_warp needs all its tensors on one device")
+    img_out = torch.empty_like(img)
+    if B:
+        fill = (C.c_float * 3)(*fill_img)
+        _lib.check(_lib.load().ssl4gie_paired_warp(ptr(img), ptr(img_out), ptr(tgt_bank), dtype, n, ptr(index),
+                                                   ptr(tgt_out), ptr(matrix), ptr(flip), fill, float(fill_tgt), B, S,
+                                                   stream()), "paired_warp")
+    return img_out if tgt_out is None else (img_out, tgt_out)
