@@ -15,7 +15,9 @@
  *   - callable from any host thread; the only mutable process-wide settings are the execution
  *     options ssl4gie_set_wgrad_stream / ssl4gie_set_compute_cus and the profiler;
  *   - ssl4gie_abi_version() = 12 (ssl4gie_view_sample_u8, after it ssl4gie_color_augment{_workspace_bytes,}, and after those ssl4gie_color_augment_ft / ssl4gie_paired_warp, joined revision 12
- *     without a new number: added symbols, nothing existing changed, so a caller built against the earlier 12 runs unchanged; 11: before the sixteen BatchNorm entry points that had grown one per fusion (ssl4gie_bn_fwd / _fwd_partials / _fwd_partials_bits /
+ *     without a new number: added symbols, nothing existing changed, so a caller built against the earlier 12 runs unchanged; the evaluation
+ *     metrics ssl4gie_seg_{counts,scores} / ssl4gie_confusion_{update,scores} / ssl4gie_lower_median_{workspace_bytes,f32} / ssl4gie_depth_eval{_workspace_bytes,}
+ *     joined it the same way; 11: before the sixteen BatchNorm entry points that had grown one per fusion (ssl4gie_bn_fwd / _fwd_partials / _fwd_partials_bits /
  *     _coef_partials / _coef_stats / _apply_bits, _stats / _stats_partials, _bwd / _bwd_xmask / _bwd_bits, _bwd_reduce / _reduce_xmask / _reduce_bits,
  *     _bwd_apply / _apply_xmask) were REPLACED by five with a source and a mask kind — the same launches, new signatures; 10: before the diagnostics entry point that read the 256x256 NT kernel's in-kernel
  *     time stamps was REMOVED with the debug build of the library — the one removal in this history; 9: before ssl4gie_infonce_{workspace_bytes,loss} / ssl4gie_cross_entropy{_workspace_bytes,} /
@@ -810,6 +812,61 @@ size_t ssl4gie_bt_loss_workspace_bytes(int D);
 int ssl4gie_bt_loss(const float* c, float* loss, int D, float lambd, void* workspace, void* stream);
 int ssl4gie_bt_loss_grad(const float* c, const float* scale, void* w, void* wt, int dtype, int D, float lambd,
                          void* stream);
+
+/* ---------------------------------------------------------------- evaluation metrics (joined ABI 12)
+ * The `test()` loops and eval_*.py CLIs of the three finetune heads.  Integer counts by integer atomics (order-free),
+ * floating sums as per-block partials added in a fixed order in fp64, no float atomics: bit-identical from run to run.
+ * No allocation, no host synchronisation; every output stays on the device.
+ *
+ * seg_counts   the thresholding shared by DiceScore / IoU / Precision / Recall (Binary_segmentation/Metrics/
+ *              performance.py:13-19, :38-44, :61-67, :82-88): counts int64 [B, 3] = (|m1|, |m2|, |m1 & m2|) per image,
+ *              m1 = probs > 0.5, m2 = target > 0.5.  logits [B, Hin, Win] of logits_dtype (SSL4GIE_F32 / SSL4GIE_BF16),
+ *              target [B, H, W] of target_dtype (SSL4GIE_TGT_U8 / SSL4GIE_TGT_F32).  Where (Hin, Win) != (H, W) the
+ *              logits are resampled per target pixel and never stored: F.interpolate(mode = "bilinear", align_corners =
+ *              False) without antialiasing, in fp32 — TF.resize of a tensor at eval_segmentation.py:36-37.  sigmoid != 0:
+ *              m1 = logit > 0 (the reference's fp32 sigmoid(x) > 0.5 is false for 0 < x <~ 1.2e-7 as well: DESIGN.md
+ *              section 8); sigmoid == 0: m1 = logit > 0.5.  counts is overwritten.  H * W and Hin * Win < 2^31.
+ * seg_scores   scores fp32 [4] = batch means of Dice, IoU, precision, recall from counts, each by the reference's fp32
+ *              formula in its operation order (performance.py:21-26, :46-49, :69-70, :90-91; an empty prediction on an
+ *              empty target scores 2, 1, 1, 1 as there); the sum over the images in fp64.  accum (fp64 [5] or NULL):
+ *              accum[0..3] += the four per-image sums, accum[4] += B, in the same launch.
+ * confusion_update  conf int64 [C, C] (row = target, column = prediction) += the batch's counts.  input: logits [B, C]
+ *              (SSL4GIE_F32 / SSL4GIE_BF16; the prediction is the first maximum, a NaN counting as the largest value:
+ *              torch.argmax at Classification/train_classification.py:93,96) or predictions int64 [B]
+ *              (SSL4GIE_PRED_I64); target int64 [B].  A target or prediction outside [0, C) is never used as an index:
+ *              *rejected (int64) += 1 and the matrix is left alone.
+ * confusion_scores  scores fp32 [4] = mean F1, mean precision, mean recall (Classification/Metrics/performance.py:10-22,
+ *              :31-39, :48-56: per class tp = conf[i][i], |m1| = column sum, |m2| = row sum, every term in fp32 as the
+ *              reference forms it — a class absent from predictions and targets adds 2, 1, 1 —, added in class order in
+ *              fp32 as its loops add them, / C: the reference's means bit for bit) and accuracy = trace / total.
+ * lower_median_f32  out = the element of rank (n - 1) / 2 of x fp32 [n]: torch.median's lower median
+ *              (Depth_estimation/eval_depth.py:24).  Exact: a radix select on the bit pattern (three histogram passes,
+ *              11 + 11 + 10 bits, the bin picked on the device), so x must hold non-negative values (sign bit clear;
+ *              +inf allowed) — any other entry gives an unspecified, but safe, result.  x is not modified.  n == 0: NaN.
+ *              workspace: ssl4gie_lower_median_workspace_bytes() bytes.
+ * depth_eval   out fp32 [B, 3] = (rmse, rel_err, abs_err) per image as eval_depth.py:43-61 computes them: pred, target
+ *              fp32 [B, S, S] (Sh == Sw), target_og fp32 [B, H, W] (not modified; the reference scales it in place).
+ *              (scale, shift) = the 2 x 2 least squares of compute_scale_and_shift over target > 0, sums and solve in
+ *              fp64, det == 0 -> (0, 0); one pass over the H x W stored pixels evaluates scale * pred + shift (fp32)
+ *              resampled bilinearly (align_corners = False, no antialiasing) to M x M, M = max(H, W), cropped at
+ *              torchvision's centre-crop offsets int(round((M - H) / 2.0)), int(round((M - W) / 2.0)) (half to even),
+ *              clamped to [0, 1], zero where target_og == 0, both sides times scale_; valid = target_og * scale_ > 0;
+ *              rmse = sqrt(mean d^2), abs_err = mean |d| (fp64 sums), rel_err = lower median of |d / t| by the select
+ *              above.  An image without a valid pixel gives three NaNs.  workspace: 16-byte aligned,
+ *              ssl4gie_depth_eval_workspace_bytes(B, S, H, W) bytes (0 for an invalid shape).
+ * SSL4GIE_EARG: a null pointer, B, C or a size <= 0, an unknown dtype / kind, Sh != Sw, B > 65535 (per-image grids). */
+#define SSL4GIE_PRED_I64 2
+int ssl4gie_seg_counts(const void* logits, int logits_dtype, const void* target, int target_dtype, long long* counts,
+                       int B, int Hin, int Win, int H, int W, int sigmoid, void* stream);
+int ssl4gie_seg_scores(const long long* counts, int B, float smooth, float* scores, double* accum, void* stream);
+int ssl4gie_confusion_update(const void* input, int input_kind, const long long* target, long long* conf,
+                             long long* rejected, int B, int C, void* stream);
+int ssl4gie_confusion_scores(const long long* conf, int C, float smooth, float* scores, void* stream);
+size_t ssl4gie_lower_median_workspace_bytes(void);
+int ssl4gie_lower_median_f32(const float* x, long long n, float* out, void* workspace, void* stream);
+size_t ssl4gie_depth_eval_workspace_bytes(int B, int S, int H, int W);
+int ssl4gie_depth_eval(const float* pred, const float* target, const float* target_og, float* out, int B, int Sh,
+                       int Sw, int H, int W, float scale_, void* workspace, void* stream);
 
 /* ---------------------------------------------------------------- direct xGMI gradient all-reduce
  * replaces the NCCL bucket all-reduce of DistributedDataParallel (Models/mae/main_pretrain.py:175,

@@ -1481,3 +1481,119 @@ def paired_warp(img, matrix, flip, fill_img, tgt_bank=None, index=None, fill_tgt
                                                    ptr(tgt_out), ptr(matrix), ptr(flip), fill, float(fill_tgt), B, S,
                                                    stream()), "paired_warp")
     return img_out if tgt_out is None else (img_out, tgt_out)
+
+
+# ------------------------------------------------------------------ evaluation metrics (csrc/metric_ops.hip)
+def _same_device(*ts):
+    ts = [t for t in ts if t is not None]
+    if any(t.device != ts[0].device for t in ts):
+        raise ValueError("the metric ops need all their tensors on one device")
+
+
+def seg_counts(logits, target, sigmoid=True):
+    """int64 [B, 3] = (|m1|, |m2|, |m1 & m2|) per image, m1 = probs > 0.5 and m2 = target > 0.5: the thresholding the
+    reference's DiceScore / IoU / Precision / Recall share.  logits fp32 / bf16 [B, Hin, Win], target fp32 / uint8
+    [B, H, W]; where the sizes differ the logits are resampled bilinearly (align_corners=False) inside the kernel."""
+    _dev(logits, target)
+    _same_device(logits, target)
+    if logits.dim() != 3 or target.dim() != 3 or logits.shape[0] != target.shape[0]:
+        raise ValueError(f"seg_counts needs logits [B, Hin, Win] and target [B, H, W], got {tuple(logits.shape)}, "
+                         f"{tuple(target.shape)}")
+    if target.dtype not in (torch.uint8, torch.float32):
+        raise TypeError(f"target must be uint8 or float32, got {target.dtype}")
+    B, Hin, Win = logits.shape
+    counts = torch.empty(B, 3, dtype=torch.int64, device=logits.device)
+    _lib.check(_lib.load().ssl4gie_seg_counts(ptr(logits), code(logits.dtype), ptr(target),
+                                              _lib.TGT_U8 if target.dtype == torch.uint8 else _lib.TGT_F32, ptr(counts),
+                                              B, Hin, Win, target.shape[1], target.shape[2], int(bool(sigmoid)),
+                                              stream()), "seg_counts")
+    return counts
+
+
+def seg_scores(counts, smooth, accum=None):
+    """fp32 [4] = batch means of Dice, IoU, precision, recall from seg_counts' output; accum (fp64 [5]) += the four
+    per-image sums and the image count, in the same launch."""
+    _dev(counts, accum)
+    _same_device(counts, accum)
+    if counts.dtype != torch.int64 or counts.dim() != 2 or counts.shape[1] != 3 or counts.shape[0] < 1:
+        raise ValueError("counts must be int64 [B, 3], B >= 1")
+    if accum is not None and (accum.dtype != torch.float64 or accum.numel() != 5):
+        raise ValueError("accum must be float64 [5]")
+    scores = torch.empty(4, dtype=torch.float32, device=counts.device)
+    _lib.check(_lib.load().ssl4gie_seg_scores(ptr(counts), counts.shape[0], float(smooth), ptr(scores), ptr(accum),
+                                              stream()), "seg_scores")
+    return scores
+
+
+def confusion_update(conf, x, target):
+    """conf (int64 [C * C + 1]: the C x C matrix, row = target, column = prediction, then the rejected counter) += the
+    counts of one batch.  x: logits fp32 / bf16 [B, C] (first maximum) or predictions int64 [B]; target int64 [B]."""
+    _dev(conf, x, target)
+    _same_device(conf, x, target)
+    if conf.dtype != torch.int64 or conf.dim() != 1:
+        raise ValueError("conf must be int64 [C * C + 1]")
+    Cn = int(round((conf.numel() - 1) ** 0.5))
+    if Cn < 1 or Cn * Cn + 1 != conf.numel():
+        raise ValueError("conf must be int64 [C * C + 1]")
+    if target.dtype != torch.int64 or target.dim() != 1:
+        raise ValueError("target must be int64 [B]")
+    B = target.shape[0]
+    if x.dtype == torch.int64:
+        if tuple(x.shape) != (B,):
+            raise ValueError(f"predictions must be int64 [{B}]")
+        kind = _lib.PRED_I64
+    else:
+        if tuple(x.shape) != (B, Cn):
+            raise ValueError(f"logits must be [{B}, {Cn}], got {tuple(x.shape)}")
+        kind = code(x.dtype)
+    if B:
+        _lib.check(_lib.load().ssl4gie_confusion_update(ptr(x), kind, ptr(target), ptr(conf), conf.data_ptr() + 8 * Cn * Cn,
+                                                        B, Cn, stream()), "confusion_update")
+    return conf
+
+
+def confusion_scores(conf, smooth):
+    """fp32 [4] = mean F1, mean precision, mean recall, accuracy from confusion_update's matrix"""
+    _dev(conf)
+    Cn = int(round((conf.numel() - 1) ** 0.5))
+    if conf.dtype != torch.int64 or conf.dim() != 1 or Cn < 1 or Cn * Cn + 1 != conf.numel():
+        raise ValueError("conf must be int64 [C * C + 1]")
+    scores = torch.empty(4, dtype=torch.float32, device=conf.device)
+    _lib.check(_lib.load().ssl4gie_confusion_scores(ptr(conf), Cn, float(smooth), ptr(scores), stream()),
+               "confusion_scores")
+    return scores
+
+
+def lower_median(x):
+    """0-dim fp32: the element of rank (n - 1) // 2 of the non-negative fp32 values x (torch.median's lower median),
+    by an exact radix select; NaN for an empty x.  x is not modified."""
+    _dev(x)
+    _f32(x)
+    L = _lib.load()
+    out = torch.empty((), dtype=torch.float32, device=x.device)
+    ws = torch.empty(L.ssl4gie_lower_median_workspace_bytes(), dtype=torch.uint8, device=x.device)
+    _lib.check(L.ssl4gie_lower_median_f32(ptr(x), x.numel(), ptr(out), ptr(ws), stream()), "lower_median_f32")
+    return out
+
+
+def depth_eval(pred, target, target_og, scale_):
+    """fp32 [B, 3] = (rmse, rel_err, abs_err) per image of the depth evaluation (eval_depth.py:43-61): pred, target
+    fp32 [B, S, S], target_og fp32 [B, H, W].  An image without a valid pixel gives three NaNs."""
+    _dev(pred, target, target_og)
+    _f32(pred, target, target_og)
+    _same_device(pred, target, target_og)
+    if pred.dim() != 3 or pred.shape[1] != pred.shape[2] or pred.shape != target.shape:
+        raise ValueError(f"depth_eval needs pred and target [B, S, S], got {tuple(pred.shape)}, {tuple(target.shape)}")
+    if target_og.dim() != 3 or target_og.shape[0] != pred.shape[0]:
+        raise ValueError(f"target_og must be [B, H, W], got {tuple(target_og.shape)}")
+    B, S, _ = pred.shape
+    H, W = target_og.shape[1:]
+    L = _lib.load()
+    nb = L.ssl4gie_depth_eval_workspace_bytes(B, S, H, W)
+    if nb == 0:
+        raise ValueError(f"depth_eval: invalid shape B={B} S={S} H={H} W={W}")
+    ws = torch.empty(nb, dtype=torch.uint8, device=pred.device)
+    out = torch.empty(B, 3, dtype=torch.float32, device=pred.device)
+    _lib.check(L.ssl4gie_depth_eval(ptr(pred), ptr(target), ptr(target_og), ptr(out), B, S, S, H, W, float(scale_),
+                                    ptr(ws), stream()), "depth_eval")
+    return out
