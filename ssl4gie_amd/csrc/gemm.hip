@@ -757,11 +757,13 @@ __global__ __launch_bounds__(64 * G) void slab_reduce_wide_kernel(const float* _
     if (accumulate) s += ld4(o);
     st4(o, s);
 }
-// slab reduction of one product: the wide form from 32 slabs on when no column-sum partials ride along
+// slab reduction of one product.  `wide_ok` (the lone product): the wide form from 32 slabs on when no column-sum
+// partials ride along; it sums in another order, so the pair and the group stay on the plain kernel at every count
 static int launch_slab_reduce(const float* slabs, float* C, long long ldc, int M, int N, int splits, float alpha,
-                              int accumulate, const float* cs_part, float* cs_out, bool fused_cs, hipStream_t st) {
+                              int accumulate, const float* cs_part, float* cs_out, bool fused_cs, bool wide_ok,
+                              hipStream_t st) {
     const size_t total4 = (size_t)M * N / 4;
-    if (splits >= 32 && !fused_cs) {
+    if (wide_ok && splits >= 32 && !fused_cs) {
         if (splits >= 128)
             hipLaunchKernelGGL(slab_reduce_wide_kernel<16>, dim3((unsigned)((total4 + 63) / 64)), dim3(1024), 0, st,
                                slabs, C, ldc, M, N, splits, alpha, accumulate);
@@ -885,7 +887,7 @@ struct TnPlan {
 static TnPlan tn_plan(const ssl4gie_gemm_desc* d) {
     TnPlan p;
     p.big = ssl4gie_internal_tn256_ok(d);
-    p.splits = p.big ? ssl4gie_internal_tn256_splits(d) : tn_splits(d);
+    p.splits = p.big ? ssl4gie_internal_tn256_splits(d, 1, TN_SPLIT_LONE) : tn_splits(d);
     p.slab_bytes = p.splits > 1 ? (size_t)p.splits * d->M * d->N * sizeof(float) : 0;
     p.cs_off = al256(p.slab_bytes);
     p.cs_bytes = 0;
@@ -971,7 +973,7 @@ extern "C" int ssl4gie_gemm(const ssl4gie_gemm_desc* d, void* workspace, size_t 
         {
             ProfScope prof(PROF_GEMM_TN, 2.0 * d->M * d->N * d->K, st);
             if (p.big) {
-                const int rc = ssl4gie_internal_tn256_launch(d, slabs, cs_ws, st);
+                const int rc = ssl4gie_internal_tn256_launch(d, 1, splits, &slabs, &cs_ws, st);
                 if (rc) return rc;
             } else {
                 dim3 grid(tm * tn * splits), block(256);
@@ -985,7 +987,7 @@ extern "C" int ssl4gie_gemm(const ssl4gie_gemm_desc* d, void* workspace, size_t 
         const bool fused_cs = p.big && d->colsum_a;
         if (splits > 1) {
             const int rc = launch_slab_reduce((const float*)slabs, (float*)d->C, d->ldc, d->M, d->N, splits, d->alpha,
-                                              d->accumulate, (const float*)cs_ws, d->colsum_a, fused_cs, st);
+                                              d->accumulate, (const float*)cs_ws, d->colsum_a, fused_cs, true, st);
             if (rc) return rc;
         }
         if (d->colsum_a && !fused_cs)
@@ -1024,11 +1026,62 @@ extern "C" int ssl4gie_gemm(const ssl4gie_gemm_desc* d, void* workspace, size_t 
 
 
 // ---------------------------------------------------------------------------------------------
-// Two weight-gradient (TN) products with the same contraction length in ONE launch.  A split-K TN
-// product alone spreads over ~one workgroup per CU, each writing a full 256 x 256 fp32 slab (64 MiB
-// per product whatever its shape); two products sharing the grid need half the splits each, hence
-// half the slab traffic and reduction work.  Falls back to two ssl4gie_gemm calls when the pair does
-// not qualify (shape rules of the 256x256 TN kernel, equal K, no implicit-conv operand).
+// Several weight-gradient (TN) products with the same contraction length in ONE launch (ssl4gie_gemm_tn_pair,
+// ssl4gie_gemm_tn_group).  A split-K TN product alone spreads over ~one workgroup per CU, each writing a full
+// 256 x 256 fp32 slab (64 MiB per product whatever its shape); products sharing the grid need fewer splits each,
+// hence less slab traffic and reduction work, and none at all once their tiles fill the chip.  The entry points
+// keep their eligibility rule and split policy and fall back to one ssl4gie_gemm call per product.
+// Workspace: [slabs 0 .. n-1] [column-sum partials of the products with colsum_a], each rounded to 256 B; nothing
+// when splits == 1.
+struct TnManyPlan {
+    size_t slab_off[TN_GROUP_MAX], cs_off[TN_GROUP_MAX], total;
+};
+static TnManyPlan tn_many_plan(const ssl4gie_gemm_desc* ds, int n, int splits) {
+    TnManyPlan p;
+    size_t o = 0;
+    for (int i = 0; i < n; ++i) {
+        p.slab_off[i] = o;
+        if (splits > 1) o += al256((size_t)splits * ds[i].M * ds[i].N * sizeof(float));
+    }
+    for (int i = 0; i < n; ++i) {
+        p.cs_off[i] = o;
+        if (splits > 1 && ds[i].colsum_a) o += al256((size_t)splits * ds[i].M * sizeof(float));
+    }
+    p.total = o;
+    return p;
+}
+static int tn_many_run(const ssl4gie_gemm_desc* ds, int n, int splits, void* workspace, size_t workspace_bytes,
+                       hipStream_t st) {
+    for (int i = 0; i < n; ++i) {
+        REQUIRE(ds[i].A && ds[i].B && ds[i].C);
+        REQUIRE(!ds[i].colsum_a || ds[i].sAk >= ds[i].M);
+    }
+    const TnManyPlan p = tn_many_plan(ds, n, splits);
+    REQUIRE(p.total == 0 || (workspace && workspace_bytes >= p.total));
+    char* ws = (char*)workspace;
+    float* slabs[TN_GROUP_MAX];
+    float* cs[TN_GROUP_MAX];
+    double flops = 0;
+    for (int i = 0; i < n; ++i) {
+        slabs[i] = splits > 1 ? (float*)(ws + p.slab_off[i]) : nullptr;
+        cs[i] = (splits > 1 && ds[i].colsum_a) ? (float*)(ws + p.cs_off[i]) : nullptr;
+        flops += 2.0 * ds[i].K * (double)ds[i].M * ds[i].N;
+    }
+    {
+        ProfScope prof(PROF_GEMM_TN, flops, st);
+        const int rc = ssl4gie_internal_tn256_launch(ds, n, splits, slabs, cs, st);
+        if (rc) return rc;
+    }
+    for (int i = 0; splits > 1 && i < n; ++i) {
+        const ssl4gie_gemm_desc* d = &ds[i];
+        const int rc = launch_slab_reduce(slabs[i], (float*)d->C, d->ldc, d->M, d->N, splits, d->alpha, d->accumulate,
+                                          cs[i], d->colsum_a, d->colsum_a != nullptr, false, st);
+        if (rc) return rc;
+    }
+    return 0;
+}
+
+// ---- two products (ssl4gie_gemm_tn_pair): equal accumulate and alpha == 1 on both
 static bool tn_pair_ok(const ssl4gie_gemm_desc* a, const ssl4gie_gemm_desc* b) {
     static int enabled = -1;  // SSL4GIE_TN_PAIR=0: always two launches (A/B measurements)
     if (enabled < 0) {
@@ -1040,28 +1093,13 @@ static bool tn_pair_ok(const ssl4gie_gemm_desc* a, const ssl4gie_gemm_desc* b) {
            a->accumulate == b->accumulate && a->alpha == 1.f && b->alpha == 1.f &&
            a->N % 4 == 0 && b->N % 4 == 0;
 }
-struct PairPlan {
-    int splits;
-    size_t slab_a, slab_b, cs_a, cs_b, off_b, off_csa, off_csb, total;
-};
-static PairPlan pair_plan(const ssl4gie_gemm_desc* a, const ssl4gie_gemm_desc* b) {
-    PairPlan p;
-    p.splits = ssl4gie_internal_tn256_pair_splits(a, b);
-    const bool sp = p.splits > 1;
-    p.slab_a = sp ? al256((size_t)p.splits * a->M * a->N * sizeof(float)) : 0;
-    p.slab_b = sp ? al256((size_t)p.splits * b->M * b->N * sizeof(float)) : 0;
-    p.cs_a = (sp && a->colsum_a) ? al256((size_t)p.splits * a->M * sizeof(float)) : 0;
-    p.cs_b = (sp && b->colsum_a) ? al256((size_t)p.splits * b->M * sizeof(float)) : 0;
-    p.off_b = p.slab_a;
-    p.off_csa = p.off_b + p.slab_b;
-    p.off_csb = p.off_csa + p.cs_a;
-    p.total = p.off_csb + p.cs_b;
-    return p;
-}
 extern "C" size_t ssl4gie_gemm_tn_pair_workspace_bytes(const ssl4gie_gemm_desc* a,
                                                        const ssl4gie_gemm_desc* b) {
     if (!a || !b) return 0;
-    if (tn_pair_ok(a, b)) return pair_plan(a, b).total;
+    if (tn_pair_ok(a, b)) {
+        const ssl4gie_gemm_desc ds[2] = {*a, *b};
+        return tn_many_plan(ds, 2, ssl4gie_internal_tn256_splits(ds, 2, TN_SPLIT_PAIR)).total;
+    }
     const size_t wa = ssl4gie_gemm_workspace_bytes(a), wb = ssl4gie_gemm_workspace_bytes(b);
     return wa > wb ? wa : wb;
 }
@@ -1073,41 +1111,12 @@ extern "C" int ssl4gie_gemm_tn_pair(const ssl4gie_gemm_desc* a, const ssl4gie_ge
         if (rc) return rc;
         return ssl4gie_gemm(b, workspace, workspace_bytes, stream);
     }
-    REQUIRE(a->A && a->B && a->C && b->A && b->B && b->C);
-    REQUIRE(!a->colsum_a || a->sAk >= a->M);
-    REQUIRE(!b->colsum_a || b->sAk >= b->M);
-    hipStream_t st = (hipStream_t)stream;
-    const PairPlan p = pair_plan(a, b);
-    REQUIRE(p.total == 0 || (workspace && workspace_bytes >= p.total));
-    char* ws = (char*)workspace;
-    float* slabs_a = (float*)ws;
-    float* slabs_b = (float*)(ws + p.off_b);
-    float* cs_a = p.cs_a ? (float*)(ws + p.off_csa) : nullptr;
-    float* cs_b = p.cs_b ? (float*)(ws + p.off_csb) : nullptr;
-    {
-        ProfScope prof(PROF_GEMM_TN, 2.0 * a->K * ((double)a->M * a->N + (double)b->M * b->N), st);
-        const int rc = ssl4gie_internal_tn256_launch_pair(a, b, p.splits, slabs_a, cs_a, slabs_b, cs_b, st);
-        if (rc) return rc;
-    }
-    if (p.splits > 1) {
-        const ssl4gie_gemm_desc* ds[2] = {a, b};
-        float* sl[2] = {slabs_a, slabs_b};
-        float* cs[2] = {cs_a, cs_b};
-        for (int i = 0; i < 2; ++i) {
-            const ssl4gie_gemm_desc* d = ds[i];
-            const size_t total4 = (size_t)d->M * d->N / 4;
-            const unsigned c_blocks = (unsigned)((total4 + 255) / 256);
-            const unsigned b_blocks = d->colsum_a ? (unsigned)((d->M + 255) / 256) : 0;
-            hipLaunchKernelGGL(slab_reduce_kernel, dim3(c_blocks + b_blocks), dim3(256), 0, st,
-                               (const float*)sl[i], (float*)d->C, d->ldc, d->M, d->N, p.splits, d->alpha,
-                               d->accumulate, (const float*)cs[i], d->colsum_a, c_blocks);
-            LAUNCH_CHECK();
-        }
-    }
-    return 0;
+    const ssl4gie_gemm_desc ds[2] = {*a, *b};
+    return tn_many_run(ds, 2, ssl4gie_internal_tn256_splits(ds, 2, TN_SPLIT_PAIR), workspace, workspace_bytes,
+                       (hipStream_t)stream);
 }
 
-// ---- grouped weight-gradient products (ssl4gie_gemm_tn_group)
+// ---- 1 .. TN_GROUP_MAX products (ssl4gie_gemm_tn_group)
 static bool tn_group_ok(const ssl4gie_gemm_desc* ds, int n) {
     if (!ds || n < 1 || n > TN_GROUP_MAX) return false;
     for (int i = 0; i < n; ++i) {
@@ -1118,28 +1127,10 @@ static bool tn_group_ok(const ssl4gie_gemm_desc* ds, int n) {
     }
     return true;
 }
-struct GroupPlan {
-    int splits;
-    size_t slab_off[TN_GROUP_MAX], cs_off[TN_GROUP_MAX], total;
-};
-static GroupPlan group_plan(const ssl4gie_gemm_desc* ds, int n) {
-    GroupPlan p;
-    p.splits = ssl4gie_internal_tn256_group_splits(ds, n);
-    size_t o = 0;
-    for (int i = 0; i < n; ++i) {
-        p.slab_off[i] = o;
-        if (p.splits > 1) o += al256((size_t)p.splits * ds[i].M * ds[i].N * sizeof(float));
-    }
-    for (int i = 0; i < n; ++i) {
-        p.cs_off[i] = o;
-        if (p.splits > 1 && ds[i].colsum_a) o += al256((size_t)p.splits * ds[i].M * sizeof(float));
-    }
-    p.total = o;
-    return p;
-}
 extern "C" size_t ssl4gie_gemm_tn_group_workspace_bytes(const ssl4gie_gemm_desc* descs, int n) {
     if (!descs || n < 1) return 0;
-    if (tn_group_ok(descs, n)) return group_plan(descs, n).total;
+    if (tn_group_ok(descs, n))
+        return tn_many_plan(descs, n, ssl4gie_internal_tn256_splits(descs, n, TN_SPLIT_GROUP)).total;
     size_t m = 0;
     for (int i = 0; i < n; ++i) {
         const size_t w = ssl4gie_gemm_workspace_bytes(&descs[i]);
@@ -1157,38 +1148,6 @@ extern "C" int ssl4gie_gemm_tn_group(const ssl4gie_gemm_desc* descs, int n, void
         }
         return 0;
     }
-    for (int i = 0; i < n; ++i) {
-        REQUIRE(descs[i].A && descs[i].B && descs[i].C);
-        REQUIRE(!descs[i].colsum_a || descs[i].sAk >= descs[i].M);
-    }
-    hipStream_t st = (hipStream_t)stream;
-    const GroupPlan p = group_plan(descs, n);
-    REQUIRE(p.total == 0 || (workspace && workspace_bytes >= p.total));
-    char* ws = (char*)workspace;
-    float* slabs[TN_GROUP_MAX];
-    float* cs[TN_GROUP_MAX];
-    double flops = 0;
-    for (int i = 0; i < n; ++i) {
-        slabs[i] = p.splits > 1 ? (float*)(ws + p.slab_off[i]) : nullptr;
-        cs[i] = (p.splits > 1 && descs[i].colsum_a) ? (float*)(ws + p.cs_off[i]) : nullptr;
-        flops += 2.0 * descs[i].K * (double)descs[i].M * descs[i].N;
-    }
-    {
-        ProfScope prof(PROF_GEMM_TN, flops, st);
-        const int rc = ssl4gie_internal_tn256_launch_group(descs, n, p.splits, slabs, cs, st);
-        if (rc) return rc;
-    }
-    if (p.splits > 1) {
-        for (int i = 0; i < n; ++i) {
-            const ssl4gie_gemm_desc* d = &descs[i];
-            const size_t total4 = (size_t)d->M * d->N / 4;
-            const unsigned c_blocks = (unsigned)((total4 + 255) / 256);
-            const unsigned b_blocks = d->colsum_a ? (unsigned)((d->M + 255) / 256) : 0;
-            hipLaunchKernelGGL(slab_reduce_kernel, dim3(c_blocks + b_blocks), dim3(256), 0, st,
-                               (const float*)slabs[i], (float*)d->C, d->ldc, d->M, d->N, p.splits, d->alpha,
-                               d->accumulate, (const float*)cs[i], d->colsum_a, c_blocks);
-            LAUNCH_CHECK();
-        }
-    }
-    return 0;
+    return tn_many_run(descs, n, ssl4gie_internal_tn256_splits(descs, n, TN_SPLIT_GROUP), workspace, workspace_bytes,
+                       (hipStream_t)stream);
 }

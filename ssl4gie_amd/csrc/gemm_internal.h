@@ -50,10 +50,6 @@ int ssl4gie_internal_nt256_launch(const ssl4gie_gemm_desc* d, hipStream_t st);
 
 // 256x256x64 ping-pong TN kernel (gemm_tn256.hip): weight-gradient product with split-K slabs.
 bool ssl4gie_internal_tn256_ok(const ssl4gie_gemm_desc* d);
-int ssl4gie_internal_tn256_splits(const ssl4gie_gemm_desc* d);
-// `slabs` (splits > 1) and `colsum_part` ([splits][M], splits > 1 and d->colsum_a) are workspace
-int ssl4gie_internal_tn256_launch(const ssl4gie_gemm_desc* d, float* slabs, float* colsum_part,
-                                  hipStream_t st);
 // Further problems of a grouped launch (TN products with the same contraction length K share one
 // grid: with enough output tiles in the group no split-K slabs are needed at all).  Problem 0 is
 // passed as plain kernel arguments, problems 1..n as this table; `tile0` is the first tile of the
@@ -73,11 +69,10 @@ struct TnExtras {
     int m_inner;  // walk the shorter tile dimension innermost (gemm_tn256.hip)
     TnSecond p[TN_GROUP_MAX - 1];
 };
-int ssl4gie_internal_tn256_group_splits(const ssl4gie_gemm_desc* descs, int n);
-// slabs[i] / cs[i]: split-K workspace of problem i (splits > 1), cs[i] only if it has colsum_a
-int ssl4gie_internal_tn256_launch_group(const ssl4gie_gemm_desc* descs, int n, int splits,
-                                        float* const* slabs, float* const* cs, hipStream_t st);
-int ssl4gie_internal_tn256_pair_splits(const ssl4gie_gemm_desc* a, const ssl4gie_gemm_desc* b);
-int ssl4gie_internal_tn256_launch_pair(const ssl4gie_gemm_desc* a, const ssl4gie_gemm_desc* b,
-                                       int splits, float* slabs_a, float* cs_a, float* slabs_b,
-                                       float* cs_b, hipStream_t st);
+// Split-K count of one launch of n products (same K) under the lone product's, the pair's or the group's policy
+enum TnSplitPolicy { TN_SPLIT_LONE, TN_SPLIT_PAIR, TN_SPLIT_GROUP };
+int ssl4gie_internal_tn256_splits(const ssl4gie_gemm_desc* descs, int n, TnSplitPolicy policy);
+// One launch for descs[0..n): `splits` is the caller's plan; slabs[i] / cs[i]: split-K workspace of problem i
+// (splits > 1), cs[i] ([splits][M]) only if it has colsum_a
+int ssl4gie_internal_tn256_launch(const ssl4gie_gemm_desc* descs, int n, int splits, float* const* slabs,
+                                  float* const* cs, hipStream_t st);

@@ -606,79 +606,47 @@ bool ssl4gie_internal_tn256_ok(const ssl4gie_gemm_desc* d) {
     return d->K >= 16 * P_BK && (long long)d->M * d->N >= 128 * 128 * 4;
 }
 
-int ssl4gie_internal_tn256_splits(const ssl4gie_gemm_desc* d) {
-    const int tiles = ((d->M + P_BM - 1) / P_BM) * ((d->N + P_BN - 1) / P_BN);
-    const int nkt = d->K / P_BK;
-    // SSL4GIE_TN_FILL1 (percent, default 75): share of the CUs a lone product aims to fill.  These launches run
-    // beside the data-gradient chain on a weight-gradient stream, like the pairs (whose fill is 75 % too): MoCo-R50
-    // step 55.5 / 55.7 -> 54.9 / 55.0 ms in a same-box A/B (profiles/r04cy_tn_fill1.log), depth and MAE unchanged
-    static int fill1 = -1;
-    if (fill1 < 0) { const char* e = getenv("SSL4GIE_TN_FILL1"); fill1 = e ? atoi(e) : 75; if (fill1 < 10) fill1 = 10; }
-    int s = (ssl4gie_internal_compute_cus() * fill1 / 100 + tiles / 2) / tiles;  // one workgroup per CU
-    if (s > nkt / 8) s = nkt / 8;       // at least 8 K-tiles per split
-    if (s < 1) s = 1;
-    if (s > 256) s = 256;               // (a single-tile product over a long contraction: one split per CU)
-    return s;
-}
-
-int ssl4gie_internal_tn256_pair_splits(const ssl4gie_gemm_desc* a, const ssl4gie_gemm_desc* b) {
-    const int tiles = ((a->M + P_BM - 1) / P_BM) * ((a->N + P_BN - 1) / P_BN) +
-                      ((b->M + P_BM - 1) / P_BM) * ((b->N + P_BN - 1) / P_BN);
-    const int nkt = a->K / P_BK;
-    // SSL4GIE_TN_FILL (percent, default 75): share of the CUs a paired launch aims to fill — on the
-    // weight-gradient side stream fewer, longer workgroups mean less slab traffic (measured:
-    // profiles/r01w_ab_grid_sizing.log)
-    static int fill = -1;
-    if (fill < 0) {
-        const char* e = getenv("SSL4GIE_TN_FILL");
-        fill = e ? atoi(e) : 75;
-        if (fill < 10) fill = 10;
-        if (fill > 200) fill = 200;
-    }
-    const int target = ssl4gie_internal_compute_cus() * fill / 100;
-    int s = (target + tiles / 2) / tiles;
-    if (s > nkt / 8) s = nkt / 8;
-    if (s < 1) s = 1;
-    if (s > 64) s = 64;
-    return s;
-}
-
-int ssl4gie_internal_tn256_group_splits(const ssl4gie_gemm_desc* descs, int n) {
+// Split-K count of one launch of n products with the same K.  The lone product, the pair and the group share the
+// arithmetic; they differ in the share of the CUs they aim to fill, the cap and the group's whole-K rule.
+int ssl4gie_internal_tn256_splits(const ssl4gie_gemm_desc* descs, int n, TnSplitPolicy policy) {
     int tiles = 0;
     for (int i = 0; i < n; ++i)
         tiles += ((descs[i].M + P_BM - 1) / P_BM) * ((descs[i].N + P_BN - 1) / P_BN);
     const int nkt = descs[0].K / P_BK;
     const int cus = ssl4gie_internal_compute_cus();
-    if (tiles * 10 >= cus * 7) return 1;  // >= 70 % of the CUs busy with whole-K tiles: no slabs at all
-    int s = (cus + tiles / 2) / tiles;
-    if (s > nkt / 8) s = nkt / 8;
+    int fill = 100, cap = 64;
+    if (policy == TN_SPLIT_LONE) {
+        // SSL4GIE_TN_FILL1 (percent, default 75): share of the CUs a lone product aims to fill.  These launches run
+        // beside the data-gradient chain on a weight-gradient stream, like the pairs (whose fill is 75 % too): MoCo-R50
+        // step 55.5 / 55.7 -> 54.9 / 55.0 ms in a same-box A/B (profiles/r04cy_tn_fill1.log), depth and MAE unchanged
+        static int fill1 = -1;
+        if (fill1 < 0) { const char* e = getenv("SSL4GIE_TN_FILL1"); fill1 = e ? atoi(e) : 75; if (fill1 < 10) fill1 = 10; }
+        fill = fill1;
+        cap = 256;  // (a single-tile product over a long contraction: one split per CU)
+    } else if (policy == TN_SPLIT_PAIR) {
+        // SSL4GIE_TN_FILL (percent, default 75): share of the CUs a paired launch aims to fill — on the
+        // weight-gradient side stream fewer, longer workgroups mean less slab traffic (measured:
+        // profiles/r01w_ab_grid_sizing.log)
+        static int fill2 = -1;
+        if (fill2 < 0) {
+            const char* e = getenv("SSL4GIE_TN_FILL");
+            fill2 = e ? atoi(e) : 75;
+            if (fill2 < 10) fill2 = 10;
+            if (fill2 > 200) fill2 = 200;
+        }
+        fill = fill2;
+    } else if (tiles * 10 >= cus * 7) {
+        return 1;  // group: >= 70 % of the CUs busy with whole-K tiles: no slabs at all
+    }
+    int s = (cus * fill / 100 + tiles / 2) / tiles;  // one workgroup per CU
+    if (s > nkt / 8) s = nkt / 8;                    // at least 8 K-tiles per split
     if (s < 1) s = 1;
-    if (s > 64) s = 64;
+    if (s > cap) s = cap;
     return s;
 }
 
-static int tn256_launch_impl(const ssl4gie_gemm_desc* descs, int n, int splits, float* const* slabs,
-                             float* const* cs, hipStream_t st);
-
-int ssl4gie_internal_tn256_launch(const ssl4gie_gemm_desc* d, float* slabs, float* colsum_part,
-                                  hipStream_t st) {
-    return tn256_launch_impl(d, 1, ssl4gie_internal_tn256_splits(d), &slabs, &colsum_part, st);
-}
-int ssl4gie_internal_tn256_launch_pair(const ssl4gie_gemm_desc* a, const ssl4gie_gemm_desc* b,
-                                       int splits, float* slabs_a, float* cs_a, float* slabs_b,
-                                       float* cs_b, hipStream_t st) {
-    const ssl4gie_gemm_desc ds[2] = {*a, *b};
-    float* sl[2] = {slabs_a, slabs_b};
-    float* cp[2] = {cs_a, cs_b};
-    return tn256_launch_impl(ds, 2, splits, sl, cp, st);
-}
-int ssl4gie_internal_tn256_launch_group(const ssl4gie_gemm_desc* descs, int n, int splits,
-                                        float* const* slabs, float* const* cs, hipStream_t st) {
-    return tn256_launch_impl(descs, n, splits, slabs, cs, st);
-}
-
-static int tn256_launch_impl(const ssl4gie_gemm_desc* descs, int n, int splits, float* const* slabs_v,
-                             float* const* cs_v, hipStream_t st) {
+int ssl4gie_internal_tn256_launch(const ssl4gie_gemm_desc* descs, int n, int splits, float* const* slabs_v,
+                                  float* const* cs_v, hipStream_t st) {
     if (n < 1 || n > TN_GROUP_MAX) return ARG_ERR;
     const ssl4gie_gemm_desc* d = &descs[0];
     float* slabs = slabs_v[0];

@@ -255,6 +255,20 @@ def linear_bwd_data(dy2d, w, w_t=None, out_dtype=None, dgelu_aux=None, mul_aux=N
     return dx
 
 
+def _wgrad_desc(dy, x, out, bias_out, accumulate):
+    """descriptor of out[n_out, k_in] (+)= dy[T, n_out]^T @ x[T, k_in] (fp32), bias_out[n_out] = column sums of dy"""
+    (T, n_out), k_in = dy.shape, x.shape[1]
+    d = _desc(n_out, k_in, T, code(dy.dtype), F32)
+    d.A, d.sAm, d.sAk = ptr(dy), 1, n_out
+    d.B, d.sBk, d.sBn = ptr(x), k_in, 1
+    d.C, d.ldc = ptr(out), k_in
+    d.accumulate = int(accumulate)
+    if bias_out is not None:
+        assert bias_out.dtype == torch.float32 and bias_out.numel() == n_out
+        d.colsum_a = ptr(bias_out)
+    return d
+
+
 def linear_bwd_weight(dy2d, x2d, out=None, accumulate=False, bias_out=None):
     """dW[n_out, k_in] = dy[T, n_out]^T @ x[T, k_in]  (fp32 output); with `bias_out` [n_out] the
     bias gradient (column sums of dy) is produced by the same call."""
@@ -265,15 +279,7 @@ def linear_bwd_weight(dy2d, x2d, out=None, accumulate=False, bias_out=None):
     if out is None:
         out = torch.empty(n_out, k_in, dtype=torch.float32, device=x2d.device)
     assert out.dtype == torch.float32 and out.numel() == n_out * k_in
-    d = _desc(n_out, k_in, T, code(dy2d.dtype), F32)
-    d.A, d.sAm, d.sAk = ptr(dy2d), 1, n_out
-    d.B, d.sBk, d.sBn = ptr(x2d), k_in, 1
-    d.C, d.ldc = ptr(out), k_in
-    d.accumulate = int(accumulate)
-    if bias_out is not None:
-        assert bias_out.dtype == torch.float32 and bias_out.numel() == n_out
-        d.colsum_a = ptr(bias_out)
-    gemm_raw(d, x2d.device)
+    gemm_raw(_wgrad_desc(dy2d, x2d, out, bias_out, accumulate), x2d.device)
     return out
 
 
@@ -285,17 +291,8 @@ def linear_bwd_weight_pair(dy_a, x_a, dy_b, x_b, bias_a=None, bias_b=None):
     assert dy_b.shape[0] == T and x_a.shape[0] == T and x_b.shape[0] == T
     outs, descs = [], []
     for dy, x, b in ((dy_a, x_a, bias_a), (dy_b, x_b, bias_b)):
-        n_out, k_in = dy.shape[1], x.shape[1]
-        out = torch.empty(n_out, k_in, dtype=torch.float32, device=x.device)
-        d = _desc(n_out, k_in, T, code(dy.dtype), F32)
-        d.A, d.sAm, d.sAk = ptr(dy), 1, n_out
-        d.B, d.sBk, d.sBn = ptr(x), k_in, 1
-        d.C, d.ldc = ptr(out), k_in
-        if b is not None:
-            assert b.dtype == torch.float32 and b.numel() == n_out
-            d.colsum_a = ptr(b)
-        outs.append(out)
-        descs.append(d)
+        outs.append(torch.empty(dy.shape[1], x.shape[1], dtype=torch.float32, device=x.device))
+        descs.append(_wgrad_desc(dy, x, outs[-1], b, False))
     L = _lib.load()
     nbytes = L.ssl4gie_gemm_tn_pair_workspace_bytes(C.byref(descs[0]), C.byref(descs[1]))
     ws = torch.empty(nbytes, dtype=torch.uint8, device=dy_a.device) if nbytes else None
@@ -321,16 +318,7 @@ def linear_bwd_weight_group(pairs, accumulate_into=None):
             assert out.shape == (n_out, k_in) and out.dtype == torch.float32
         else:
             out = torch.empty(n_out, k_in, dtype=torch.float32, device=x.device)
-        d = descs[i]
-        d.M, d.N, d.K, d.batch1, d.batch2 = n_out, k_in, T, 1, 1
-        d.dtype_ab, d.dtype_c, d.alpha, d.epilogue = code(dy.dtype), F32, 1.0, _lib.EPI_NONE
-        d.A, d.sAm, d.sAk = ptr(dy), 1, n_out
-        d.B, d.sBk, d.sBn = ptr(x), k_in, 1
-        d.C, d.ldc = ptr(out), k_in
-        d.accumulate = 1 if accumulate_into is not None else 0
-        if b is not None:
-            assert b.dtype == torch.float32 and b.numel() == n_out
-            d.colsum_a = ptr(b)
+        descs[i] = _wgrad_desc(dy, x, out, b, accumulate_into is not None)
         outs.append(out)
     L = _lib.load()
     nbytes = L.ssl4gie_gemm_tn_group_workspace_bytes(descs, n)

@@ -551,7 +551,8 @@ def approx_terms(form, u, out_dtype):
 # ------------------------------------------------------------------ routing (labels; splits and GELU form)
 def route(s, cus=None):
     """the dispatch of ssl4gie_gemm for spec `s` in the default environment, as read from gemm.hip (nt_ok, tn_ok,
-    tn_splits, launch_slab_reduce), gemm_nt256.hip (nt256_ok, nt256_pick_nj, the launch) and gemm_tn256.hip"""
+    tn_splits, launch_slab_reduce), gemm_nt256.hip (nt256_ok, nt256_pick_nj, the launch) and gemm_tn256.hip
+    (tn256_ok, ssl4gie_internal_tn256_splits with TN_SPLIT_LONE)"""
     cus = cus or s["cus"]
     M, N, Kd, epi = s["M"], s["N"], s["K"], s["epi"]
     r = {"kind": "generic", "splits": 1, "gelu": "erf"}
@@ -608,6 +609,19 @@ def route(s, cus=None):
                  reduce="none" if sp == 1 else ("plain" if sp < 32 else "wide4" if sp < 128 else "wide16"))
         return r
     return r
+
+
+def many_splits(cases, cus, entry):
+    """the split count of one launch of several TN products with the same K (entry "pair": ssl4gie_gemm_tn_pair,
+    "group": ssl4gie_gemm_tn_group) in the default environment, as read from gemm_tn256.hip
+    (ssl4gie_internal_tn256_splits: TN_SPLIT_PAIR aims at 75 % of the CUs, TN_SPLIT_GROUP at all of them and takes
+    whole-K tiles once they cover 70 % of the CUs; both keep 8 K-tiles per split and stop at 64)"""
+    specs = [c["spec"] for c in cases]
+    tiles = sum(-(-s["M"] // 256) * -(-s["N"] // 256) for s in specs)
+    if entry == "group" and tiles * 10 >= cus * 7:
+        return 1
+    fill = 75 if entry == "pair" else 100
+    return max(1, min((cus * fill // 100 + tiles // 2) // tiles, specs[0]["K"] // 64 // 8, 64))
 
 
 def route_label(r):

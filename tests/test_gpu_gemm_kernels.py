@@ -220,15 +220,16 @@ def tn(M, N, Kd, fam, alpha=1.0, acc=False, colsum=False, seed=0):
     return gc.make_case(spec(M, N, Kd, "tn", BF, F32, NONE, alpha, acc=acc, colsum=colsum, family=fam, seed=seed))
 
 
-def pair_splits(cases, cus, cap=64, fill=75):
-    tiles = sum(-(-c["spec"]["M"] // 256) * -(-c["spec"]["N"] // 256) for c in cases)
-    return max(1, min((cus * fill // 100 + tiles // 2) // tiles, cases[0]["spec"]["K"] // 64 // 8, cap))
+def deep_two(family):
+    """two one-tile products over K = 16384: 32 splits at 240 CUs in the pair and in the group, the count from which a
+    lone product without column sums takes the wide reduction; the second product carries colsum_a"""
+    return [tn(256, 256, 16384, family, seed=11), tn(256, 256, 16384, family, colsum=True, seed=12)]
 
 
 @pytest.mark.parametrize("family", ["gauss", "integers", "cancel"])
 def test_tn_pair(family):
     """ragged products of one launch (alpha = 1: the pair's rule), with and without the fused column sums and
-    accumulate; at 8 CUs the split count changes"""
+    accumulate; at 8 CUs the split count changes; two one-tile products over K = 16384: 32 slabs each"""
     rep = gc.Report()
     shapes = ((264, 264), (72, 1032), (520, 136))      # each M N >= 65536: the 256 x 256 kernel's own rule
     for cus in (240, 8):
@@ -237,14 +238,19 @@ def test_tn_pair(family):
             acc = i == 1
             cases = [tn(m0, n0, 1024, family, acc=acc, colsum=i != 2, seed=i), tn(m1, n1, 1024, family, acc=acc, colsum=i == 0, seed=i + 5)]
             outs, _ = launch_many(cases, "pair", cus)
-            judge_many(cases, outs, pair_splits(cases, cus), rep, "pair cus %d" % cus)
+            judge_many(cases, outs, gc.many_splits(cases, cus, "pair"), rep, "pair cus %d" % cus)
+    cases = deep_two(family)
+    assert gc.many_splits(cases, 240, "pair") == 32
+    outs, _ = launch_many(cases, "pair", 240)
+    judge_many(cases, outs, 32, rep, "pair deep")
     done(rep)
 
 
 @pytest.mark.parametrize("family", ["gauss", "integers", "cancel"])
 def test_tn_group(family):
     """three two-tile products at 8 CUs: six whole-K tiles, no slabs (the workspace query says 0 bytes), with alpha,
-    accumulate and colsum_a per product; the same group at 240 CUs splits K; one product alone"""
+    accumulate and colsum_a per product; the same group at 240 CUs splits K; one product alone; two one-tile products
+    over K = 16384: 32 slabs each"""
     rep = gc.Report()
     mk = lambda: [tn(512, 256, 1024, family, 0.5, True, True, 1), tn(256, 264, 1024, family, -2.0, False, True, 2),
                   tn(264, 256, 1024, family, 1.0, True, False, 3)]
@@ -255,10 +261,17 @@ def test_tn_group(family):
     cases = mk()
     outs, nb = launch_many(cases, "group", 240)
     assert nb > 0
-    judge_many(cases, outs, max(1, min((240 + 3) // 6, 1024 // 64 // 8, 64)), rep, "group split")
+    assert gc.many_splits(cases, 240, "group") == max(1, min((240 + 3) // 6, 1024 // 64 // 8, 64))
+    judge_many(cases, outs, gc.many_splits(cases, 240, "group"), rep, "group split")
     cases = mk()[:1]
     outs, nb = launch_many(cases, "group", 64)
-    judge_many(cases, outs, max(1, min((64 + 1) // 2, 2, 64)), rep, "group of one")
+    assert gc.many_splits(cases, 64, "group") == max(1, min((64 + 1) // 2, 2, 64))
+    judge_many(cases, outs, gc.many_splits(cases, 64, "group"), rep, "group of one")
+    cases = deep_two(family)
+    assert gc.many_splits(cases, 240, "group") == 32
+    outs, nb = launch_many(cases, "group", 240)
+    assert nb == 2 * 32 * 256 * 256 * 4 + 32 * 256 * 4, nb
+    judge_many(cases, outs, 32, rep, "group deep")
     done(rep)
 
 
