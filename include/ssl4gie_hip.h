@@ -17,7 +17,7 @@
  *   - ssl4gie_abi_version() = 12 (ssl4gie_view_sample_u8, after it ssl4gie_color_augment{_workspace_bytes,}, and after those ssl4gie_color_augment_ft / ssl4gie_paired_warp, joined revision 12
  *     without a new number: added symbols, nothing existing changed, so a caller built against the earlier 12 runs unchanged; the evaluation
  *     metrics ssl4gie_seg_{counts,scores} / ssl4gie_confusion_{update,scores} / ssl4gie_lower_median_{workspace_bytes,f32} / ssl4gie_depth_eval{_workspace_bytes,}
- *     joined it the same way; 11: before the sixteen BatchNorm entry points that had grown one per fusion (ssl4gie_bn_fwd / _fwd_partials / _fwd_partials_bits /
+ *     joined it the same way, and so did the detection input entry points ssl4gie_det_color{_workspace_bytes,} / ssl4gie_det_geometry / ssl4gie_det_boxes; 11: before the sixteen BatchNorm entry points that had grown one per fusion (ssl4gie_bn_fwd / _fwd_partials / _fwd_partials_bits /
  *     _coef_partials / _coef_stats / _apply_bits, _stats / _stats_partials, _bwd / _bwd_xmask / _bwd_bits, _bwd_reduce / _reduce_xmask / _reduce_bits,
  *     _bwd_apply / _apply_xmask) were REPLACED by five with a source and a mask kind — the same launches, new signatures; 10: before the diagnostics entry point that read the 256x256 NT kernel's in-kernel
  *     time stamps was REMOVED with the debug build of the library — the one removal in this history; 9: before ssl4gie_infonce_{workspace_bytes,loss} / ssl4gie_cross_entropy{_workspace_bytes,} /
@@ -731,6 +731,58 @@ int ssl4gie_color_augment_ft(const float* x, float* out, int B, int S, const flo
 int ssl4gie_paired_warp(const float* img, float* img_out, const void* tgt_bank, int tgt_dtype, long n,
                         const int64_t* index, float* tgt_out, const float* matrix, const uint8_t* flip,
                         const float fill_img[3], float fill_tgt, int B, int S, void* stream);
+/* The detection loaders (Object_detection/Data/dataloaders.py:75-112 and Data/dataset.py:38-113 with arch != "resnet50",
+ * post_process = False) over a RAGGED uint8 bank on the device: image i is the dense HWC bytes at pixels + offsets[i]
+ * (pixels [total], offsets int64 [n]), sizes[i] = (H0, W0) (int32 [n, 2]); sample b of a batch is image index[b]
+ * (int64 [B]).  All of these are DEVICE arrays and are checked by the kernels: a sample whose index is outside [0, n),
+ * whose side is below 13 or above 32768, whose bytes do not lie inside [0, total), whose H0 W0 exceeds plane_stride
+ * (where a scratch is involved) or whose image does not fit F x F after step 6 comes out all NaN (its boxes too), and
+ * no address is formed from such a value.  These entry points joined revision 12.
+ *
+ * ssl4gie_det_color: dataloaders.py:77-80, ColorJitter -> GaussianBlur((25, 25), sigma) on the stored H0 x W0 image,
+ *   on x = float(v) / 255 (correctly rounded, ToTensor's value): steps 1 and 3' of ssl4gie_color_augment_ft with H0 and
+ *   W0 in S's place on the two axes (the contrast mean over the sample's whole image, reflect edges per axis), no
+ *   rounding to 8-bit levels between the ops, no grayscale, solarize or normalisation.  factors fp32 [B, 4], order
+ *   uint8 [B, 4], sigma fp32 [B] as there.  Writes scratch fp32 [B][3][plane_stride], rows dense at pitch W0.
+ *   max_h / max_w: the largest H0 and W0 of THIS batch, which the host knows; they size the grid only (a smaller image's
+ *   surplus workgroups exit, a larger one is still covered).  workspace: ssl4gie_det_color_workspace_bytes(B) bytes.
+ *   Two launches (statistics, apply), no atomics, sums in a fixed order that the image's size alone decides.
+ * ssl4gie_det_geometry: dataset.py:50-52, 64-66, 73-75 and 82-102 in ONE launch that writes out fp32 [B, 3, F, F].
+ *   Source: scratch (as written by ssl4gie_det_color, same B, index and plane_stride) or, with scratch == NULL, the bank
+ *   itself through float(v) / 255 (dataloaders.py:116-120: the val / test loaders' ToTensor alone).  geom uint8 [B]
+ *   (NULL = 0): bit 0 horizontal flip, bit 1 vertical flip, bit 2 rot90.  With S the source image:
+ *     3. rot90:  T1[i][j] = S[j][W0 - 1 - i], H1 = W0, W1 = H0;   4. hflip: T2[i][j] = T1[i][W1 - 1 - j];
+ *     5. vflip:  T3[i][j] = T2[H1 - 1 - i][j];
+ *     6. only when H1 > F or W1 > F: a zero row below if H1 is odd, a zero column to the right if W1 is odd, then
+ *        F.interpolate(bicubic, antialias=True, align_corners=False) to half the size: output i reads the inputs
+ *        max(0, 2 i - 3) .. min(L, 2 i + 5) - 1 with Keys' a = -0.5 weights w((j - 2 i - 0.5) / 2) over their sum: in
+ *        the interior (-3, -9, 29, 111, 111, 29, -9, -3) / 256.  Horizontal pass, then vertical; no clamp;
+ *     7. p1 = floor((F - W2) / 2), p2 = floor((F - H2) / 2): out[c][y][x] = (T[y - p2][x - p1] - mean[c]) / std[c]
+ *        inside the image and (0 - mean[c]) / std[c] outside.  mean / std are HOST arrays of 3 floats.
+ *   Without step 6 the result is the source value moved: bit-equal to the reference for the bank source.
+ * ssl4gie_det_boxes: the box statements of dataset.py:53-61, 67-71, 76-80, 97 and 103-106, one fp32 operation each in
+ *   that order, hence bit-equal to the reference.  boxes fp32 [m, 4] = (xmin, ymin, xmax, ymax), labels int64 [m], image
+ *   i owns rows box_offsets[i] .. box_offsets[i + 1] (int64 [n + 1]).  out_start int64 [B + 1] (device) says where
+ *   sample b's rows go in out_boxes fp32 [m_out, 4] / out_labels int64 [m_out]; a sample whose row count there differs
+ *   from its bank count is refused like a bad index: NaN boxes, labels -1.  max_boxes: the largest per-sample count of
+ *   the batch (sizes the grid).  One launch.
+ * SSL4GIE_EARG, before anything is launched: a null pointer (geom and, for the geometry, scratch may be NULL),
+ * F % 4 != 0, a std entry equal to 0, scratch / out / out_boxes / boxes not 16-byte aligned, a workspace smaller than the
+ * query says, B > 65535, max_h or max_w below 13.  Pure functions of their inputs: bit-identical from run to run, and
+ * a sample's result does not depend on its place in the batch. */
+size_t ssl4gie_det_color_workspace_bytes(int B);
+int ssl4gie_det_color(const unsigned char* pixels, long long total, const long long* offsets, const int* sizes,
+                      long long n, const long long* index, int B, int max_h, int max_w, const float* factors,
+                      const unsigned char* order, const float* sigma, float* scratch, long long plane_stride,
+                      void* workspace, size_t workspace_bytes, void* stream);
+int ssl4gie_det_geometry(const float* scratch, long long plane_stride, const unsigned char* pixels, long long total,
+                         const long long* offsets, const int* sizes, long long n, const long long* index,
+                         const unsigned char* geom, float* out, int B, int F, const float* mean, const float* std,
+                         void* stream);
+int ssl4gie_det_boxes(const float* boxes, const long long* labels, const long long* box_offsets, long long m,
+                      const int* sizes, long long n, const long long* index, const unsigned char* geom,
+                      const long long* out_start, float* out_boxes, long long* out_labels, long long m_out, int B, int F,
+                      int max_boxes, void* stream);
 
 /* ---------------------------------------------------------------- detection pyramid glue (channels-last)
  * ViTDet_FPN (Models/models.py:213-259) around its GEMM-shaped convolutions:

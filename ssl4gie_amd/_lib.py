@@ -160,6 +160,11 @@ PROTOTYPES = {
     "ssl4gie_color_augment_ft": (i32, [vp, vp, i32, i32, vp, vp, vp, vp, C.POINTER(C.c_float), C.POINTER(C.c_float), vp,
                                        sz, vp]),
     "ssl4gie_paired_warp": (i32, [vp, vp, vp, i32, C.c_long, vp, vp, vp, vp, C.POINTER(C.c_float), f32, i32, i32, vp]),
+    "ssl4gie_det_color_workspace_bytes": (sz, [i32]),
+    "ssl4gie_det_color": (i32, [vp, i64, vp, vp, i64, vp, i32, i32, i32, vp, vp, vp, vp, i64, vp, sz, vp]),
+    "ssl4gie_det_geometry": (i32, [vp, i64, vp, i64, vp, vp, i64, vp, vp, vp, i32, i32, C.POINTER(C.c_float),
+                                   C.POINTER(C.c_float), vp]),
+    "ssl4gie_det_boxes": (i32, [vp, vp, vp, i64, vp, i64, vp, vp, vp, vp, vp, i64, i32, i32, i32, vp]),
     "ssl4gie_maxpool2x2_fwd": (i32, [vp, vp, i32, i32, i32, i32, i32, vp]),
     "ssl4gie_maxpool2x2_bwd": (i32, [vp, vp, vp, i32, i32, i32, i32, i32, vp]),
     "ssl4gie_gelu_map": (i32, [vp, vp, vp, i32, i64, vp]),

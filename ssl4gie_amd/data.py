@@ -34,6 +34,18 @@ same flips and affine) are `FinetuneAugment`: ops.color_augment_ft, then ops.pai
     loader = DeviceLoader(bank, 16, transform=FinetuneAugment.segmentation())
     for batch_idx, (data, target) in enumerate(loader):                 # Binary_segmentation/train.py, as written
         data, target = data.to(device), target.to(device)               # already there
+
+The detection loaders (Object_detection/Data/dataloaders.py:75-112, Data/dataset.py:38-113 with a fixed size: colour
+jitter and the 25-tap blur on the full-resolution image, rot90 and two flips with the boxes carried along, an
+antialiased bicubic halving when a side exceeds the fixed size, a centre pad) are `DetectionTransform` over a
+`RaggedImageBank` — images of different stored sizes in one flat buffer, with their boxes —: ops.det_color,
+ops.det_geometry and ops.det_boxes.  `DetectionLoader` yields the reference's collate_fn tuples:
+
+    bank = RaggedImageBank.from_npy("kvasir_det", "cuda")               # tools/pack_images.py --ragged --boxes wrote it
+    loader = DetectionLoader(bank, 4, sampler=sampler, transform=DetectionTransform(1024))
+    for images, targets in loader:                                      # train_detection.py:67-69, as written
+        images = list(image.cuda(rank) for image in images)             # already there
+        targets = [{k: v.cuda(rank) for k, v in t.items()} for t in targets]
 """
 from __future__ import annotations
 
@@ -121,6 +133,133 @@ class DeviceImageBank:
         if isinstance(labels, str):
             labels = np.load(labels)
         return cls(to_device(arr), labels, targets)
+
+
+class RaggedImageBank:
+    """uint8 HWC images of DIFFERENT sizes in one flat device buffer, and their ground-truth boxes: the stored form of
+    a detection dataset.  pixels uint8 [total]; image i is the dense rows (3 W bytes each) at offsets[i] (int64 [n], each
+    a multiple of 16, derived from the sizes) and is sizes[i] = (H, W) (int32 [n, 2]).  boxes fp32 [m, 4] = (xmin, ymin,
+    xmax, ymax) in stored-image pixels, image i owning rows box_offsets[i] .. box_offsets[i + 1] (int64 [n + 1]);
+    box_labels int64 [m], all 1 by default (train_detection.py:154-166: one class).  `sizes_host` / `box_offsets_host`
+    are host copies (lists), so that grids and the per-image split need no read-back.  A map-style dataset like
+    DeviceImageBank: items are (index, 0), torch's samplers and set_epoch work unchanged."""
+
+    ALIGN = 16
+    MIN_SIDE = 13   # the 25-tap blur reflects 12 pixels
+
+    @staticmethod
+    def offsets_of(sizes):
+        """int64 numpy [n] and the total byte count: each image starts at the next multiple of 16"""
+        sizes = np.asarray(sizes, dtype=np.int64).reshape(-1, 2)
+        nbytes = (sizes[:, 0] * sizes[:, 1] * 3 + RaggedImageBank.ALIGN - 1) // RaggedImageBank.ALIGN * RaggedImageBank.ALIGN
+        ends = np.cumsum(nbytes)
+        return (ends - nbytes).astype(np.int64), int(ends[-1]) if len(ends) else 0
+
+    def __init__(self, pixels, sizes, boxes, box_offsets, box_labels=None):
+        if not (torch.is_tensor(pixels) and pixels.dtype == torch.uint8 and pixels.dim() == 1 and pixels.is_contiguous()):
+            raise ValueError("RaggedImageBank needs pixels as a contiguous uint8 vector")
+        if not (torch.is_tensor(sizes) and sizes.dtype == torch.int32 and sizes.dim() == 2 and sizes.shape[1] == 2
+                and sizes.shape[0] >= 1):
+            raise ValueError("sizes must be an int32 tensor [n, 2], n >= 1")
+        n = int(sizes.shape[0])
+        self.sizes_host = [(int(h), int(w)) for h, w in sizes.cpu().tolist()]
+        if min(min(hw) for hw in self.sizes_host) < self.MIN_SIDE:
+            raise ValueError(f"every side must be >= {self.MIN_SIDE} (the 25-tap blur reflects 12 pixels)")
+        offsets, total = self.offsets_of(self.sizes_host)
+        if pixels.numel() != total:
+            raise ValueError(f"pixels holds {pixels.numel()} bytes, the sizes need {total} (each image at a multiple of 16)")
+        if not (torch.is_tensor(boxes) and boxes.dtype == torch.float32 and boxes.dim() == 2 and boxes.shape[1] == 4):
+            raise ValueError("boxes must be a float32 tensor [m, 4]")
+        if not (torch.is_tensor(box_offsets) and box_offsets.dtype == torch.int64 and tuple(box_offsets.shape) == (n + 1,)):
+            raise ValueError(f"box_offsets must be an int64 tensor [{n + 1}]")
+        self.box_offsets_host = [int(v) for v in box_offsets.cpu().tolist()]
+        if self.box_offsets_host[0] != 0 or any(b < a for a, b in zip(self.box_offsets_host, self.box_offsets_host[1:])):
+            raise ValueError("box_offsets must start at 0 and never decrease")
+        m = int(boxes.shape[0])
+        if self.box_offsets_host[-1] != m:
+            raise ValueError(f"{m} boxes, but box_offsets[-1] = {self.box_offsets_host[-1]}")
+        dev = pixels.device
+        if box_labels is None:
+            box_labels = torch.ones(m, dtype=torch.int64, device=dev)
+        elif not (torch.is_tensor(box_labels) and box_labels.dtype == torch.int64 and tuple(box_labels.shape) == (m,)):
+            raise ValueError(f"box_labels must be an int64 tensor [{m}]")
+        self.pixels, self.sizes = pixels, sizes.contiguous().to(dev)
+        self.offsets = torch.from_numpy(offsets).to(dev)
+        self.boxes, self.box_offsets = boxes.contiguous().to(dev), box_offsets.contiguous().to(dev)
+        self.box_labels = box_labels.contiguous().to(dev)
+        self.offsets_host = offsets.tolist()
+        self.max_hw = (max(h for h, _ in self.sizes_host), max(w for _, w in self.sizes_host))
+        self.max_pixels = max(h * w for h, w in self.sizes_host)
+
+    device = property(lambda self: self.pixels.device)
+    targets = None
+
+    def __len__(self):
+        return len(self.sizes_host)
+
+    def __getitem__(self, i):
+        i = int(i)
+        if not 0 <= i < len(self):
+            raise IndexError(i)
+        return i, 0
+
+    def image(self, i):
+        """uint8 [H, W, 3] view of image i"""
+        i, _ = self[i]
+        (h, w), o = self.sizes_host[i], self.offsets_host[i]
+        return self.pixels[o:o + h * w * 3].view(h, w, 3)
+
+    @staticmethod
+    def _box_arrays(boxes_per_image, n):
+        if len(boxes_per_image) != n:
+            raise ValueError(f"{len(boxes_per_image)} box arrays for {n} images")
+        arrs = []
+        for b in boxes_per_image:
+            b = np.asarray(b, dtype=np.float32)
+            b = b.reshape(0, 4) if b.size == 0 else b
+            if b.ndim != 2 or b.shape[1] != 4:
+                raise ValueError(f"boxes of an image must be [k, 4], got {b.shape}")
+            arrs.append(b)
+        counts = np.array([len(b) for b in arrs], dtype=np.int64)
+        return (np.concatenate(arrs, axis=0) if arrs else np.zeros((0, 4), np.float32)), \
+            np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
+
+    @classmethod
+    def from_arrays(cls, images, boxes_per_image, device, box_labels=None):
+        """images: a list of HWC uint8 arrays; boxes_per_image: a list of [k, 4] arrays, one per image (k may be 0)"""
+        if len(images) < 1:
+            raise ValueError("RaggedImageBank needs at least one image")
+        for a in images:
+            if not (isinstance(a, np.ndarray) and a.dtype == np.uint8 and a.ndim == 3 and a.shape[2] == 3
+                    and a.flags["C_CONTIGUOUS"]):
+                raise ValueError("every image must be a C-contiguous uint8 array [H, W, 3]")
+        sizes = np.array([a.shape[:2] for a in images], dtype=np.int32)
+        offsets, total = cls.offsets_of(sizes)
+        flat = np.zeros(total, dtype=np.uint8)
+        for a, o in zip(images, offsets):
+            flat[o:o + a.size] = a.reshape(-1)
+        boxes, box_offsets = cls._box_arrays(boxes_per_image, len(images))
+        labels = None if box_labels is None else torch.as_tensor(np.asarray(box_labels), dtype=torch.int64)
+        return cls(torch.from_numpy(flat).to(device), torch.from_numpy(sizes), torch.from_numpy(boxes),
+                   torch.from_numpy(box_offsets), labels)
+
+    @classmethod
+    def from_npy(cls, prefix, device, chunk_bytes=256 << 20):
+        """<prefix>.pixels.npy, .sizes.npy, .boxes.npy, .box_offsets.npy as tools/pack_images.py --ragged writes them.
+        The pixel file is memory-mapped and copied chunk by chunk, so the host never holds a second copy of it."""
+        arr = np.load(prefix + ".pixels.npy", mmap_mode="r")
+        if arr.dtype != np.uint8 or arr.ndim != 1:
+            raise ValueError(f"{prefix}.pixels.npy: expected a uint8 vector, got {arr.dtype} {arr.shape}")
+        sizes, boxes = np.load(prefix + ".sizes.npy"), np.load(prefix + ".boxes.npy")
+        box_offsets = np.load(prefix + ".box_offsets.npy")
+        if sizes.dtype != np.int32 or boxes.dtype != np.float32 or box_offsets.dtype != np.int64:
+            raise ValueError(f"{prefix}: expected int32 sizes, float32 boxes and int64 box_offsets, got {sizes.dtype}, "
+                             f"{boxes.dtype}, {box_offsets.dtype}")
+        dst = torch.empty(arr.shape[0], dtype=torch.uint8, device=device)
+        step = max(1, int(chunk_bytes))
+        for a in range(0, arr.shape[0], step):
+            dst[a:a + step].copy_(torch.from_numpy(np.array(arr[a:a + step])))
+        return cls(dst, torch.from_numpy(sizes), torch.from_numpy(boxes), torch.from_numpy(box_offsets))
 
 
 @functools.lru_cache(maxsize=64)
@@ -363,6 +502,143 @@ class FinetuneAugment:
         if bank.targets is None:
             return ops.paired_warp(x, matrix, flip, self.fill)
         return ops.paired_warp(x, matrix, flip, self.fill, bank.targets, index, 0.0)
+
+
+class DetectionTransform:
+    """The detection train loader (Object_detection/Data/dataloaders.py:75-99, Data/dataset.py:38-113 with arch !=
+    "resnet50") for DetectionLoader, drawn and computed on the bank's device: ColorJitter(brightness, contrast,
+    saturation, hue) -> GaussianBlur((25, 25), blur_sigma) on the stored image -> ToTensor -> rot90, hflip, vflip, each
+    where a uniform draw exceeds 0.5, the boxes carried along -> an antialiased bicubic halving when a side exceeds
+    fixed_size -> a centre pad to fixed_size^2 -> (x - mean) / std, the padding being the normalised value of black
+    (the reference normalises in the model: mean 0, std 1 here).  DetectionTransform.eval(fixed_size) is the val /
+    test loader: ToTensor, the halving and the pad.
+    __call__(bank, index) -> (images fp32 [B, 3, F, F], boxes fp32 [sum k, 4], labels int64 [sum k]); the per-sample
+    counts are the bank's host copy, index being known on the host too (`index_host`, else it is read back).
+    Out of scope: arch = "resnet50" (no fixed size), post_process=True, and a bank with a side above 2 fixed_size
+    (the reference's negative pad, a crop)."""
+
+    def __init__(self, fixed_size=1024, brightness=0.4, contrast=0.5, saturation=0.25, hue=0.01,
+                 blur_sigma=(0.001, 2.0), rotate=True, hflip=True, vflip=True, mean=(0.0, 0.0, 0.0),
+                 std=(1.0, 1.0, 1.0), generator=None, color=True):
+        if fixed_size < 4 or fixed_size % 4:
+            raise ValueError(f"fixed_size must be a multiple of 4, got {fixed_size}")
+        if blur_sigma is not None and not 0 < blur_sigma[0] <= blur_sigma[1]:
+            raise ValueError(f"blur_sigma must be None or 0 < lo <= hi, got {tuple(blur_sigma)}")
+        if len(mean) != 3 or len(std) != 3 or any(float(v) == 0.0 for v in std):
+            raise ValueError("mean and std must hold three values, std none equal to 0")
+        self.fixed_size, self.rotate, self.hflip, self.vflip = int(fixed_size), bool(rotate), bool(hflip), bool(vflip)
+        self.blur_sigma = None if blur_sigma is None else (float(blur_sigma[0]), float(blur_sigma[1]))
+        self.mean, self.std, self.generator = tuple(float(v) for v in mean), tuple(float(v) for v in std), generator
+        # the jitter parameters are ColorAugment's draw with nothing else switched on, as in FinetuneAugment
+        self.color = None if not color else ColorAugment(brightness, contrast, saturation, hue, jitter_p=1.0, gray_p=0.0,
+                                                         blur_p=0.0, solarize_p=0.0, generator=generator)
+        self._scratch = None
+        self.last_draw = None
+
+    @classmethod
+    def eval(cls, fixed_size=1024, mean=(0.0, 0.0, 0.0), std=(1.0, 1.0, 1.0)):
+        """dataloaders.py:116-120: no colour stage, no rotation, no flips"""
+        return cls(fixed_size, rotate=False, hflip=False, vflip=False, mean=mean, std=std, color=False)
+
+    def draw(self, B, device):
+        """(factors fp32 [B, 4], order uint8 [B, 4], sigma fp32 [B], geom uint8 [B]: bit 0 hflip, bit 1 vflip, bit 2
+        rot90); advances the generator.  Without a colour stage the first three are None."""
+        factors = order = sigma = None
+        if self.color is not None:
+            factors, order, _, _ = self.color.draw(B, device)
+        u = torch.rand(B, 4, dtype=torch.float64, device=device, generator=self.generator)
+        if self.color is not None:
+            if self.blur_sigma is None:
+                sigma = torch.zeros(B, dtype=torch.float32, device=device)
+            else:
+                lo, hi = self.blur_sigma
+                sigma = (lo + u[:, 0] * (hi - lo)).to(torch.float32)
+        geom = (((u[:, 2] > 0.5) & self.hflip).to(torch.uint8) + 2 * ((u[:, 3] > 0.5) & self.vflip).to(torch.uint8)
+                + 4 * ((u[:, 1] > 0.5) & self.rotate).to(torch.uint8))
+        return factors, order, sigma, geom
+
+    def check(self, bank):
+        if not isinstance(bank, RaggedImageBank):
+            raise TypeError("DetectionTransform needs a RaggedImageBank")
+        if max(bank.max_hw) > 2 * self.fixed_size:
+            raise ValueError(f"the bank holds a side of {max(bank.max_hw)} > 2 x fixed_size = {2 * self.fixed_size}: the "
+                             "reference's negative pad (a crop) is not supported")
+
+    def __call__(self, bank, index, index_host=None):
+        self.check(bank)
+        if index_host is None:
+            index_host = index.tolist()
+        B, F, dev = len(index_host), self.fixed_size, bank.device
+        for i in index_host:
+            if not 0 <= i < len(bank):
+                raise IndexError(i)
+        off = bank.box_offsets_host
+        counts = [off[i + 1] - off[i] for i in index_host]
+        starts = [0]
+        for c in counts:
+            starts.append(starts[-1] + c)
+        self.last_counts = counts
+        out_start = torch.tensor(starts, dtype=torch.int64)
+        if dev.type != "cpu":
+            out_start = out_start.pin_memory()
+        out_start = out_start.to(dev, non_blocking=True)
+        factors, order, sigma, geom = self.last_draw = self.draw(B, dev)
+        scratch = None
+        if self.color is not None and B:
+            need = (bank.max_pixels + 3) & ~3
+            if self._scratch is None or self._scratch.shape[0] < B or self._scratch.shape[2] != need \
+                    or self._scratch.device != dev:
+                self._scratch = torch.empty(B, 3, need, dtype=torch.float32, device=dev)
+            scratch = self._scratch[:B]
+            max_hw = (max(bank.sizes_host[i][0] for i in index_host), max(bank.sizes_host[i][1] for i in index_host))
+            ops.det_color(bank.pixels, bank.offsets, bank.sizes, index, factors, order, sigma, max_hw, scratch)
+        images = ops.det_geometry(bank.pixels, bank.offsets, bank.sizes, index, geom, F, self.mean, self.std, scratch)
+        boxes, labels = ops.det_boxes(bank.boxes, bank.box_labels, bank.box_offsets, bank.sizes, index, geom, out_start,
+                                      starts[-1], max(counts, default=0), F)
+        return images, boxes, labels
+
+
+class DetectionLoader:
+    """The reference's detection DataLoader with its collate_fn (Object_detection/Data/dataloaders.py:12-13, 105-112)
+    over a RaggedImageBank: iteration yields (tuple of B images [3, F, F], tuple of B {"boxes": [k, 4], "labels": [k]}
+    dicts), every entry a view of the batch's tensors, so train_detection.py:67-69 runs as written and its .cuda(rank)
+    calls return the tensors themselves.  The stacked batch of the last iteration is `last_images` ([B, 3, F, F]),
+    `last_boxes`, `last_labels`, for callers that feed the backbone directly.  Per batch the host sends the indices
+    and the boxes' split points; nothing synchronises."""
+
+    def __init__(self, bank, batch_size, sampler=None, drop_last=True, transform=None):
+        if batch_size < 1:
+            raise ValueError("batch_size must be >= 1")
+        self.bank, self.batch_size, self.drop_last = bank, int(batch_size), bool(drop_last)
+        self.sampler = sampler if sampler is not None else torch.utils.data.RandomSampler(bank)
+        self.transform = transform if transform is not None else DetectionTransform()
+        self.transform.check(bank)
+        self.last_images = self.last_boxes = self.last_labels = None
+
+    def __len__(self):
+        n = len(self.sampler)
+        return n // self.batch_size if self.drop_last else (n + self.batch_size - 1) // self.batch_size
+
+    def _batch(self, idx):
+        host = torch.tensor(idx, dtype=torch.int64)
+        dev = self.bank.device
+        if dev.type != "cpu":
+            host = host.pin_memory()
+        images, boxes, labels = self.transform(self.bank, host.to(dev, non_blocking=True), idx)
+        self.last_images, self.last_boxes, self.last_labels = images, boxes, labels
+        counts = self.transform.last_counts
+        targets = tuple({"boxes": b, "labels": l} for b, l in zip(boxes.split(counts), labels.split(counts)))
+        return tuple(images.unbind(0)), targets
+
+    def __iter__(self):
+        idx = []
+        for i in self.sampler:
+            idx.append(int(i))
+            if len(idx) == self.batch_size:
+                yield self._batch(idx)
+                idx = []
+        if idx and not self.drop_last:
+            yield self._batch(idx)
 
 
 class DeviceLoader:

@@ -1471,6 +1471,129 @@ def paired_warp(img, matrix, flip, fill_img, tgt_bank=None, index=None, fill_tgt
     return img_out if tgt_out is None else (img_out, tgt_out)
 
 
+# ------------------------------------------------------------------ detection input pipeline (csrc/color_ops.hip)
+def _det_bank(name, pixels, offsets, sizes, index):
+    _dev(pixels, offsets, sizes, index)
+    if pixels.dtype != torch.uint8 or pixels.dim() != 1 or not pixels.is_contiguous() or pixels.numel() < 1:
+        raise ValueError(f"{name} needs pixels as a contiguous uint8 vector")
+    if sizes.dtype != torch.int32 or sizes.dim() != 2 or sizes.shape[1] != 2 or sizes.shape[0] < 1 \
+            or not sizes.is_contiguous():
+        raise ValueError(f"{name} needs sizes int32 [n, 2]")
+    n = sizes.shape[0]
+    if offsets.dtype != torch.int64 or tuple(offsets.shape) != (n,) or not offsets.is_contiguous():
+        raise ValueError(f"{name} needs offsets int64 [{n}]")
+    if index.dtype != torch.int64 or index.dim() != 1 or not index.is_contiguous():
+        raise ValueError(f"{name} needs index as a contiguous int64 vector")
+    if any(t.device != pixels.device for t in (offsets, sizes, index)):
+        raise ValueError(f"{name} needs all its tensors on one device")
+    return n, index.shape[0]
+
+
+def det_color(pixels, offsets, sizes, index, factors, order, sigma, max_hw, scratch=None):
+    """The colour stage of the detection train loader (ColorJitter -> GaussianBlur((25, 25), sigma)) on the stored
+    H0 x W0 rectangles of a ragged uint8 bank (data.RaggedImageBank's pixels / offsets / sizes): sample b is image
+    index[b]; factors fp32 [B, 4], order uint8 [B, 4], sigma fp32 [B] as in color_augment_ft.  max_hw = (largest H0,
+    largest W0) of this batch, which the caller knows on the host.  Returns the scratch fp32 [B, 3, plane_stride]
+    (rows dense at pitch W0, values in [0, 1] up to the blur's rounding, not normalised) that det_geometry reads;
+    `scratch`, if given, is written instead and decides plane_stride: it must be >= the largest H0 * W0 of the batch
+    (which can be less than max_hw's product); the kernels check it per sample, one that does not fit comes out NaN."""
+    n, B = _det_bank("det_color", pixels, offsets, sizes, index)
+    _dev(factors, order, sigma, scratch)
+    _f32(factors, sigma, scratch)
+    if order.dtype != torch.uint8:
+        raise TypeError(f"order must be uint8, got {order.dtype}")
+    if tuple(factors.shape) != (B, 4) or tuple(order.shape) != (B, 4) or tuple(sigma.shape) != (B,):
+        raise ValueError("det_color needs factors [B, 4], order [B, 4], sigma [B]")
+    max_h, max_w = int(max_hw[0]), int(max_hw[1])
+    if min(max_h, max_w) < 13:
+        raise ValueError(f"det_color needs max_hw >= (13, 13), got {(max_h, max_w)}")
+    if scratch is None:
+        scratch = torch.empty(B, 3, (max_h * max_w + 3) & ~3, dtype=torch.float32, device=pixels.device)
+    elif scratch.dim() != 3 or tuple(scratch.shape[:2]) != (B, 3) or scratch.shape[2] < 169 or not scratch.is_contiguous():
+        raise ValueError(f"scratch must be contiguous fp32 [{B}, 3, plane_stride], got {tuple(scratch.shape)}")
+    if any(t.device != pixels.device for t in (factors, order, sigma, scratch)):
+        raise ValueError("det_color needs all its tensors on one device")
+    if B == 0:
+        return scratch
+    L = _lib.load()
+    ws = torch.empty(L.ssl4gie_det_color_workspace_bytes(B), dtype=torch.uint8, device=pixels.device)
+    _lib.check(L.ssl4gie_det_color(ptr(pixels), pixels.numel(), ptr(offsets), ptr(sizes), n, ptr(index), B, max_h, max_w,
+                                   ptr(factors), ptr(order), ptr(sigma), ptr(scratch), scratch.shape[2], ptr(ws),
+                                   ws.numel(), stream()), "det_color")
+    return scratch
+
+
+def det_geometry(pixels, offsets, sizes, index, geom, F, mean=(0.0, 0.0, 0.0), std=(1.0, 1.0, 1.0), scratch=None):
+    """rot90 / hflip / vflip, the antialiased bicubic halving when a side exceeds F, the centre pad to F x F and
+    (x - mean) / std of the detection loaders, in one launch: fp32 [B, 3, F, F].  geom uint8 [B] (bit 0 hflip, bit 1
+    vflip, bit 2 rot90) or None.  The source is `scratch` (det_color's result for the same index) or, without it, the
+    uint8 bank itself through v / 255 — the val / test loaders' path.  The padding is the normalised value of black.
+    A sample whose index is outside the bank, or whose image does not fit F x F after the halving, is all NaN."""
+    n, B = _det_bank("det_geometry", pixels, offsets, sizes, index)
+    _dev(geom, scratch)
+    _f32(scratch)
+    F = int(F)
+    if F < 4 or F % 4:
+        raise ValueError(f"det_geometry needs F >= 4 and a multiple of 4, got {F}")
+    if geom is not None and (geom.dtype != torch.uint8 or tuple(geom.shape) != (B,) or geom.device != pixels.device):
+        raise ValueError(f"geom must be uint8 [{B}] on the bank's device")
+    if len(mean) != 3 or len(std) != 3 or any(float(v) == 0.0 for v in std):
+        raise ValueError("mean and std must hold three values, std none equal to 0")
+    stride = 0
+    if scratch is not None:
+        if scratch.dim() != 3 or tuple(scratch.shape[:2]) != (B, 3) or not scratch.is_contiguous() \
+                or scratch.device != pixels.device:
+            raise ValueError(f"scratch must be contiguous fp32 [{B}, 3, plane_stride] on the bank's device")
+        stride = scratch.shape[2]
+    out = torch.empty(B, 3, F, F, dtype=torch.float32, device=pixels.device)
+    if B:
+        m = (C.c_float * 3)(*mean)
+        s = (C.c_float * 3)(*std)
+        _lib.check(_lib.load().ssl4gie_det_geometry(ptr(scratch), stride, ptr(pixels), pixels.numel(), ptr(offsets),
+                                                    ptr(sizes), n, ptr(index), ptr(geom), ptr(out), B, F, m, s,
+                                                    stream()), "det_geometry")
+    return out
+
+
+def det_boxes(boxes, labels, box_offsets, sizes, index, geom, out_start, m_out, max_boxes, F):
+    """The boxes of a batch through det_geometry's decisions, in the reference's order of fp32 operations.  boxes fp32
+    [m, 4], labels int64 [m], box_offsets int64 [n + 1], sizes int32 [n, 2]: the bank's; out_start int64 [B + 1] on
+    the device: sample b's rows are out_start[b] .. out_start[b + 1] of the result; m_out = out_start[-1] and max_boxes
+    = the largest per-sample count, both known on the host.  Returns (boxes fp32 [m_out, 4], labels int64 [m_out]);
+    a sample with a bad index, or whose count in out_start is not its bank count, gets NaN boxes and labels -1."""
+    _dev(boxes, labels, box_offsets, sizes, index, geom, out_start)
+    _f32(boxes)
+    if boxes.dim() != 2 or boxes.shape[1] != 4 or not boxes.is_contiguous():
+        raise ValueError(f"boxes must be contiguous fp32 [m, 4], got {tuple(boxes.shape)}")
+    m = boxes.shape[0]
+    if labels.dtype != torch.int64 or tuple(labels.shape) != (m,) or not labels.is_contiguous():
+        raise ValueError(f"labels must be int64 [{m}]")
+    if sizes.dtype != torch.int32 or sizes.dim() != 2 or sizes.shape[1] != 2 or not sizes.is_contiguous():
+        raise ValueError("sizes must be int32 [n, 2]")
+    n = sizes.shape[0]
+    if box_offsets.dtype != torch.int64 or tuple(box_offsets.shape) != (n + 1,) or not box_offsets.is_contiguous():
+        raise ValueError(f"box_offsets must be int64 [{n + 1}]")
+    if index.dtype != torch.int64 or index.dim() != 1 or not index.is_contiguous():
+        raise ValueError("index must be a contiguous int64 vector")
+    B = index.shape[0]
+    if out_start.dtype != torch.int64 or tuple(out_start.shape) != (B + 1,) or not out_start.is_contiguous():
+        raise ValueError(f"out_start must be int64 [{B + 1}]")
+    if geom is not None and (geom.dtype != torch.uint8 or tuple(geom.shape) != (B,)):
+        raise ValueError(f"geom must be uint8 [{B}]")
+    if any(t is not None and t.device != boxes.device for t in (labels, box_offsets, sizes, index, geom, out_start)):
+        raise ValueError("det_boxes needs all its tensors on one device")
+    F, m_out, max_boxes = int(F), int(m_out), int(max_boxes)
+    if F < 4 or F % 4 or m_out < 0 or max_boxes < 0:
+        raise ValueError("det_boxes needs F a multiple of 4, m_out >= 0 and max_boxes >= 0")
+    out_boxes = torch.empty(m_out, 4, dtype=torch.float32, device=boxes.device)
+    out_labels = torch.empty(m_out, dtype=torch.int64, device=boxes.device)
+    if B and m_out:
+        _lib.check(_lib.load().ssl4gie_det_boxes(ptr(boxes), ptr(labels), ptr(box_offsets), m, ptr(sizes), n, ptr(index),
+                                                 ptr(geom), ptr(out_start), ptr(out_boxes), ptr(out_labels), m_out, B, F,
+                                                 max_boxes, stream()), "det_boxes")
+    return out_boxes, out_labels
+
+
 # ------------------------------------------------------------------ evaluation metrics (csrc/metric_ops.hip)
 def _same_device(*ts):
     ts = [t for t in ts if t is not None]

@@ -13,6 +13,15 @@ run once per dataset.
                                      maps), file k of the targets folder (same order rule) beside image k: the
                                      `targets=` of DeviceImageBank.from_npy, for ssl4gie_amd.data.FinetuneAugment
 
+    python tools/pack_images.py /data/kvasir-seg/images --ragged --boxes /data/kvasir-seg/bounding-boxes.json --out kvasir_det
+      -> kvasir_det.pixels.npy       [total] uint8: every image at its OWN size, HWC rows dense, each starting at a
+                                     multiple of 16 bytes (ssl4gie_amd.data.RaggedImageBank.from_npy loads the four)
+         kvasir_det.sizes.npy        [n, 2] int32 (H, W)
+         kvasir_det.boxes.npy        [m, 4] float32 (xmin, ymin, xmax, ymax) in stored-image pixels, from Kvasir's JSON
+                                     ({name: {"bbox": [{"xmin": ..}, ..]}}, read as Object_detection/train_detection.py:154-166)
+         kvasir_det.box_offsets.npy  [n + 1] int64: image k owns rows box_offsets[k] .. box_offsets[k + 1]
+         kvasir_det.files.txt        the file names in bank order: sorted(glob), as train_detection.py:172-173
+
 Every image is converted to RGB and resized to the stored size (--size S: S x S; --size H W) with PIL's antialiased
 bicubic filter, aspect ratio NOT preserved unless --center-crop first cuts the largest centred region of the
 target's aspect.  The stored size is what the random crops are later taken from: 256 for a 224 training size keeps
@@ -96,6 +105,45 @@ def pack(root, out, Hs, Ws, center_crop=False, limit=None):
     return len(items)
 
 
+def pack_ragged(root, boxes_json, out, limit=None):
+    """every image of a flat folder at its own size + Kvasir's boxes -> the four files of a RaggedImageBank"""
+    import json
+    names = sorted(f for f in os.listdir(root) if f.lower().endswith(EXTENSIONS))[:limit]   # sorted(glob(root + "*"))
+    if not names:
+        raise SystemExit(f"no images under {root}")
+    with open(boxes_json) as f:
+        table = json.load(f)
+    sizes = np.zeros((len(names), 2), np.int32)
+    for k, name in enumerate(names):
+        with Image.open(os.path.join(root, name)) as im:
+            sizes[k] = (im.size[1], im.size[0])
+    if sizes.min() < 13:
+        raise SystemExit("an image has a side below 13 pixels: the 25-tap blur reflects 12")
+    nbytes = (sizes[:, 0].astype(np.int64) * sizes[:, 1] * 3 + 15) // 16 * 16
+    ends = np.cumsum(nbytes)
+    flat = np.lib.format.open_memmap(out + ".pixels.npy", mode="w+", dtype=np.uint8, shape=(int(ends[-1]),))
+    boxes, offsets = [], [0]
+    for k, name in enumerate(names):
+        with Image.open(os.path.join(root, name)) as im:
+            a = np.asarray(im.convert("RGB"), dtype=np.uint8)
+        start = int(ends[k] - nbytes[k])
+        flat[start:start + a.size] = a.reshape(-1)
+        flat[start + a.size:int(ends[k])] = 0
+        entry = table.get(os.path.splitext(name)[0], table.get(name))
+        if entry is None:
+            raise SystemExit(f"{name}: no entry in {boxes_json}")
+        boxes += [[b["xmin"], b["ymin"], b["xmax"], b["ymax"]] for b in entry["bbox"]]
+        offsets.append(len(boxes))
+    flat.flush()
+    del flat
+    np.save(out + ".sizes.npy", sizes)
+    np.save(out + ".boxes.npy", np.asarray(boxes, dtype=np.float32).reshape(-1, 4))
+    np.save(out + ".box_offsets.npy", np.asarray(offsets, dtype=np.int64))
+    with open(out + ".files.txt", "w") as f:
+        f.writelines(n + "\n" for n in names)
+    return len(names), len(boxes), int(ends[-1])
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("root")
@@ -104,7 +152,16 @@ def main():
     ap.add_argument("--center-crop", action="store_true")
     ap.add_argument("--limit", type=int, default=None)
     ap.add_argument("--targets", default=None, help="folder of masks (8-bit) or depth maps (16-bit), one per image")
+    ap.add_argument("--ragged", action="store_true", help="keep every image at its own size (detection): needs --boxes")
+    ap.add_argument("--boxes", default=None, help="Kvasir's bounding-boxes.json, with --ragged")
     a = ap.parse_args()
+    if a.ragged or a.boxes:
+        if not (a.ragged and a.boxes):
+            raise SystemExit("--ragged and --boxes come together")
+        n, m, total = pack_ragged(a.root, a.boxes, a.out, a.limit)
+        print(f"{n} images, {m} boxes -> {a.out}.pixels.npy [{total}] uint8 ({total / 1e9:.2f} GB), .sizes.npy, .boxes.npy, "
+              f".box_offsets.npy")
+        return
     Hs, Ws = (a.size[0], a.size[0]) if len(a.size) == 1 else (a.size[0], a.size[1])
     if a.targets and a.center_crop:
         raise SystemExit("--targets with --center-crop is not supported: the reference squashes both to the size")
