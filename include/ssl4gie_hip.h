@@ -17,7 +17,8 @@
  *   - ssl4gie_abi_version() = 12 (ssl4gie_view_sample_u8, after it ssl4gie_color_augment{_workspace_bytes,}, and after those ssl4gie_color_augment_ft / ssl4gie_paired_warp, joined revision 12
  *     without a new number: added symbols, nothing existing changed, so a caller built against the earlier 12 runs unchanged; the evaluation
  *     metrics ssl4gie_seg_{counts,scores} / ssl4gie_confusion_{update,scores} / ssl4gie_lower_median_{workspace_bytes,f32} / ssl4gie_depth_eval{_workspace_bytes,}
- *     joined it the same way, and so did the detection input entry points ssl4gie_det_color{_workspace_bytes,} / ssl4gie_det_geometry / ssl4gie_det_boxes; 11: before the sixteen BatchNorm entry points that had grown one per fusion (ssl4gie_bn_fwd / _fwd_partials / _fwd_partials_bits /
+ *     joined it the same way, and so did the detection input entry points ssl4gie_det_color{_workspace_bytes,} / ssl4gie_det_geometry / ssl4gie_det_boxes and the
+ *     detection metric ssl4gie_det_map_{workspace_bytes,match,order,accumulate}; 11: before the sixteen BatchNorm entry points that had grown one per fusion (ssl4gie_bn_fwd / _fwd_partials / _fwd_partials_bits /
  *     _coef_partials / _coef_stats / _apply_bits, _stats / _stats_partials, _bwd / _bwd_xmask / _bwd_bits, _bwd_reduce / _reduce_xmask / _reduce_bits,
  *     _bwd_apply / _apply_xmask) were REPLACED by five with a source and a mask kind — the same launches, new signatures; 10: before the diagnostics entry point that read the 256x256 NT kernel's in-kernel
  *     time stamps was REMOVED with the debug build of the library — the one removal in this history; 9: before ssl4gie_infonce_{workspace_bytes,loss} / ssl4gie_cross_entropy{_workspace_bytes,} /
@@ -919,6 +920,59 @@ int ssl4gie_lower_median_f32(const float* x, long long n, float* out, void* work
 size_t ssl4gie_depth_eval_workspace_bytes(int B, int S, int H, int W);
 int ssl4gie_depth_eval(const float* pred, const float* target, const float* target_og, float* out, int B, int Sh,
                        int Sw, int H, int W, float scale_, void* workspace, void* stream);
+
+/* ---------------------------------------------------------------- detection metric: COCO mAP (joined ABI 12)
+ * Object_detection/train_detection.py:113-151 (`test()`, every epoch) and Object_detection/eval_detection.py:21-44 score
+ * the detector with torchmetrics.detection.mean_ap.MeanAveragePrecision() (torchmetrics 1.1.2, requirements.txt:9:
+ * pycocotools' COCOeval with the default 10 IoU thresholds, 101 recall thresholds, maxDets (1, 10, 100) and the four
+ * area ranges) and read ["map"], ["map_50"], ["map_75"].  The rule is written out in ssl4gie_amd/metrics.py
+ * (MeanAveragePrecision); csrc/det_map_ops.hip has the kernels.  All detections of a loader lie end to end: det_boxes
+ * fp32 [n_det, 4] (xyxy), det_scores fp32 [n_det], det_labels int64 [n_det], image i owning [det_off[i], det_off[i + 1])
+ * (det_off, gt_off: int32 [n_img + 1] on the device); gt_boxes fp32 [n_gt, 4], gt_labels int64 [n_gt] likewise.
+ *
+ * match       one workgroup per image.  rank int32 [n_det]: the stable rank of a detection among the same-label
+ *             detections of its image (descending score, insertion order on ties); a rank >= 100 is dropped, and a
+ *             detection with a label outside [0, 255] gets rank 1024.  matched / ignored uint64 [n_det]: bit
+ *             (area * 10 + threshold) of COCOeval.evaluateImg's dtm != 0 / dtIg, areas in the order all, small, medium,
+ *             large, thresholds = iou_thresholds (HOST array of 10 doubles; torch.linspace(0.5, 0.95, 10).tolist()); 0
+ *             for a dropped detection.  npig int32 [256, 4]: non-ignored ground truths per class and area; present
+ *             int32 [256]: 1 for a class seen in a detection or a ground truth; flag int32 [1]: bit 0 = a label outside
+ *             [0, 255] (such an entry takes no part), bit 1 = offsets that are not ascending, leave [0, n] or give an
+ *             image more than 1024 entries (such an image is skipped; nothing is read through its offsets).  The three
+ *             are zeroed first.  Width and height are fp32 differences; every decision after that is fp64, uncontracted
+ *             (csrc/Makefile builds det_map_ops.hip with -ffp-contract=off: -ffp-contract=fast disregards the pragma).
+ * order       sorted_idx uint32 [n_det]: the first seg_off[256] entries are the kept detections (rank < 100, label in
+ *             range) stably sorted by (label ascending, score descending; -0 == +0), ties in insertion order; seg_off
+ *             int32 [257]: class c owns [seg_off[c], seg_off[c + 1]).  A least-significant-digit radix sort, five 8-bit
+ *             passes, 15 launches; workspace: 16-byte aligned, ssl4gie_det_map_workspace_bytes(n_img, n_det, n_gt) bytes
+ *             (0 where a size is <= 0 or a total exceeds SSL4GIE_DET_MAP_MAX_TOTAL; the size depends on n_det alone).
+ * accumulate  COCOeval.accumulate for the six (area, maxDet) pairs the summaries read — (all, 100), (small, 100),
+ *             (medium, 100), (large, 100), (all, 1), (all, 10) — one workgroup per (class, pair, threshold): stats fp64
+ *             [256, 6, 10, 2] = (sum of the 101 interpolated precisions, final recall), -1 where the class has no
+ *             non-ignored ground truth in the area, untouched for a class not present; rec_thresholds: HOST array of 101
+ *             doubles (torch.linspace(0, 1, 101).tolist()).  Then COCOeval.summarize: out64 fp64 [12] / out32 fp32 [12]
+ *             (the same values rounded) = map, map_50, map_75, map_small, map_medium, map_large, mar_1, mar_10, mar_100,
+ *             mar_small, mar_medium, mar_large (the mean over the entries > -1, -1 without any); outi int32 [258] =
+ *             number of classes, flag word, the classes ascending (-1 beyond).  With n_det == 0 (or no ground truth)
+ *             skip `order` and pass a zeroed seg_off.
+ * SSL4GIE_EARG: a null pointer (those of an empty side excepted), n_img <= 0, a negative count, a total above
+ * SSL4GIE_DET_MAP_MAX_TOTAL, n_det <= 0 for `order`. */
+#define SSL4GIE_DET_MAP_MAX_PER_IMAGE 1024
+#define SSL4GIE_DET_MAP_CLASSES 256
+#define SSL4GIE_DET_MAP_CHUNK 256            /* detections per scan step of `accumulate` */
+#define SSL4GIE_DET_MAP_MAX_TOTAL (1 << 24)
+size_t ssl4gie_det_map_workspace_bytes(int n_img, long long n_det, long long n_gt);
+int ssl4gie_det_map_match(const float* det_boxes, const float* det_scores, const long long* det_labels,
+                          const int* det_off, const float* gt_boxes, const long long* gt_labels, const int* gt_off,
+                          int n_img, long long n_det, long long n_gt, const double* iou_thresholds, int* rank,
+                          unsigned long long* matched, unsigned long long* ignored, int* npig, int* present, int* flag,
+                          void* stream);
+int ssl4gie_det_map_order(const float* det_scores, const long long* det_labels, const int* rank, long long n_det,
+                          unsigned* sorted_idx, int* seg_off, void* workspace, void* stream);
+int ssl4gie_det_map_accumulate(const unsigned* sorted_idx, const int* seg_off, const int* rank,
+                               const unsigned long long* matched, const unsigned long long* ignored, const int* npig,
+                               const int* present, const int* flag, long long n_det, const double* rec_thresholds,
+                               double* stats, double* out64, float* out32, int* outi, void* stream);
 
 /* ---------------------------------------------------------------- direct xGMI gradient all-reduce
  * replaces the NCCL bucket all-reduce of DistributedDataParallel (Models/mae/main_pretrain.py:175,

@@ -23,6 +23,7 @@ EPI_NONE, EPI_BIAS, EPI_BIAS_GELU, EPI_BIAS_RESIDUAL, EPI_DGELU, EPI_BIAS_GELU_G
 BN_FROM_X, BN_FROM_PARTIALS, BN_FROM_STATS, BN_FROM_COEF = range(4)   # ssl4gie_bn_fwd: source of the normalisation
 FILTER_BILINEAR, FILTER_BICUBIC = 0, 1                                # ssl4gie_view_sample_u8: resampling filter
 TGT_U8, TGT_U16, TGT_F32 = range(3)                                   # ssl4gie_paired_warp: element type of the target bank
+DET_MAP_MAX_PER_IMAGE, DET_MAP_CLASSES, DET_MAP_CHUNK = 1024, 256, 256   # ssl4gie_det_map_*: the caps and the scan step
 PRED_I64 = 2                                                          # ssl4gie_confusion_update: int64 predictions instead of logits
 BN_MASK_NONE, BN_MASK_Y, BN_MASK_X, BN_MASK_BITS = range(4)           # backward: source of the ReLU mask
 
@@ -200,6 +201,12 @@ PROTOTYPES = {
     "ssl4gie_lower_median_f32": (i32, [vp, i64, vp, vp, vp]),
     "ssl4gie_depth_eval_workspace_bytes": (sz, [i32, i32, i32, i32]),
     "ssl4gie_depth_eval": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, i32, f32, vp, vp]),
+    "ssl4gie_det_map_workspace_bytes": (sz, [i32, i64, i64]),
+    "ssl4gie_det_map_match": (i32, [vp, vp, vp, vp, vp, vp, vp, i32, i64, i64, C.POINTER(C.c_double), vp, vp, vp, vp, vp,
+                                    vp, vp]),
+    "ssl4gie_det_map_order": (i32, [vp, vp, vp, i64, vp, vp, vp, vp]),
+    "ssl4gie_det_map_accumulate": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, i64, C.POINTER(C.c_double), vp, vp, vp, vp,
+                                         vp]),
     "ssl4gie_allreduce_direct_blob_bytes": (sz, []),
     "ssl4gie_allreduce_direct_init": (i32, [i32, i32, sz, vp, C.POINTER(vp)]),
     "ssl4gie_allreduce_direct_connect": (i32, [vp, vp]),

@@ -1708,3 +1708,100 @@ def depth_eval(pred, target, target_og, scale_):
     _lib.check(L.ssl4gie_depth_eval(ptr(pred), ptr(target), ptr(target_og), ptr(out), B, S, S, H, W, float(scale_),
                                     ptr(ws), stream()), "depth_eval")
     return out
+
+
+# ------------------------------------------------------------------ detection metric (csrc/det_map_ops.hip)
+DET_MAP_IOU_THRESHOLDS = torch.linspace(0.5, 0.95, 10).tolist()   # fp32 values widened: as torchmetrics builds them
+DET_MAP_REC_THRESHOLDS = torch.linspace(0.0, 1.0, 101).tolist()
+DET_MAP_NAMES = ("map", "map_50", "map_75", "map_small", "map_medium", "map_large", "mar_1", "mar_10", "mar_100",
+                 "mar_small", "mar_medium", "mar_large")
+
+
+def _det_map_side(boxes, labels, off, n_img, what):
+    if boxes.dtype != torch.float32 or boxes.dim() != 2 or boxes.shape[1] != 4:
+        raise ValueError(f"{what} boxes must be float32 [n, 4], got {boxes.dtype} {tuple(boxes.shape)}")
+    if labels.dtype != torch.int64 or tuple(labels.shape) != (boxes.shape[0],):
+        raise ValueError(f"{what} labels must be int64 [{boxes.shape[0]}]")
+    if off.dtype != torch.int32 or tuple(off.shape) != (n_img + 1,):
+        raise ValueError(f"{what} offsets must be int32 [{n_img + 1}]")
+
+
+def det_map_match(det_boxes, det_scores, det_labels, det_off, gt_boxes, gt_labels, gt_off):
+    """COCOeval.evaluateImg for every image, class, area range and IoU threshold in one launch.  The detections of all
+    images end to end (boxes fp32 [N, 4] xyxy, scores fp32 [N], labels int64 [N]), image i owning [det_off[i],
+    det_off[i + 1]) (int32 [n_img + 1] on the device); ground truths likewise.  Returns rank int32 [N], matched and
+    ignored int64 [N] (bit = area * 10 + threshold), npig int32 [256, 4], present int32 [256], flag int32 [1]."""
+    ts = (det_boxes, det_scores, det_labels, det_off, gt_boxes, gt_labels, gt_off)
+    _dev(*ts)
+    _same_device(*ts)
+    n_img = det_off.numel() - 1
+    if n_img < 1:
+        raise ValueError("det_map_match needs at least one image")
+    _det_map_side(det_boxes, det_labels, det_off, n_img, "detection")
+    _det_map_side(gt_boxes, gt_labels, gt_off, n_img, "ground-truth")
+    N, G = det_boxes.shape[0], gt_boxes.shape[0]
+    if det_scores.dtype != torch.float32 or tuple(det_scores.shape) != (N,):
+        raise ValueError(f"scores must be float32 [{N}]")
+    dev = det_off.device
+    rank = torch.zeros(N, dtype=torch.int32, device=dev)
+    matched = torch.zeros(N, dtype=torch.int64, device=dev)
+    ignored = torch.zeros(N, dtype=torch.int64, device=dev)
+    npig = torch.empty(_lib.DET_MAP_CLASSES, 4, dtype=torch.int32, device=dev)
+    present = torch.empty(_lib.DET_MAP_CLASSES, dtype=torch.int32, device=dev)
+    flag = torch.empty(1, dtype=torch.int32, device=dev)
+    thr = (C.c_double * 10)(*DET_MAP_IOU_THRESHOLDS)
+    _lib.check(_lib.load().ssl4gie_det_map_match(ptr(det_boxes) if N else 0, ptr(det_scores) if N else 0,
+                                                 ptr(det_labels) if N else 0, ptr(det_off), ptr(gt_boxes) if G else 0,
+                                                 ptr(gt_labels) if G else 0, ptr(gt_off), n_img, N, G, thr, ptr(rank),
+                                                 ptr(matched), ptr(ignored), ptr(npig), ptr(present), ptr(flag),
+                                                 stream()), "det_map_match")
+    return rank, matched, ignored, npig, present, flag
+
+
+def det_map_order(det_scores, det_labels, rank):
+    """The kept detections (rank < 100, label in [0, 255]) stably sorted by (label ascending, score descending), ties
+    in insertion order: sorted_idx int32 [N] (the first seg_off[256] entries count) and seg_off int32 [257]."""
+    _dev(det_scores, det_labels, rank)
+    _same_device(det_scores, det_labels, rank)
+    N = det_scores.numel()
+    if det_scores.dtype != torch.float32 or det_labels.dtype != torch.int64 or rank.dtype != torch.int32 or \
+            det_scores.dim() != 1 or tuple(det_labels.shape) != (N,) or tuple(rank.shape) != (N,):
+        raise ValueError("det_map_order needs scores float32 [N], labels int64 [N], rank int32 [N]")
+    L = _lib.load()
+    nb = L.ssl4gie_det_map_workspace_bytes(1, N, 1)   # the size depends on the number of detections alone
+    if nb == 0:
+        raise ValueError(f"det_map_order: invalid number of detections {N}")
+    ws = torch.empty(nb, dtype=torch.uint8, device=det_scores.device)
+    sorted_idx = torch.zeros(N, dtype=torch.int32, device=det_scores.device)
+    seg_off = torch.empty(_lib.DET_MAP_CLASSES + 1, dtype=torch.int32, device=det_scores.device)
+    _lib.check(L.ssl4gie_det_map_order(ptr(det_scores), ptr(det_labels), ptr(rank), N, ptr(sorted_idx), ptr(seg_off),
+                                       ptr(ws), stream()), "det_map_order")
+    return sorted_idx, seg_off
+
+
+def det_map_accumulate(sorted_idx, seg_off, rank, matched, ignored, npig, present, flag):
+    """COCOeval.accumulate and .summarize: stats fp64 [256, 6, 10, 2] (101-point precision sum, final recall; pairs
+    (all, 100), (small, 100), (medium, 100), (large, 100), (all, 1), (all, 10)), out64 fp64 [12] and out32 fp32 [12]
+    in DET_MAP_NAMES' order, outi int32 [258] = number of classes, flag word, classes ascending."""
+    ts = (sorted_idx, seg_off, rank, matched, ignored, npig, present, flag)
+    _dev(*ts)
+    _same_device(*ts)
+    N = rank.numel()
+    if sorted_idx.dtype != torch.int32 or rank.dtype != torch.int32 or matched.dtype != torch.int64 or \
+            ignored.dtype != torch.int64 or sorted_idx.numel() != N or matched.numel() != N or ignored.numel() != N:
+        raise ValueError("det_map_accumulate needs sorted_idx, rank int32 [N] and matched, ignored int64 [N]")
+    if any(t.dtype != torch.int32 for t in (seg_off, npig, present, flag)) or seg_off.numel() != 257 or \
+            npig.numel() != 1024 or present.numel() != 256 or flag.numel() != 1:
+        raise ValueError("det_map_accumulate needs seg_off int32 [257], npig int32 [256, 4], present int32 [256], "
+                         "flag int32 [1]")
+    dev = rank.device
+    stats = torch.zeros(_lib.DET_MAP_CLASSES, 6, 10, 2, dtype=torch.float64, device=dev)
+    out64 = torch.empty(12, dtype=torch.float64, device=dev)
+    out32 = torch.empty(12, dtype=torch.float32, device=dev)
+    outi = torch.empty(2 + _lib.DET_MAP_CLASSES, dtype=torch.int32, device=dev)
+    rec = (C.c_double * 101)(*DET_MAP_REC_THRESHOLDS)
+    _lib.check(_lib.load().ssl4gie_det_map_accumulate(ptr(sorted_idx) if N else 0, ptr(seg_off), ptr(rank) if N else 0,
+                                                      ptr(matched) if N else 0, ptr(ignored) if N else 0, ptr(npig),
+                                                      ptr(present), ptr(flag), N, rec, ptr(stats), ptr(out64),
+                                                      ptr(out32), ptr(outi), stream()), "det_map_accumulate")
+    return stats, out64, out32, outi
