@@ -18,7 +18,8 @@
  *     without a new number: added symbols, nothing existing changed, so a caller built against the earlier 12 runs unchanged; the evaluation
  *     metrics ssl4gie_seg_{counts,scores} / ssl4gie_confusion_{update,scores} / ssl4gie_lower_median_{workspace_bytes,f32} / ssl4gie_depth_eval{_workspace_bytes,}
  *     joined it the same way, and so did the detection input entry points ssl4gie_det_color{_workspace_bytes,} / ssl4gie_det_geometry / ssl4gie_det_boxes and the
- *     detection metric ssl4gie_det_map_{workspace_bytes,match,order,accumulate}; 11: before the sixteen BatchNorm entry points that had grown one per fusion (ssl4gie_bn_fwd / _fwd_partials / _fwd_partials_bits /
+ *     detection metric ssl4gie_det_map_{workspace_bytes,match,order,accumulate}, and the Faster R-CNN head entry points ssl4gie_nms_{workspace_bytes,segments} /
+ *     ssl4gie_rpn_decode / ssl4gie_roi_decode / ssl4gie_roi_align_{fwd,bwd}; 11: before the sixteen BatchNorm entry points that had grown one per fusion (ssl4gie_bn_fwd / _fwd_partials / _fwd_partials_bits /
  *     _coef_partials / _coef_stats / _apply_bits, _stats / _stats_partials, _bwd / _bwd_xmask / _bwd_bits, _bwd_reduce / _reduce_xmask / _reduce_bits,
  *     _bwd_apply / _apply_xmask) were REPLACED by five with a source and a mask kind — the same launches, new signatures; 10: before the diagnostics entry point that read the 256x256 NT kernel's in-kernel
  *     time stamps was REMOVED with the debug build of the library — the one removal in this history; 9: before ssl4gie_infonce_{workspace_bytes,loss} / ssl4gie_cross_entropy{_workspace_bytes,} /
@@ -973,6 +974,63 @@ int ssl4gie_det_map_accumulate(const unsigned* sorted_idx, const int* seg_off, c
                                const unsigned long long* matched, const unsigned long long* ignored, const int* npig,
                                const int* present, const int* flag, long long n_det, const double* rec_thresholds,
                                double* stats, double* out64, float* out32, int* outi, void* stream);
+
+/* ---------------------------------------------------------------- Faster R-CNN heads: NMS, box decode, RoIAlign (joined ABI 12)
+ * Object_detection/train_detection.py:244-250 and Object_detection/eval_detection.py build
+ * torchvision.models.detection.faster_rcnn.FasterRCNN(backbone, num_classes=...); its proposal and detection stages run
+ * torchvision's C++ / CUDA ops.  The rules (torchvision 0.10's published source) are written out in
+ * ssl4gie_amd/Models/detection.py; csrc/det_head_ops.hip has the kernels, built with -ffp-contract=off.
+ *
+ * nms_segments  replaces torchvision.ops.nms / batched_nms (rpn.py filter_proposals, roi_heads.py postprocess_detections).
+ *               boxes fp32 [n, 4] xyxy, 16-byte aligned, sorted by descending score inside every segment (ties: lower
+ *               original index first); segment s owns [seg_off[s], seg_off[s + 1]) (int32 [n_seg + 1] on the device);
+ *               valid uint8 [n] or NULL: a box with valid == 0 is never kept and suppresses nothing.  In fp32, inter =
+ *               max(0, xx2 - xx1) * max(0, yy2 - yy1), iou = inter / (area_i + area_j - inter); box j is dropped when
+ *               iou > thr against a kept box i earlier in its segment.  keep_rank int32 [n]: the position of a kept box
+ *               among the kept boxes of its segment, -1 for a dropped one or one outside every segment; count int32
+ *               [n_seg].  max_seg: an upper bound of the segment sizes known on the host, <= 4096; of a longer segment
+ *               only the first max_seg boxes take part.  Nothing is read through offsets that are not ascending or leave
+ *               [0, n] (count 0).  workspace: 8-byte aligned, ssl4gie_nms_workspace_bytes(n, max_seg) bytes (a 64-bit word per box and
+ *               64 boxes of max_seg; 0 for n <= 0, n > SSL4GIE_NMS_MAX_TOTAL or max_seg outside [1, 4096]).  No host round trip: torchvision's CUDA nms sweeps its mask on the host.
+ * rpn_decode    replaces, for the top-k candidates of every (image, level), AnchorGenerator + BoxCoder.decode_single
+ *               (weights 1) + clip_boxes_to_image + remove_small_boxes + sigmoid + the score test of
+ *               RegionProposalNetwork.filter_proposals.  head / grids / k_off / base_anchors are HOST arrays: head[l] the
+ *               device pointer of level l's fp32 head output [B * grid * grid, ld] (columns [0, A) objectness logits,
+ *               [A + 4 a, A + 4 a + 4) the deltas of anchor a), grids[l] its side, candidates [k_off[l], k_off[l + 1]) of
+ *               an image belong to level l, base_anchors [L, A, 4] the level's base anchors (round([-w, -h, w, h] / 2));
+ *               the anchor of flat index (y * grid + x) * A + a is base + (x, y, x, y) * (F / grid).  topk_idx int64
+ *               [B, k_off[L]]: flat indices inside the level (one outside gives a zero box, valid 0).  Outputs boxes fp32
+ *               [B * k_off[L], 4], scores fp32 (sigmoid), valid uint8 = w >= min_size && h >= min_size && score >=
+ *               score_thresh.  dw, dh are clamped at log(1000 / 16); boxes are clamped to [0, F]^2.
+ * roi_decode    replaces RoIHeads.postprocess_detections up to the NMS: proposals fp32 [K, 4], logits rows of C at
+ *               ld_logits, deltas rows of 4 C at ld_deltas, weights (wx, wy, ww, wh); boxes fp32 [K, C - 1, 4], scores
+ *               fp32 [K, C - 1] (row softmax, background column 0 dropped), valid uint8 [K, C - 1].
+ * roi_align     replaces MultiScaleRoIAlign(["0", "1", "2", "3"], 7, 2) (aligned=False, sampling_ratio 2) and its
+ *               backward.  maps / map_hw / scales are HOST arrays of the four levels: device pointers of channels-last
+ *               fp32 maps [B, H, W, C], (H, W) pairs, spatial scales.  rois fp32 [K, 4] in image coordinates, roi_batch
+ *               int32 [K] (a RoI with an image index outside [0, B) gives zeros / adds nothing).  Level per RoI on the
+ *               device: floor(4 + log2(sqrt(area) / 224) + 1e-6) clamped to [2, 5]; levels int32 [K] (0 .. 3) or NULL.
+ *               fwd writes [K, C * 49] in (c, ph, pw) order in out_dtype.  bwd ADDS into dmaps (zeroed by the caller)
+ *               with float atomics: not bitwise reproducible.  C: a multiple of 64, and of 256 above 256.
+ * SSL4GIE_EARG: a null pointer, a size <= 0 or above the caps, a misaligned pointer. */
+#define SSL4GIE_NMS_MAX_PER_SEGMENT 4096
+#define SSL4GIE_NMS_MAX_TOTAL (1 << 24)
+#define SSL4GIE_RPN_MAX_LEVELS 8
+#define SSL4GIE_RPN_MAX_ANCHORS 3
+size_t ssl4gie_nms_workspace_bytes(long long n, int max_seg);
+int ssl4gie_nms_segments(const float* boxes, const unsigned char* valid, const int* seg_off, int n_seg, long long n,
+                         int max_seg, float thr, int* keep_rank, int* count, void* workspace, void* stream);
+int ssl4gie_rpn_decode(const float* const* head, const int* grids, const int* k_off, const float* base_anchors, int L,
+                       int A, int ld, const long long* topk_idx, int B, int F, float min_size, float score_thresh,
+                       float* boxes, float* scores, unsigned char* valid, void* stream);
+int ssl4gie_roi_decode(const float* proposals, const float* logits, int ld_logits, const float* deltas, int ld_deltas,
+                       int K, int C, float wx, float wy, float ww, float wh, float W, float H, float min_size,
+                       float score_thresh, float* boxes, float* scores, unsigned char* valid, void* stream);
+int ssl4gie_roi_align_fwd(const float* const* maps, const int* map_hw, const float* scales, int B, int C,
+                          const float* rois, const int* roi_batch, int K, void* out, int out_dtype, int* levels,
+                          void* stream);
+int ssl4gie_roi_align_bwd(float* const* dmaps, const int* map_hw, const float* scales, int B, int C, const float* rois,
+                          const int* roi_batch, int K, const void* dy, int dy_dtype, void* stream);
 
 /* ---------------------------------------------------------------- direct xGMI gradient all-reduce
  * replaces the NCCL bucket all-reduce of DistributedDataParallel (Models/mae/main_pretrain.py:175,

@@ -24,6 +24,7 @@ BN_FROM_X, BN_FROM_PARTIALS, BN_FROM_STATS, BN_FROM_COEF = range(4)   # ssl4gie_
 FILTER_BILINEAR, FILTER_BICUBIC = 0, 1                                # ssl4gie_view_sample_u8: resampling filter
 TGT_U8, TGT_U16, TGT_F32 = range(3)                                   # ssl4gie_paired_warp: element type of the target bank
 DET_MAP_MAX_PER_IMAGE, DET_MAP_CLASSES, DET_MAP_CHUNK = 1024, 256, 256   # ssl4gie_det_map_*: the caps and the scan step
+NMS_MAX_PER_SEGMENT = 4096                                            # ssl4gie_nms_segments: 64 lanes x 64 bits
 PRED_I64 = 2                                                          # ssl4gie_confusion_update: int64 predictions instead of logits
 BN_MASK_NONE, BN_MASK_Y, BN_MASK_X, BN_MASK_BITS = range(4)           # backward: source of the ReLU mask
 
@@ -207,6 +208,14 @@ PROTOTYPES = {
     "ssl4gie_det_map_order": (i32, [vp, vp, vp, i64, vp, vp, vp, vp]),
     "ssl4gie_det_map_accumulate": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, i64, C.POINTER(C.c_double), vp, vp, vp, vp,
                                          vp]),
+    "ssl4gie_nms_workspace_bytes": (sz, [i64, i32]),
+    "ssl4gie_nms_segments": (i32, [vp, vp, vp, i32, i64, i32, f32, vp, vp, vp, vp]),
+    "ssl4gie_rpn_decode": (i32, [C.POINTER(vp), C.POINTER(i32), C.POINTER(i32), C.POINTER(f32), i32, i32, i32, vp, i32,
+                                 i32, f32, f32, vp, vp, vp, vp]),
+    "ssl4gie_roi_decode": (i32, [vp, vp, i32, vp, i32, i32, i32, f32, f32, f32, f32, f32, f32, f32, f32, vp, vp, vp, vp]),
+    "ssl4gie_roi_align_fwd": (i32, [C.POINTER(vp), C.POINTER(i32), C.POINTER(f32), i32, i32, vp, vp, i32, vp, i32, vp,
+                                    vp]),
+    "ssl4gie_roi_align_bwd": (i32, [C.POINTER(vp), C.POINTER(i32), C.POINTER(f32), i32, i32, vp, vp, i32, vp, i32, vp]),
     "ssl4gie_allreduce_direct_blob_bytes": (sz, []),
     "ssl4gie_allreduce_direct_init": (i32, [i32, i32, sz, vp, C.POINTER(vp)]),
     "ssl4gie_allreduce_direct_connect": (i32, [vp, vp]),

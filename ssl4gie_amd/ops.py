@@ -1805,3 +1805,150 @@ def det_map_accumulate(sorted_idx, seg_off, rank, matched, ignored, npig, presen
                                                       ptr(present), ptr(flag), N, rec, ptr(stats), ptr(out64),
                                                       ptr(out32), ptr(outi), stream()), "det_map_accumulate")
     return stats, out64, out32, outi
+
+
+# ------------------------------------------------------------------ Faster R-CNN heads (csrc/det_head_ops.hip)
+def nms_segments(boxes, seg_off, thr, valid=None, max_seg=None):
+    """Greedy NMS inside every segment without a host round trip.  boxes fp32 [n, 4] xyxy sorted by descending score
+    within each segment, seg_off int32 [S + 1] on the device, valid uint8 [n] or None.  max_seg: an upper bound of the
+    segment sizes known on the host (at most 4096); None reads the offsets back once to find it.  Returns keep_rank
+    int32 [n] (position among the kept boxes of the segment, -1 for a dropped box) and count int32 [S]."""
+    if max_seg is None:
+        so = seg_off.detach().cpu()
+        max_seg = int((so[1:] - so[:-1]).max()) if so.numel() > 1 else 0
+    if max_seg > _lib.NMS_MAX_PER_SEGMENT:
+        raise ValueError(f"nms_segments: {max_seg} boxes in a segment, the cap is {_lib.NMS_MAX_PER_SEGMENT}")
+    _dev(boxes, seg_off, valid)
+    _f32(boxes)
+    _same_device(boxes, seg_off, valid)
+    n, S = boxes.shape[0], seg_off.numel() - 1
+    if boxes.dim() != 2 or boxes.shape[1] != 4 or seg_off.dtype != torch.int32 or seg_off.dim() != 1 or S < 1:
+        raise ValueError("nms_segments needs boxes float32 [n, 4] and seg_off int32 [S + 1], S >= 1")
+    if valid is not None and (valid.dtype != torch.uint8 or tuple(valid.shape) != (n,)):
+        raise ValueError(f"valid must be uint8 [{n}]")
+    keep_rank = torch.empty(n, dtype=torch.int32, device=boxes.device)
+    count = torch.zeros(S, dtype=torch.int32, device=boxes.device)
+    if n == 0 or max_seg <= 0:
+        return keep_rank.fill_(-1), count
+    L = _lib.load()
+    nb = L.ssl4gie_nms_workspace_bytes(n, int(max_seg))
+    if nb == 0:
+        raise ValueError(f"nms_segments: invalid number of boxes {n}")
+    ws = torch.empty(nb, dtype=torch.uint8, device=boxes.device)
+    _lib.check(L.ssl4gie_nms_segments(ptr(boxes), ptr(valid), ptr(seg_off), S, n, int(max_seg), float(thr),
+                                      ptr(keep_rank), ptr(count), ptr(ws), stream()), "nms_segments")
+    return keep_rank, count
+
+
+def rpn_decode(heads, grids, k_off, base_anchors, topk_idx, F, min_size, score_thresh):
+    """The top-k candidates of every (image, level) decoded, clipped and flagged in one launch.  heads: the fp32 head
+    outputs [B * g * g, ld] of the levels (columns [0, A) logits, then A x 4 deltas), grids their sides, k_off the
+    candidate ranges of the levels (Python ints, k_off[0] == 0), base_anchors fp32 [L, A, 4] (host), topk_idx int64
+    [B, k_off[-1]].  Returns boxes fp32 [B, Ktot, 4], scores fp32 [B, Ktot], valid uint8 [B, Ktot]."""
+    _dev(topk_idx, *heads)
+    _f32(*heads)
+    _same_device(topk_idx, *heads)
+    Ln = len(heads)
+    base = torch.as_tensor(base_anchors, dtype=torch.float32).cpu().contiguous()
+    A = base.shape[1]
+    ld = heads[0].shape[1]
+    B, ktot = topk_idx.shape
+    if topk_idx.dtype != torch.int64 or len(grids) != Ln or len(k_off) != Ln + 1 or tuple(base.shape) != (Ln, A, 4) or \
+            ktot != k_off[-1]:
+        raise ValueError("rpn_decode: inconsistent level description")
+    for h, g in zip(heads, grids):
+        if h.dim() != 2 or tuple(h.shape) != (B * g * g, ld):
+            raise ValueError(f"rpn_decode: a head output must be [{B * g * g}, {ld}], got {tuple(h.shape)}")
+    dev = topk_idx.device
+    boxes = torch.empty(B, ktot, 4, dtype=torch.float32, device=dev)
+    scores = torch.empty(B, ktot, dtype=torch.float32, device=dev)
+    valid = torch.empty(B, ktot, dtype=torch.uint8, device=dev)
+    if B * ktot:
+        hp = (_lib.vp * Ln)(*[h.data_ptr() for h in heads])
+        gp = (_lib.i32 * Ln)(*[int(g) for g in grids])
+        kp = (_lib.i32 * (Ln + 1))(*[int(k) for k in k_off])
+        bp = (_lib.f32 * (Ln * A * 4))(*base.view(-1).tolist())
+        _lib.check(_lib.load().ssl4gie_rpn_decode(hp, gp, kp, bp, Ln, A, ld, ptr(topk_idx), B, int(F), float(min_size),
+                                                  float(score_thresh), ptr(boxes), ptr(scores), ptr(valid), stream()),
+                   "rpn_decode")
+    return boxes, scores, valid
+
+
+def roi_decode(proposals, logits, deltas, weights, W, H, min_size, score_thresh):
+    """Per-class boxes of the detection stage: proposals fp32 [K, 4], logits fp32 [K, C] and deltas fp32 [K, 4 C] (row
+    views of one product are fine: unit stride inside a row).  Returns boxes fp32 [K, C - 1, 4], scores fp32 [K, C - 1]
+    (row softmax without the background column) and valid uint8 [K, C - 1]."""
+    for t in (proposals, logits, deltas):
+        if not t.is_cuda:
+            raise RuntimeError("ssl4gie_amd ops need tensors on the HIP device (no CPU fallback)")
+    _f32(proposals, logits, deltas)
+    _same_device(proposals, logits, deltas)
+    K, Cn = logits.shape
+    if not proposals.is_contiguous() or tuple(proposals.shape) != (K, 4) or tuple(deltas.shape) != (K, 4 * Cn) or \
+            Cn < 2 or logits.stride(1) != 1 or deltas.stride(1) != 1:
+        raise ValueError("roi_decode needs proposals [K, 4], logits [K, C], deltas [K, 4 C] with unit-stride rows")
+    dev = logits.device
+    boxes = torch.empty(K, Cn - 1, 4, dtype=torch.float32, device=dev)
+    scores = torch.empty(K, Cn - 1, dtype=torch.float32, device=dev)
+    valid = torch.empty(K, Cn - 1, dtype=torch.uint8, device=dev)
+    if K:
+        wx, wy, ww, wh = (float(w) for w in weights)
+        _lib.check(_lib.load().ssl4gie_roi_decode(ptr(proposals), ptr(logits), logits.stride(0), ptr(deltas),
+                                                  deltas.stride(0), K, Cn, wx, wy, ww, wh, float(W), float(H),
+                                                  float(min_size), float(score_thresh), ptr(boxes), ptr(scores),
+                                                  ptr(valid), stream()), "roi_decode")
+    return boxes, scores, valid
+
+
+def _roi_maps(maps, what):
+    """the four NCHW views of channels-last fp32 storage as (pointers, (H, W) pairs, B, C)"""
+    if len(maps) != 4:
+        raise ValueError(f"{what} needs the four pyramid maps")
+    B, Cn = maps[0].shape[:2]
+    for m in maps:
+        if not m.is_cuda:
+            raise RuntimeError("ssl4gie_amd ops need tensors on the HIP device (no CPU fallback)")
+        if m.dtype != torch.float32 or m.dim() != 4 or m.shape[0] != B or m.shape[1] != Cn:
+            raise ValueError(f"{what}: a map must be float32 [B, C, H, W]")
+        if not m.permute(0, 2, 3, 1).is_contiguous():
+            raise RuntimeError(f"{what} needs channels-last maps (NCHW views of NHWC storage)")
+    if Cn % 64 or (Cn > 256 and Cn % 256):
+        raise ValueError(f"{what}: C = {Cn} must be a multiple of 64 (of 256 above 256)")
+    hp = (_lib.vp * 4)(*[m.data_ptr() for m in maps])
+    hw = (_lib.i32 * 8)(*[int(s) for m in maps for s in m.shape[2:]])
+    return hp, hw, B, Cn
+
+
+def roi_align_fwd(maps, scales, rois, roi_batch, out_dtype, want_levels=False):
+    """MultiScaleRoIAlign(7, 2) over the four maps: [K, C * 49] in (c, ph, pw) order in out_dtype (and the level of every
+    RoI, int32 [K], when asked).  rois fp32 [K, 4], roi_batch int32 [K]."""
+    hp, hw, B, Cn = _roi_maps(maps, "roi_align_fwd")
+    _dev(rois, roi_batch)
+    _f32(rois)
+    K = rois.shape[0]
+    if tuple(rois.shape) != (K, 4) or roi_batch.dtype != torch.int32 or tuple(roi_batch.shape) != (K,):
+        raise ValueError("roi_align_fwd needs rois float32 [K, 4] and roi_batch int32 [K]")
+    out = torch.empty(K, Cn * 49, dtype=out_dtype, device=rois.device)
+    levels = torch.empty(K, dtype=torch.int32, device=rois.device) if want_levels else None
+    if K:
+        sc = (_lib.f32 * 4)(*[float(s) for s in scales])
+        _lib.check(_lib.load().ssl4gie_roi_align_fwd(hp, hw, sc, B, Cn, ptr(rois), ptr(roi_batch), K, ptr(out),
+                                                     code(out_dtype), ptr(levels), stream()), "roi_align_fwd")
+    return (out, levels) if want_levels else out
+
+
+def roi_align_bwd(dmaps, scales, rois, roi_batch, dy):
+    """dmaps (zeroed fp32 channels-last maps) += the gradient of roi_align_fwd's output (float atomics: the sums are not
+    bitwise reproducible)"""
+    hp, hw, B, Cn = _roi_maps(dmaps, "roi_align_bwd")
+    _dev(rois, roi_batch, dy)
+    _f32(rois)
+    K = rois.shape[0]
+    if tuple(rois.shape) != (K, 4) or roi_batch.dtype != torch.int32 or tuple(roi_batch.shape) != (K,) or \
+            tuple(dy.shape) != (K, Cn * 49):
+        raise ValueError("roi_align_bwd needs rois float32 [K, 4], roi_batch int32 [K] and dy [K, C * 49]")
+    if K:
+        sc = (_lib.f32 * 4)(*[float(s) for s in scales])
+        _lib.check(_lib.load().ssl4gie_roi_align_bwd(hp, hw, sc, B, Cn, ptr(rois), ptr(roi_batch), K, ptr(dy),
+                                                     code(dy.dtype), stream()), "roi_align_bwd")
+    return dmaps
