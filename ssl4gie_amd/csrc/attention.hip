@@ -25,9 +25,10 @@
 int ssl4gie_internal_compute_cus();  // gemm.hip: CUs the persistent grids are sized for (ssl4gie_set_compute_cus)
 
 #include <math.h>
-#include <stdlib.h>
 #include <string.h>
+#include <array>
 #include <type_traits>
+#include <utility>
 
 // ------------------------------------------------------------------ LDS image helpers
 template <int HD> DEVI int kv_swz(int row) { return HD == 64 ? (row & 6) : ((row >> 1) & 2); }
@@ -109,15 +110,15 @@ DEVI u32x4 pair8(const f32x4 a, const f32x4 b) {
 }
 DEVI int pair8_col(int g) { return 16 * (g & 1) + 8 * (g >> 1); }  // the piece's first column inside the 32-column pair
 
-// three [n, HD] slices (Q, K, V of one head: same row stride, bases D apart) staged in one go: all
-// global loads of a thread are issued before the first LDS write, so the prologue costs one HBM
-// round trip instead of one per 16-byte chunk (the per-image loop above waits for each load before
-// it stores)
-template <int HD, int NPAD, int NTH>
-DEVI void stage_qkv(char* img0, char* img1, char* img2, const bf16_t* src0, const bf16_t* src1,
-                    const bf16_t* src2, long long rs, int n, int tid) {
-    constexpr int CPR = HD / 8, TOTAL = NPAD * CPR, IT = (TOTAL + NTH - 1) / NTH;
-    u32x4 v[3][IT];
+// NIMG = 2 or 3 [n, HD] slices (K, V and, for 3, Q of one head: same row stride) staged into consecutive images in one
+// go: all global loads of a thread are issued before the first LDS write, so the prologue costs one HBM round trip
+// instead of one per 16-byte chunk (the per-image loop above waits for each load before it stores)
+template <int HD, int NPAD, int NTH, int NIMG>
+DEVI void stage_imgs(char* img0, const bf16_t* src0, const bf16_t* src1, const bf16_t* src2, long long rs, int n,
+                     int tid) {
+    static_assert(NIMG == 2 || NIMG == 3, "K, V or K, V, Q");
+    constexpr int CPR = HD / 8, TOTAL = NPAD * CPR, IT = (TOTAL + NTH - 1) / NTH, IMG = NPAD * HD * 2;
+    u32x4 v[NIMG][IT];
 #pragma unroll
     for (int i = 0; i < IT; ++i) {
         const int idx = tid + i * NTH, row = idx / CPR, c = idx % CPR;
@@ -125,41 +126,27 @@ DEVI void stage_qkv(char* img0, char* img1, char* img2, const bf16_t* src0, cons
         const size_t off = (size_t)row * rs + c * 8;
         v[0][i] = ok ? *(const u32x4*)(src0 + off) : u32x4{0, 0, 0, 0};
         v[1][i] = ok ? *(const u32x4*)(src1 + off) : u32x4{0, 0, 0, 0};
-        v[2][i] = ok ? *(const u32x4*)(src2 + off) : u32x4{0, 0, 0, 0};
+        if constexpr (NIMG == 3) v[2][i] = ok ? *(const u32x4*)(src2 + off) : u32x4{0, 0, 0, 0};
     }
 #pragma unroll
     for (int i = 0; i < IT; ++i) {
         const int idx = tid + i * NTH, row = idx / CPR, c = idx % CPR;
         if (idx < TOTAL) {
             *(u32x4*)(img0 + img_off<HD>(row, c)) = v[0][i];
-            *(u32x4*)(img1 + img_off<HD>(row, c)) = v[1][i];
-            *(u32x4*)(img2 + img_off<HD>(row, c)) = v[2][i];
+            *(u32x4*)(img0 + IMG + img_off<HD>(row, c)) = v[1][i];
+            if constexpr (NIMG == 3) *(u32x4*)(img0 + 2 * IMG + img_off<HD>(row, c)) = v[2][i];
         }
     }
 }
-
-// two slices (K, V) staged the same way
-template <int HD, int NPAD, int NTH>
-DEVI void stage_kv(char* img0, char* img1, const bf16_t* src0, const bf16_t* src1, long long rs, int n,
-                   int tid) {
-    constexpr int CPR = HD / 8, TOTAL = NPAD * CPR, IT = (TOTAL + NTH - 1) / NTH;
-    u32x4 v[2][IT];
+// sum of the products of two 16-byte chunks of bf16 values, in fp32 (a thread's share of delta = sum_d dO[q, d] O[q, d])
+DEVI float dot_bf16x8(const u32x4 a, const u32x4 b) {
+    float dot = 0.f;
 #pragma unroll
-    for (int i = 0; i < IT; ++i) {
-        const int idx = tid + i * NTH, row = idx / CPR, c = idx % CPR;
-        const bool ok = idx < TOTAL && row < n;
-        const size_t off = (size_t)row * rs + c * 8;
-        v[0][i] = ok ? *(const u32x4*)(src0 + off) : u32x4{0, 0, 0, 0};
-        v[1][i] = ok ? *(const u32x4*)(src1 + off) : u32x4{0, 0, 0, 0};
+    for (int j = 0; j < 4; ++j) {
+        dot += __uint_as_float(a[j] << 16) * __uint_as_float(b[j] << 16);
+        dot += __uint_as_float(a[j] & 0xffff0000u) * __uint_as_float(b[j] & 0xffff0000u);
     }
-#pragma unroll
-    for (int i = 0; i < IT; ++i) {
-        const int idx = tid + i * NTH, row = idx / CPR, c = idx % CPR;
-        if (idx < TOTAL) {
-            *(u32x4*)(img0 + img_off<HD>(row, c)) = v[0][i];
-            *(u32x4*)(img1 + img_off<HD>(row, c)) = v[1][i];
-        }
-    }
+    return dot;
 }
 
 // ------------------------------------------------------------------ forward
@@ -177,11 +164,12 @@ template <int HD, int NKT> struct AttnFwdQG { static constexpr bool value = HD =
 // (profiles/r04dd, same box): the hd-32 forward (N = 197: 60 -> 57 us, N = 208: 58.5 -> 53) and the hd-64
 // backward (N = 197: 286 -> 271 us); the hd-64 forward variant spills and the hd-32 backward does not move
 // (159 us either way: it follows the bytes, not the tile count), so those keep the plain kernels.
-template <int HD, int NKT, int WAVES, bool HT>
-__global__ __launch_bounds__(64 * WAVES, (WAVES == 8 ? 1 : (HD == 32 && NKT <= 14 ? 3 : 2))) void attn_fwd_bf16_kernel(
+constexpr int ATTN_FWD_WAVES = 4;
+template <int HD, int NKT, bool HT>
+__global__ __launch_bounds__(64 * ATTN_FWD_WAVES, (HD == 32 && NKT <= 14 ? 3 : 2)) void attn_fwd_bf16_kernel(
     const bf16_t* __restrict__ qkv, bf16_t* __restrict__ out, float* __restrict__ lse, int N, int H,
     float scale) {
-    constexpr int NPAD = NKT * 16, RB = HD * 2, KS = HD / 32, DT = HD / 16;
+    constexpr int NPAD = NKT * 16, RB = HD * 2, KS = HD / 32, DT = HD / 16, WAVES = ATTN_FWD_WAVES;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     char* Kimg = smem;
     char* Vimg = smem + NPAD * RB;
@@ -195,8 +183,7 @@ __global__ __launch_bounds__(64 * WAVES, (WAVES == 8 ? 1 : (HD == 32 && NKT <= 1
     const long long rs = 3LL * D;
     const bf16_t* qb = qkv + (size_t)b * N * rs + h * HD;
     constexpr bool QG = AttnFwdQG<HD, NKT>::value;
-    if (QG) stage_kv<HD, NPAD, 64 * WAVES>(Kimg, Vimg, qb + D, qb + 2 * D, rs, N, tid);
-    else stage_qkv<HD, NPAD, 64 * WAVES>(Kimg, Vimg, Qimg, qb + D, qb + 2 * D, qb, rs, N, tid);
+    stage_imgs<HD, NPAD, 64 * WAVES, QG ? 2 : 3>(smem, qb + D, qb + 2 * D, qb, rs, N, tid);  // K, V (, Q) images
     // QG: this lane's query fragment of tile qt (rows past N repeat the last one; never stored)
     auto load_q = [&](int qt, bf16x8 (&dst)[KS]) {
         int row = qt * 16 + (lane & 15);
@@ -545,10 +532,11 @@ DEVI void attn_bwd_phases(char* smem, bf16_t* __restrict__ dqb, const int N, con
 
 // HT as in the forward kernel: the last pair of key tiles (phase A) / query tiles (phase B) is a single tile
 template <int HD, int NKT, bool HT>
-__global__ __launch_bounds__(64 * AttnBwdWaves<NKT>::value, (AttnBwdU<HD, NKT>::value == 2 ? 2 : 4)) void attn_bwd_bf16_kernel(
+__global__ __launch_bounds__(64 * AttnBwdWaves<NKT>::value, 4) void attn_bwd_bf16_kernel(
     const bf16_t* __restrict__ qkv, const bf16_t* __restrict__ out,
     const bf16_t* __restrict__ dout, const float* __restrict__ lse, bf16_t* __restrict__ dqkv,
     int N, int H, float scale) {
+    static_assert(AttnBwdU<HD, NKT>::value == 1, "two tiles per wave: the persistent kernel below");
     constexpr int NPAD = NKT * 16, RB = HD * 2, CPR = HD / 8;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     char* Kimg = smem;
@@ -600,12 +588,7 @@ __global__ __launch_bounds__(64 * AttnBwdWaves<NKT>::value, (AttnBwdU<HD, NKT>::
                 *(u32x4*)(Kimg + img_off<HD>(row, ch)) = kk[i];
                 *(u32x4*)(Vimg + img_off<HD>(row, ch)) = vk[i];
                 *(u32x4*)(Qimg + img_off<HD>(row, ch)) = qq[i];
-                float dot = 0.f;
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    dot += __uint_as_float(vv[i][j] << 16) * __uint_as_float(oo[i][j] << 16);
-                    dot += __uint_as_float(vv[i][j] & 0xffff0000u) * __uint_as_float(oo[i][j] & 0xffff0000u);
-                }
+                float dot = dot_bf16x8(vv[i], oo[i]);
                 *(u32x4*)(Oimg + img_off<HD>(row, ch)) = vv[i];
 #pragma unroll
                 for (int o = CPR / 2; o > 0; o >>= 1) dot += __shfl_xor(dot, o, 64);  // the row's CPR lanes
@@ -714,12 +697,7 @@ __global__ __launch_bounds__(64 * AttnBwdWaves<NKT>::value, 2) void attn_bwd_pf_
             const int idx = tid + i * NTH, row = idx / CPR, ch = idx % CPR;
             if (idx < TOTAL) {
                 *(u32x4*)(Qimg + img_off<HD>(row, ch)) = ra[i];
-                float dot = 0.f;
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    dot += __uint_as_float(rb[i][j] << 16) * __uint_as_float(rc[i][j] << 16);
-                    dot += __uint_as_float(rb[i][j] & 0xffff0000u) * __uint_as_float(rc[i][j] & 0xffff0000u);
-                }
+                float dot = dot_bf16x8(rb[i], rc[i]);
                 *(u32x4*)(Oimg + img_off<HD>(row, ch)) = rb[i];
 #pragma unroll
                 for (int o = CPR / 2; o > 0; o >>= 1) dot += __shfl_xor(dot, o, 64);  // the row's CPR lanes
@@ -1162,78 +1140,98 @@ static ssl4gie_gemm_desc bdesc(int M, int N, int K, int B, int H) {
     return d;
 }
 
-// SSL4GIE_ATTN_STREAM_MIN: smallest N that takes the streaming kernels.  Default 257: measured
-// (profiles/r01q_attn_stream_vs_whole.log), the whole-head-in-LDS kernels win up to N = 256 —
-// at N = 197 the 128-row blocks pad keys to 256 and queries to 256, K/V are staged twice per head
-// and the backward recomputes the scores in two kernels.  Lower values are for A/B measurements;
-// the streaming kernels handle any N (MASK variant) for hd 32 / 64.
-static int attn_stream_min() {
-    static int v = -1;
-    if (v < 0) {
-        const char* e = getenv("SSL4GIE_ATTN_STREAM_MIN");
-        v = e ? atoi(e) : 257;
-        if (v < 1) v = 1;
-    }
-    return v;
-}
-static bool attn_long(int N, int hd) {
-    return (hd == 64 || hd == 32) && (N > 256 || N >= attn_stream_min());
+// ---- bf16 dispatch: one rule from (N, hd) to the kernels that serve the shape.  ssl4gie_attn_fwd, ssl4gie_attn_bwd and
+// ssl4gie_attn_workspace_bytes read this key, and the tables below instantiate exactly the variants it can name.
+struct AttnKey {
+    bool stream;      // the streaming kernels (else the whole-head ones)
+    bool mask;        // streaming: N is no multiple of the 128-row block
+    int nkt;          // whole-head: 16-key tiles of an LDS image
+    bool fwd_ht;      // whole-head: the forward / backward kernel is the half-tail variant
+    bool bwd_ht;
+    bool persistent;  // whole-head backward: the persistent prefetching kernel
+};
+// The whole-head-in-LDS kernels serve N <= 256 and win there (profiles/r01q_attn_stream_vs_whole.log): at N = 197 the
+// streaming kernels' 128-row blocks pad keys to 256 and queries to 256, K / V are staged twice per head and the backward
+// recomputes the scores in two kernels.  The streaming kernels take every longer sequence (MASK variant: any N).
+// Whole-head kernels exist for every even number of 16-key tiles, 16 (NKT - 2) < N <= 16 NKT, so that only the last
+// tile pair can hold padded keys (the kernels rely on it).  Half tail where it was measured to pay (see AttnFwdQG's
+// neighbour above): the hd-32 forward (the hd-64 variant spills) and the hd-64 backward (hd 32: no gain).
+constexpr int ATTN_WHOLE_MAX_N = 256;
+constexpr AttnKey attn_key(int N, int hd) {
+    if (N > ATTN_WHOLE_MAX_N) return AttnKey{true, N % LONG_BLK != 0, 0, false, false, false};
+    const int nkt = 2 * ((N + 31) >> 5);
+    const bool half = N <= 16 * (nkt - 1);
+    return AttnKey{false, false, nkt, half && hd == 32, half && hd == 64, hd == 64 && nkt >= 10};
 }
 
 extern "C" size_t ssl4gie_attn_workspace_bytes(int dtype, int B, int N, int H, int hd) {
     if (dtype == SSL4GIE_BF16)  // long sequences: delta[b, h, q] of the backward pass
-        return attn_long(N, hd) ? (size_t)B * H * N * sizeof(float) : 0;
+        return ((hd == 64 || hd == 32) && attn_key(N, hd).stream) ? (size_t)B * H * N * sizeof(float) : 0;
     return (size_t)2 * B * H * N * N * sizeof(float);  // scores + dscores
 }
 
-// SSL4GIE_ATTN_HALF_TAIL=0: the kernels without the half-tail variants (A/B)
-static bool attn_half_tail() {
-    static int v = -1;
-    if (v < 0) { const char* e = getenv("SSL4GIE_ATTN_HALF_TAIL"); v = e ? atoi(e) != 0 : 1; }
-    return v != 0;
+// Raise the dynamic-LDS limit of a kernel that needs more than the 64 KiB every kernel may ask for, once.  The limit is
+// a pure function of the kernel and the (single) architecture, so the benign race of two host threads setting it twice
+// writes the same value.
+template <auto KFN, int BYTES>
+static hipError_t attn_lds_limit() {
+    if constexpr (BYTES > 65536) {
+        static bool done = false;
+        if (!done) {
+            const hipError_t e = hipFuncSetAttribute((const void*)KFN, hipFuncAttributeMaxDynamicSharedMemorySize, BYTES);
+            if (e != hipSuccess) return e;
+            done = true;
+        }
+    }
+    return hipSuccess;
 }
+
+using AttnFwdFn = int (*)(const void* qkv, void* out, float* lse, int B, int N, int H, float scale, hipStream_t st);
+using AttnBwdFn = int (*)(const void* qkv, const void* out, const void* dout, const float* lse, void* dqkv, int B, int N,
+                          int H, float scale, hipStream_t st);
+
 template <int HD, int NKT, bool HT>
-static int launch_fwd(const void* qkv, void* out, float* lse, int B, int N, int H, float scale,
-                      hipStream_t st) {
-    constexpr bool QG = AttnFwdQG<HD, NKT>::value;
-    const size_t lds = (size_t)(QG ? 2 : 3) * NKT * 16 * HD * 2;
-    constexpr int WAVES = (!QG && 3 * NKT * 16 * HD * 2 > 80 * 1024) ? 8 : 4;
-    auto k = attn_fwd_bf16_kernel<HD, NKT, WAVES, HT>;
-    if (lds > 65536)
-        HIP_RET(hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+static int launch_fwd(const void* qkv, void* out, float* lse, int B, int N, int H, float scale, hipStream_t st) {
+    constexpr int LDS = (AttnFwdQG<HD, NKT>::value ? 2 : 3) * NKT * 16 * HD * 2;
+    constexpr auto k = attn_fwd_bf16_kernel<HD, NKT, HT>;
+    HIP_RET((attn_lds_limit<k, LDS>()));
     ProfScope prof(PROF_ATTN_FWD, 4.0 * B * H * (double)N * N * HD, st);
-    hipLaunchKernelGGL(k, dim3(B * H), dim3(64 * WAVES), lds, st, (const bf16_t*)qkv, (bf16_t*)out, lse,
-                       N, H, scale);
+    hipLaunchKernelGGL(k, dim3(B * H), dim3(64 * ATTN_FWD_WAVES), LDS, st, (const bf16_t*)qkv, (bf16_t*)out, lse, N, H,
+                       scale);
     LAUNCH_CHECK();
     return 0;
 }
-static bool attn_prefetch() {  // SSL4GIE_ATTN_PREFETCH=0: the one-head-per-workgroup kernel everywhere (A/B; same results)
-    static int on = -1;
-    if (on < 0) { const char* e = getenv("SSL4GIE_ATTN_PREFETCH"); on = (e && e[0] == '0') ? 0 : 1; }
-    return on != 0;
+template <int HD, int NKT, bool HT>
+static int launch_bwd(const void* qkv, const void* out, const void* dout, const float* lse, void* dqkv, int B, int N,
+                      int H, float scale, hipStream_t st) {
+    constexpr int LDS = 4 * NKT * 16 * HD * 2 + 2 * NKT * 16 * (int)sizeof(float);
+    constexpr auto k = attn_bwd_bf16_kernel<HD, NKT, HT>;
+    HIP_RET((attn_lds_limit<k, LDS>()));
+    ProfScope prof(PROF_ATTN_BWD, 10.0 * B * H * (double)N * N * HD, st);
+    hipLaunchKernelGGL(k, dim3(B * H), dim3(64 * AttnBwdWaves<NKT>::value), LDS, st, (const bf16_t*)qkv,
+                       (const bf16_t*)out, (const bf16_t*)dout, lse, (bf16_t*)dqkv, N, H, scale);
+    LAUNCH_CHECK();
+    return 0;
 }
 template <int HD, int NKT, bool HT>
-static int launch_bwd(const void* qkv, const void* out, const void* dout, const float* lse,
-                      void* dqkv, int B, int N, int H, float scale, hipStream_t st);
-template <int HD, int NKT, bool HT>
-static int launch_bwd_pf(const void* qkv, const void* out, const void* dout, const float* lse,
-                         void* dqkv, int B, int N, int H, float scale, hipStream_t st) {
+static int launch_bwd_pf(const void* qkv, const void* out, const void* dout, const float* lse, void* dqkv, int B, int N,
+                         int H, float scale, hipStream_t st) {
     constexpr int W = AttnBwdWaves<NKT>::value;
-    const size_t lds = (size_t)4 * NKT * 16 * HD * 2 + 2 * NKT * 16 * sizeof(float);
-    auto k = attn_bwd_pf_bf16_kernel<HD, NKT, HT>;
-    // workgroups one CU holds at once: a pure function of the kernel and the (single) architecture, so the benign
-    // race of two host threads computing it twice writes the same value.  The persistent grid covers the
-    // CUs the compute kernels may use (ssl4gie_set_compute_cus: data-parallel runs keep a few for the
-    // communication kernels, which these long-lived workgroups would otherwise occupy).
+    constexpr int LDS = 4 * NKT * 16 * HD * 2 + 2 * NKT * 16 * (int)sizeof(float);
+    // every wave of the workgroup has a tile in both phases, so none misses the hooks' barriers: a bucket of NKT tiles
+    // holds more than 16 (NKT - 2) tokens, i.e. at least NKT - 1 query tiles
+    static_assert(NKT - 1 >= W, "a wave without a tile would miss the barriers of the prefetch hooks");
+    constexpr auto k = attn_bwd_pf_bf16_kernel<HD, NKT, HT>;
+    HIP_RET((attn_lds_limit<k, LDS>()));
+    // workgroups one CU holds at once, computed once per instantiation (the same benign race as attn_lds_limit's).  The
+    // persistent grid covers the CUs the compute kernels may use (ssl4gie_set_compute_cus: data-parallel runs keep a
+    // few for the communication kernels, which these long-lived workgroups would otherwise occupy).
     static int per_cu = 0;
     if (!per_cu) {
-        HIP_RET(hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
         int v = 0;
-        HIP_RET(hipOccupancyMaxActiveBlocksPerMultiprocessor(&v, (const void*)k, 64 * W, lds));
+        HIP_RET(hipOccupancyMaxActiveBlocksPerMultiprocessor(&v, (const void*)k, 64 * W, LDS));
         per_cu = v < 1 ? 1 : v;
     }
-    if (((N + 15) >> 4) < W)  // a wave without a tile would miss the hooks' barriers: the one-head kernel handles it
-        return launch_bwd<HD, NKT, HT>(qkv, out, dout, lse, dqkv, B, N, H, scale, st);
     const int slots = per_cu * ssl4gie_internal_compute_cus();
     const int heads = B * H;
     int grid = heads;
@@ -1242,24 +1240,83 @@ static int launch_bwd_pf(const void* qkv, const void* out, const void* dout, con
         grid = (heads + rounds - 1) / rounds;
     }
     ProfScope prof(PROF_ATTN_BWD, 10.0 * B * H * (double)N * N * HD, st);
-    hipLaunchKernelGGL(k, dim3(grid), dim3(64 * W), lds, st, (const bf16_t*)qkv, (const bf16_t*)out,
+    hipLaunchKernelGGL(k, dim3(grid), dim3(64 * W), LDS, st, (const bf16_t*)qkv, (const bf16_t*)out,
                        (const bf16_t*)dout, lse, (bf16_t*)dqkv, N, H, scale, heads);
     LAUNCH_CHECK();
     return 0;
 }
-template <int HD, int NKT, bool HT>
-static int launch_bwd(const void* qkv, const void* out, const void* dout, const float* lse,
-                      void* dqkv, int B, int N, int H, float scale, hipStream_t st) {
-    const size_t lds = (size_t)4 * NKT * 16 * HD * 2 + 2 * NKT * 16 * sizeof(float);
-    auto k = attn_bwd_bf16_kernel<HD, NKT, HT>;
-    if (lds > 65536)
-        HIP_RET(hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    ProfScope prof(PROF_ATTN_BWD, 10.0 * B * H * (double)N * N * HD, st);
-    hipLaunchKernelGGL(k, dim3(B * H), dim3(64 * AttnBwdWaves<NKT>::value), lds, st, (const bf16_t*)qkv,
-                       (const bf16_t*)out, (const bf16_t*)dout, lse, (bf16_t*)dqkv, N, H, scale);
+template <int HD, bool MASK>
+static int launch_long_fwd(const void* qkv, void* out, float* lse, int B, int N, int H, float scale, hipStream_t st) {
+    constexpr int LDS = 4 * LONG_BLK * HD * 2;
+    constexpr auto k = attn_long_fwd_kernel<HD, MASK>;
+    HIP_RET((attn_lds_limit<k, LDS>()));
+    ProfScope prof(PROF_ATTN_FWD, 4.0 * B * H * (double)N * N * HD, st);
+    hipLaunchKernelGGL(k, dim3((N + LONG_BLK - 1) / LONG_BLK, B * H), dim3(64 * LONG_WAVES), LDS, st,
+                       (const bf16_t*)qkv, (bf16_t*)out, lse, N, H, scale);
     LAUNCH_CHECK();
     return 0;
 }
+// streaming backward: delta[b, h, q] into the workspace, then the dQ and the dK / dV kernel
+template <int HD, bool MASK>
+static int launch_long_bwd(const void* qkv, const void* out, const void* dout, const float* lse, void* dqkv, float* delta,
+                           int B, int N, int H, float scale, hipStream_t st) {
+    const long long rows = (long long)B * N;
+    const long long items = rows * H * (HD / 8);
+    hipLaunchKernelGGL(attn_delta_kernel<HD>, dim3((unsigned)((items + 255) / 256)), dim3(256), 0, st,
+                       (const bf16_t*)out, (const bf16_t*)dout, delta, rows, N, H);
+    LAUNCH_CHECK();
+    constexpr int LDS_Q = 4 * LONG_BLK * HD * 2, LDS_KV = LDS_Q + 4 * LONG_BLK * (int)sizeof(float);
+    constexpr auto kq = attn_long_bwd_dq_kernel<HD, MASK>;
+    constexpr auto kkv = attn_long_bwd_dkv_kernel<HD, MASK>;
+    HIP_RET((attn_lds_limit<kq, LDS_Q>()));
+    HIP_RET((attn_lds_limit<kkv, LDS_KV>()));
+    ProfScope prof(PROF_ATTN_BWD, 10.0 * B * H * (double)N * N * HD, st);
+    const dim3 grid((N + LONG_BLK - 1) / LONG_BLK, B * H), block(64 * LONG_WAVES);
+    hipLaunchKernelGGL(kq, grid, block, LDS_Q, st, (const bf16_t*)qkv, (const bf16_t*)dout, lse, delta, (bf16_t*)dqkv, N,
+                       H, scale);
+    hipLaunchKernelGGL(kkv, grid, block, LDS_KV, st, (const bf16_t*)qkv, (const bf16_t*)dout, lse, delta, (bf16_t*)dqkv,
+                       N, H, scale);
+    LAUNCH_CHECK();
+    return 0;
+}
+
+// Tables.  Whole-head: index (hd 64, NKT / 2 - 1, HT); an entry exists where attn_key names it, which the key of the
+// entry's largest N (16 NKT, half tail: 16 (NKT - 1)) says.  Streaming: index [hd 64][MASK].
+constexpr int ATTN_WHOLE_KEYS = 2 * 8 * 2;
+constexpr int attn_whole_index(int hd, int nkt, bool ht) { return ((hd == 64 ? 8 : 0) + nkt / 2 - 1) * 2 + ht; }
+template <int I> struct AttnWhole {
+    static constexpr int HD = I / 16 ? 64 : 32, NKT = (I / 2 % 8 + 1) * 2;
+    static constexpr bool HT = I % 2 != 0;
+    static constexpr AttnKey key = attn_key(16 * (NKT - (HT ? 1 : 0)), HD);
+    static_assert(attn_whole_index(HD, NKT, HT) == I && !key.stream && key.nkt == NKT, "key <-> index");
+};
+template <int I>
+constexpr AttnFwdFn attn_fwd_entry() {
+    using E = AttnWhole<I>;
+    if constexpr (E::key.fwd_ht == E::HT) return &launch_fwd<E::HD, E::NKT, E::HT>;
+    else return nullptr;
+}
+template <int I>
+constexpr AttnBwdFn attn_bwd_entry() {
+    using E = AttnWhole<I>;
+    if constexpr (E::key.bwd_ht != E::HT) return nullptr;
+    else if constexpr (E::key.persistent) return &launch_bwd_pf<E::HD, E::NKT, E::HT>;
+    else return &launch_bwd<E::HD, E::NKT, E::HT>;
+}
+template <int... I>
+constexpr std::array<AttnFwdFn, sizeof...(I)> attn_fwd_table(std::integer_sequence<int, I...>) {
+    return {{attn_fwd_entry<I>()...}};
+}
+template <int... I>
+constexpr std::array<AttnBwdFn, sizeof...(I)> attn_bwd_table(std::integer_sequence<int, I...>) {
+    return {{attn_bwd_entry<I>()...}};
+}
+static constexpr auto g_attn_fwd = attn_fwd_table(std::make_integer_sequence<int, ATTN_WHOLE_KEYS>{});
+static constexpr auto g_attn_bwd = attn_bwd_table(std::make_integer_sequence<int, ATTN_WHOLE_KEYS>{});
+static constexpr AttnFwdFn g_attn_long_fwd[2][2] = {{&launch_long_fwd<32, false>, &launch_long_fwd<32, true>},
+                                                    {&launch_long_fwd<64, false>, &launch_long_fwd<64, true>}};
+static constexpr decltype(&launch_long_bwd<32, false>) g_attn_long_bwd[2][2] = {
+    {&launch_long_bwd<32, false>, &launch_long_bwd<32, true>}, {&launch_long_bwd<64, false>, &launch_long_bwd<64, true>}};
 
 extern "C" int ssl4gie_attn_fwd(const void* qkv, void* out, float* lse, int dtype, int B, int N,
                                 int H, int hd, void* workspace, void* stream) {
@@ -1269,49 +1326,11 @@ extern "C" int ssl4gie_attn_fwd(const void* qkv, void* out, float* lse, int dtyp
     const int D = H * hd;
     if (dtype == SSL4GIE_BF16) {
         REQUIRE(hd == 32 || hd == 64);
-        if (attn_long(N, hd)) {
-            const int lds = 4 * LONG_BLK * hd * 2;
-            const bool mask = N % LONG_BLK != 0;
-            const dim3 grid((N + LONG_BLK - 1) / LONG_BLK, B * H), block(64 * LONG_WAVES);
-            ProfScope prof(PROF_ATTN_FWD, 4.0 * B * H * (double)N * N * hd, st);
-#define LFWD(HD_, MASK_)                                                                           \
-    do {                                                                                           \
-        auto kfn = attn_long_fwd_kernel<HD_, MASK_>;                                               \
-        static bool attr = false;                                                                  \
-        if (!attr) {                                                                               \
-            HIP_RET(hipFuncSetAttribute((const void*)kfn,                                          \
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, 65536));      \
-            attr = true;                                                                           \
-        }                                                                                          \
-        hipLaunchKernelGGL(kfn, grid, block, lds, st, (const bf16_t*)qkv, (bf16_t*)out, lse, N, H, \
-                           scale);                                                                 \
-    } while (0)
-            if (hd == 64) { if (mask) LFWD(64, true); else LFWD(64, false); }
-            else { if (mask) LFWD(32, true); else LFWD(32, false); }
-#undef LFWD
-            LAUNCH_CHECK();
-            return 0;
-        }
-        REQUIRE(N <= 256);
-// the kernels are instantiated for every even number of 16-key tiles: 16 (NKT - 2) < N <= 16 NKT,
-// so that only the last tile pair can hold padded keys (the kernels rely on it)
-#define FWD_HT(HD_, NKT_)                                                                 \
-    return (HD_ == 32 && N <= 16 * (NKT_ - 1) && attn_half_tail()) /* hd 64: the variant spills */ \
-               ? launch_fwd<HD_, NKT_, HD_ == 32>(qkv, out, lse, B, N, H, scale, st)           \
-               : launch_fwd<HD_, NKT_, false>(qkv, out, lse, B, N, H, scale, st)
-#define FWD(HD_)                                                                          \
-    switch ((N + 31) >> 5) {                                                              \
-    case 1: FWD_HT(HD_, 2); \
-    case 2: FWD_HT(HD_, 4); \
-    case 3: FWD_HT(HD_, 6); \
-    case 4: FWD_HT(HD_, 8); \
-    case 5: FWD_HT(HD_, 10); \
-    case 6: FWD_HT(HD_, 12); \
-    case 7: FWD_HT(HD_, 14); \
-    default: FWD_HT(HD_, 16); \
-    }
-        if (hd == 64) { FWD(64) } else { FWD(32) }
-#undef FWD
+        const AttnKey k = attn_key(N, hd);
+        const AttnFwdFn fn =
+            k.stream ? g_attn_long_fwd[hd == 64][k.mask] : g_attn_fwd[attn_whole_index(hd, k.nkt, k.fwd_ht)];
+        REQUIRE(fn);
+        return fn(qkv, out, lse, B, N, H, scale, st);
     }
     REQUIRE(dtype == SSL4GIE_F32 && workspace);
     float* S = (float*)workspace;
@@ -1345,68 +1364,14 @@ extern "C" int ssl4gie_attn_bwd(const void* qkv, const void* out, const void* do
     const int D = H * hd;
     if (dtype == SSL4GIE_BF16) {
         REQUIRE(hd == 32 || hd == 64);
-        if (attn_long(N, hd)) {
+        const AttnKey k = attn_key(N, hd);
+        if (k.stream) {
             REQUIRE(workspace);
-            float* delta = (float*)workspace;
-            const long long rows = (long long)B * N;
-            const long long items = rows * H * (hd / 8);
-            const dim3 dgrid((unsigned)((items + 255) / 256));
-            if (hd == 64)
-                hipLaunchKernelGGL(attn_delta_kernel<64>, dgrid, dim3(256), 0, st, (const bf16_t*)out,
-                                   (const bf16_t*)dout, delta, rows, N, H);
-            else
-                hipLaunchKernelGGL(attn_delta_kernel<32>, dgrid, dim3(256), 0, st, (const bf16_t*)out,
-                                   (const bf16_t*)dout, delta, rows, N, H);
-            LAUNCH_CHECK();
-            const int lds_q = 4 * LONG_BLK * hd * 2, lds_kv = lds_q + 4 * LONG_BLK * (int)sizeof(float);
-            const bool mask = N % LONG_BLK != 0;
-            ProfScope prof(PROF_ATTN_BWD, 10.0 * B * H * (double)N * N * hd, st);
-            const dim3 grid((N + LONG_BLK - 1) / LONG_BLK, B * H), block(64 * LONG_WAVES);
-#define LBWD(HD_, MASK_)                                                                           \
-    do {                                                                                           \
-        auto kq = attn_long_bwd_dq_kernel<HD_, MASK_>;                                             \
-        auto kkv = attn_long_bwd_dkv_kernel<HD_, MASK_>;                                           \
-        static bool attr = false;                                                                  \
-        if (!attr) {                                                                               \
-            HIP_RET(hipFuncSetAttribute((const void*)kq,                                           \
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, 65536));      \
-            HIP_RET(hipFuncSetAttribute((const void*)kkv,                                          \
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, 65536 + 2048)); \
-            attr = true;                                                                           \
-        }                                                                                          \
-        hipLaunchKernelGGL(kq, grid, block, lds_q, st, (const bf16_t*)qkv, (const bf16_t*)dout,    \
-                           lse, delta, (bf16_t*)dqkv, N, H, scale);                                \
-        hipLaunchKernelGGL(kkv, grid, block, lds_kv, st, (const bf16_t*)qkv, (const bf16_t*)dout,  \
-                           lse, delta, (bf16_t*)dqkv, N, H, scale);                                \
-    } while (0)
-            if (hd == 64) { if (mask) LBWD(64, true); else LBWD(64, false); }
-            else { if (mask) LBWD(32, true); else LBWD(32, false); }
-#undef LBWD
-            LAUNCH_CHECK();
-            return 0;
+            return g_attn_long_bwd[hd == 64][k.mask](qkv, out, dout, lse, dqkv, (float*)workspace, B, N, H, scale, st);
         }
-        REQUIRE(N <= 256);
-#define BWD_HT(HD_, NKT_)                                                                          \
-    if (HD_ == 64 && NKT_ >= 10 && attn_prefetch()) /* one workgroup per CU: persistent + prefetch */ \
-        return (N <= 16 * (NKT_ - 1) && attn_half_tail())                                              \
-                   ? launch_bwd_pf<64, (NKT_ >= 10 ? NKT_ : 10), true>(qkv, out, dout, lse, dqkv, B, N, H, scale, st) \
-                   : launch_bwd_pf<64, (NKT_ >= 10 ? NKT_ : 10), false>(qkv, out, dout, lse, dqkv, B, N, H, scale, st);     \
-    return (HD_ == 64 && N <= 16 * (NKT_ - 1) && attn_half_tail()) /* hd 32: measured no gain */   \
-               ? launch_bwd<HD_, NKT_, HD_ == 64>(qkv, out, dout, lse, dqkv, B, N, H, scale, st)   \
-               : launch_bwd<HD_, NKT_, false>(qkv, out, dout, lse, dqkv, B, N, H, scale, st)
-#define BWD(HD_)                                                                                   \
-    switch ((N + 31) >> 5) {                                                                       \
-    case 1: BWD_HT(HD_, 2); \
-    case 2: BWD_HT(HD_, 4); \
-    case 3: BWD_HT(HD_, 6); \
-    case 4: BWD_HT(HD_, 8); \
-    case 5: BWD_HT(HD_, 10); \
-    case 6: BWD_HT(HD_, 12); \
-    case 7: BWD_HT(HD_, 14); \
-    default: BWD_HT(HD_, 16); \
-    }
-        if (hd == 64) { BWD(64) } else { BWD(32) }
-#undef BWD
+        const AttnBwdFn fn = g_attn_bwd[attn_whole_index(hd, k.nkt, k.bwd_ht)];
+        REQUIRE(fn);
+        return fn(qkv, out, dout, lse, dqkv, B, N, H, scale, st);
     }
     REQUIRE(dtype == SSL4GIE_F32 && workspace);
     float* P = (float*)workspace;

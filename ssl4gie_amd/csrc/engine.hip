@@ -103,16 +103,9 @@ SideStream* side_stream() {
     SideStream* ss = &per_dev[dev];
     if (!ss->s) {
         hipStream_t st = nullptr;
-        // SSL4GIE_WGRAD_PRIO=high|low: scheduling priority of the weight-gradient stream against the caller's
-        // (default: the same).  Measured on the MAE step (profiles/r04bs): see profiles/HISTORY.md section 5.
-        const char* pe = getenv("SSL4GIE_WGRAD_PRIO");
-        int least = 0, greatest = 0;
-        if (pe && hipDeviceGetStreamPriorityRange(&least, &greatest) == hipSuccess && least != greatest) {
-            const int prio = (pe[0] == 'h' || pe[0] == 'H') ? greatest : least;
-            if (hipStreamCreateWithPriority(&st, hipStreamNonBlocking, prio) != hipSuccess) return nullptr;
-        } else if (hipStreamCreateWithFlags(&st, hipStreamNonBlocking) != hipSuccess) {
-            return nullptr;
-        }
+        // the weight-gradient stream has the caller's scheduling priority: a higher and a lower one were measured on
+        // the MAE step (profiles/r04bs) and change nothing, see profiles/HISTORY.md
+        if (hipStreamCreateWithFlags(&st, hipStreamNonBlocking) != hipSuccess) return nullptr;
         for (int i = 0; i < 10; ++i) {
             if (hipEventCreateWithFlags(&ss->ev[i], hipEventDisableTiming) != hipSuccess) {
                 (void)hipStreamDestroy(st);
@@ -313,9 +306,7 @@ extern "C" int ssl4gie_block_bwd(const ssl4gie_block_dims* d, const ssl4gie_bloc
     // ---- LN2 (adds the residual gradient dx_out)
     // with a weight-gradient stream the second stage of both LayerNorm backward passes (the sum of the per-block
     // dgamma / dbeta partials: a 6-us launch the data-gradient chain would wait for, 40 per MAE step) runs there
-    static int ln_side_on = -1;  // SSL4GIE_LN_SIDE=0: the reductions stay on the caller's stream (A/B timing; same results)
-    if (ln_side_on < 0) { const char* e = getenv("SSL4GIE_LN_SIDE"); ln_side_on = (e && e[0] == '0') ? 0 : 1; }
-    const bool ln_side = ss != nullptr && ln_side_on;
+    const bool ln_side = ss != nullptr;
     RC(ssl4gie_layernorm_bwd(dh, dt, a->xmid, w->ln2_g, a->mean2, a->rstd2, dx_out, dxmid,
                              dt == SSL4GIE_F32 ? nullptr : dxmid_lp, dt, ln_side ? nullptr : g->ln2_g,
                              ln_side ? nullptr : g->ln2_b, accumulate, ln_ws, T, D, stream));

@@ -1083,12 +1083,7 @@ static int tn_many_run(const ssl4gie_gemm_desc* ds, int n, int splits, void* wor
 
 // ---- two products (ssl4gie_gemm_tn_pair): equal accumulate and alpha == 1 on both
 static bool tn_pair_ok(const ssl4gie_gemm_desc* a, const ssl4gie_gemm_desc* b) {
-    static int enabled = -1;  // SSL4GIE_TN_PAIR=0: always two launches (A/B measurements)
-    if (enabled < 0) {
-        const char* e = getenv("SSL4GIE_TN_PAIR");
-        enabled = (e && e[0] == '0') ? 0 : 1;
-    }
-    return enabled && a && b && !nt_ok(a) && !nt_ok(b) && tn_ok(a) && tn_ok(b) && !a->conv && !b->conv &&
+    return a && b && !nt_ok(a) && !nt_ok(b) && tn_ok(a) && tn_ok(b) && !a->conv && !b->conv &&
            ssl4gie_internal_tn256_ok(a) && ssl4gie_internal_tn256_ok(b) && a->K == b->K &&
            a->accumulate == b->accumulate && a->alpha == 1.f && b->alpha == 1.f &&
            a->N % 4 == 0 && b->N % 4 == 0;

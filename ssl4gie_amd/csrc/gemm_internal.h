@@ -66,7 +66,6 @@ struct TnSecond {
 #define TN_GROUP_MAX 16
 struct TnExtras {
     int n, total_tiles;
-    int m_inner;  // walk the shorter tile dimension innermost (gemm_tn256.hip)
     TnSecond p[TN_GROUP_MAX - 1];
 };
 // Split-K count of one launch of n products (same K) under the lone product's, the pair's or the group's policy

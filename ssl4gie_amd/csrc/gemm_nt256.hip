@@ -407,18 +407,10 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_nt256_kernel(
 // =====================================================================================
 // host side
 // =====================================================================================
-static int nt256_mode() {  // SSL4GIE_NT256: "0" never, "1" whenever possible, unset = heuristic
-    static int v = -2;
-    if (v == -2) {
-        const char* s = getenv("SSL4GIE_NT256");
-        v = !s ? -1 : (s[0] == '0' ? 0 : 1);
-    }
-    return v;
-}
+constexpr int NT256_MIN_TILES = 128;       // plain products come here with enough 256 x 256 tiles to fill most of the chip
+constexpr long long NT256_STREAM_M = 16384;  // least M whose output leaves by non-temporal stores (gemm256.h est)
 
 bool ssl4gie_internal_nt256_ok(const ssl4gie_gemm_desc* d) {
-    const int mode = nt256_mode();
-    if (mode == 0 && !d->conv) return false;
     // 32-bit per-lane byte offsets; whole K-tiles; 16-byte row segments on the output
     if ((!d->conv && (long long)d->M * d->sAm * 2 >= (1LL << 32)) ||
         (long long)d->N * d->sBn * 2 >= (1LL << 32))
@@ -446,10 +438,10 @@ bool ssl4gie_internal_nt256_ok(const ssl4gie_gemm_desc* d) {
             return false;
     }
     if (ep == SSL4GIE_EPI_ADD_AUX) return d->aux != nullptr;  // exists in this kernel only
-    if (mode == 1 || d->colstats) return true;  // the statistics only exist in this kernel
+    if (d->colstats) return true;  // the statistics only exist in this kernel
     // heuristic: enough 256x256 tiles to fill most of the chip
     const long long tiles = (long long)((d->M + P_BM - 1) / P_BM) * ((d->N + P_BN - 1) / P_BN);
-    return tiles >= 128;
+    return tiles >= NT256_MIN_TILES;
 }
 
 // Columns per tile, per shape: 256, or 192 (NJ = 3) when that means less work per CU — the tiles of a launch
@@ -466,9 +458,7 @@ constexpr bool nt256_nj2_epilogue(int ep) {
     return ep == SSL4GIE_EPI_NONE || ep == SSL4GIE_EPI_BIAS || ep == SSL4GIE_EPI_ADD_AUX || ep == SSL4GIE_EPI_AFFINE_AUX_RELU;
 }
 static bool nt256_nj2_mode(const ssl4gie_gemm_desc* d) {
-    static int on = -1;  // SSL4GIE_NT256_NJ2=0: never (A/B timing; same results)
-    if (on < 0) { const char* s = getenv("SSL4GIE_NT256_NJ2"); on = (s && s[0] == '0') ? 0 : 1; }
-    if (!on || d->conv || d->dtype_c != SSL4GIE_BF16) return false;
+    if (d->conv || d->dtype_c != SSL4GIE_BF16) return false;
     return nt256_nj2_epilogue(d->epilogue);
 }
 static int nt256_pick_nj(const ssl4gie_gemm_desc* d, int cus) {
@@ -506,7 +496,10 @@ constexpr bool nt256_exists(NtKey k) {
     if (k.conv != 0)  // patch-matrix operand: 256-wide tile; plain / bias, or the ReLU mask (which has no ReLU of its own on A)
         return k.nj == 4 && (plain_or_bias || (k.mode == SSL4GIE_EPI_RELU_MASK_AUX && k.conv == 1));
     if (k.mode == SSL4GIE_EPI_RELU_MASK_AUX) return false;       // exists behind the patch matrix only
-    if (k.nj == 2) return nt256_nj2_epilogue(k.mode);            // 256 x 128: the epilogues of nt256_nj2_mode
+    // 256 x 128: the epilogues of nt256_nj2_mode.  A plain or bias product without statistics comes here through the
+    // tile-count heuristic only, and this tile means one column of tiles: M >= (NT256_MIN_TILES - 1) * 256 + 1 = 32513
+    // rows, above NT256_STREAM_M, so it always takes the streaming twin
+    if (k.nj == 2) return nt256_nj2_epilogue(k.mode) && (!plain_or_bias || k.stats || k.nts);
     return true;
 }
 constexpr int NT256_KEYS = 2 * 10 * 3 * 2 * 3 * 2 * 2;
@@ -553,20 +546,15 @@ int ssl4gie_internal_nt256_launch(const ssl4gie_gemm_desc* d, hipStream_t st) {
     // the launch takes ceil(ntiles / cus) rounds of tiles whatever happens: with that many rounds, the FEWEST
     // persistent workgroups that still finish in them (600 tiles: 3 rounds on 200 CUs instead of 240) leave the
     // other CUs to whatever runs beside the launch — the weight-gradient stream in the backward pass
-    static int balance = -1;
-    if (balance < 0) { const char* e = getenv("SSL4GIE_NT_BALANCE"); balance = e ? atoi(e) : 1; }
     int wgs = ntiles < cus ? ntiles : cus;
-    if (balance && ntiles > cus) {
+    if (ntiles > cus) {
         const int rounds = (ntiles + cus - 1) / cus;
         wgs = (ntiles + rounds - 1) / rounds;
     }
-    // non-temporal output stores for the long products (SSL4GIE_NT_STREAM_M = least M, default 16384; 0 always,
-    // -1 never): see gemm256.h est
-    static long long stream_m = -2;
-    if (stream_m == -2) { const char* s = getenv("SSL4GIE_NT_STREAM_M"); stream_m = s ? atoll(s) : 16384; }
+    // non-temporal output stores for the long products: see gemm256.h est
     NtLaunch L{d, dim3(wgs), tn, ntiles,
                EpiArgs{d->alpha, d->epilogue, d->bias, d->residual, d->ldr, d->aux, d->out2, d->accumulate,
-                       d->colstats, (stream_m >= 0 && d->M >= stream_m) ? 1 : 0},
+                       d->colstats, d->M >= NT256_STREAM_M ? 1 : 0},
                ConvK{}};
     if (d->epilogue == SSL4GIE_EPI_AFFINE_AUX_RELU) {  // two borrowed slots (gemm256.h p_epilogue)
         L.e.residual = d->scale;

@@ -20,7 +20,6 @@
 #include "gemm256.h"
 #include "prof.h"
 
-#include <stdlib.h>
 #include <type_traits>
 
 DEVI int q_swz(int k) { return ((k & 3) | ((k >> 1) & 4)) << 1; }
@@ -56,7 +55,6 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_tn256_kernel(
     int tiles_n, int ntiles, int splits, float alpha, int accumulate, float* __restrict__ colsum,
     float* __restrict__ colsum_part, ConvK cg, TnExtras ex) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    const bool tn_m_inner_ok = ex.m_inner != 0;
     const int t = threadIdx.x, lane = t & 63;
     const int wave = __builtin_amdgcn_readfirstlane(t >> 6);
     const int wr = wave >> 2, wc = wave & 3;
@@ -83,9 +81,9 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_tn256_kernel(
     // L2: a run of r x c tiles reads r + c slabs, so the run should be as square as possible — the
     // SHORTER tile dimension is the inner one (a 3 x 12 product walked row by row makes a 27-tile XCD
     // chunk read 3 + 12 slabs and its 9-tile neighbour 1 + 9; column by column they read 3 + 9 and 3 + 3:
-    // 18 slab reads instead of 25 against a minimum of 15).  SSL4GIE_TN_INNER=n restores the old walk.
+    // 18 slab reads instead of 25 against a minimum of 15).
     const int tiles_m = (M + P_BM - 1) / P_BM;
-    const bool m_inner = tiles_m < tiles_n && tn_m_inner_ok;
+    const bool m_inner = tiles_m < tiles_n;
     const int m0 = (m_inner ? tile % tiles_m : tile / tiles_n) * P_BM;
     const int n0 = (m_inner ? tile / tiles_m : tile % tiles_n) * P_BN;
     const int nkt = K / P_BK;
@@ -376,7 +374,8 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_tn256_kernel(
 // Image of a stage half: k-row r at r * 512 B, 32-byte unit u (16 m- or n-values) at position u ^ k_swz(r): the 32
 // lanes of a ds_read_b64_tr_b16 group read 8 rows x 32 B and k_swz takes 8 distinct values on them (conflict-free).
 // Same accumulator layout, same per-accumulator summation order (k ascending) as the kernel above: results are
-// bit-identical, so SSL4GIE_TN256K=0 (A/B timing) changes nothing else.
+// bit-identical.  Every product with plain operands and full (or clamped) tiles runs here; the kernel above keeps the
+// patch-matrix operands (CONV) and the lone partial-tile products (PARTIAL).
 DEVI int k_swz(int k) { return (k & 3) | ((k >> 1) & 4); }
 
 template <bool COLSUM>
@@ -386,7 +385,6 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_tn256k_kernel(
     int tiles_n, int ntiles, int splits, float alpha, int accumulate, float* __restrict__ colsum,
     float* __restrict__ colsum_part, TnExtras ex) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    const bool tn_m_inner_ok = ex.m_inner != 0;
     const int t = threadIdx.x, lane = t & 63;
     const int wave = __builtin_amdgcn_readfirstlane(t >> 6);
     const int wr = wave >> 2, wc = wave & 3;
@@ -410,7 +408,7 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_tn256k_kernel(
         }
     }
     const int tiles_m = (M + P_BM - 1) / P_BM;
-    const bool m_inner = tiles_m < tiles_n && tn_m_inner_ok;  // (tile walk: see the kernel above)
+    const bool m_inner = tiles_m < tiles_n;  // (tile walk: see the kernel above)
     const int m0 = (m_inner ? tile % tiles_m : tile / tiles_n) * P_BM;
     const int n0 = (m_inner ? tile / tiles_m : tile % tiles_n) * P_BN;
     const int nkt = K / P_BK;
@@ -578,18 +576,10 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_tn256k_kernel(
 // =====================================================================================
 // host side
 // =====================================================================================
-static int tn256_mode() {  // SSL4GIE_TN256: "0" never, "1" whenever possible, unset = heuristic
-    static int v = -2;
-    if (v == -2) {
-        const char* s = getenv("SSL4GIE_TN256");
-        v = !s ? -1 : (s[0] == '0' ? 0 : 1);
-    }
-    return v;
-}
+// share of the CUs (percent) a lone product and a paired launch aim to fill
+constexpr int TN_FILL_LONE = 75, TN_FILL_PAIR = 75;
 
 bool ssl4gie_internal_tn256_ok(const ssl4gie_gemm_desc* d) {
-    const int mode = tn256_mode();
-    if (mode == 0 && !d->conv) return false;
     if (d->K % P_BK != 0 || d->K < P_BK) return false;
     if (d->conv)
         return ssl4gie_internal_conv_geom_ok(d->conv) && d->conv->C % 8 == 0 &&
@@ -597,7 +587,6 @@ bool ssl4gie_internal_tn256_ok(const ssl4gie_gemm_desc* d) {
                (long long)d->K * d->sAk * 2 < (1LL << 32);
     if ((long long)d->K * d->sAk * 2 >= (1LL << 32) || (long long)d->K * d->sBk * 2 >= (1LL << 32))
         return false;  // 32-bit per-lane byte offsets are relative to a per-K-tile base: generous
-    if (mode == 1) return true;
     // (round 5, measured and not changed: the narrow long-contraction products of ResNet50's layer1 — dW [256, 64],
     // [64, 256], [64, 64], [128, 256] over 802 816 pixels — and the MLP heads' short ones stay on the 128-tile
     // kernel: 98 / 98 / 70 / 121 us there (5.2 TB/s) against 158 / 120 / 108 / 140 us on the partial-tile path
@@ -616,25 +605,15 @@ int ssl4gie_internal_tn256_splits(const ssl4gie_gemm_desc* descs, int n, TnSplit
     const int cus = ssl4gie_internal_compute_cus();
     int fill = 100, cap = 64;
     if (policy == TN_SPLIT_LONE) {
-        // SSL4GIE_TN_FILL1 (percent, default 75): share of the CUs a lone product aims to fill.  These launches run
-        // beside the data-gradient chain on a weight-gradient stream, like the pairs (whose fill is 75 % too): MoCo-R50
-        // step 55.5 / 55.7 -> 54.9 / 55.0 ms in a same-box A/B (profiles/r04cy_tn_fill1.log), depth and MAE unchanged
-        static int fill1 = -1;
-        if (fill1 < 0) { const char* e = getenv("SSL4GIE_TN_FILL1"); fill1 = e ? atoi(e) : 75; if (fill1 < 10) fill1 = 10; }
-        fill = fill1;
+        // These launches run beside the data-gradient chain on a weight-gradient stream, like the pairs (whose fill is
+        // 75 % too): MoCo-R50 step 55.5 / 55.7 -> 54.9 / 55.0 ms against 100 % in a same-box A/B
+        // (profiles/r04cy_tn_fill1.log), depth and MAE unchanged
+        fill = TN_FILL_LONE;
         cap = 256;  // (a single-tile product over a long contraction: one split per CU)
     } else if (policy == TN_SPLIT_PAIR) {
-        // SSL4GIE_TN_FILL (percent, default 75): share of the CUs a paired launch aims to fill — on the
-        // weight-gradient side stream fewer, longer workgroups mean less slab traffic (measured:
+        // on the weight-gradient side stream fewer, longer workgroups mean less slab traffic (measured:
         // profiles/r01w_ab_grid_sizing.log)
-        static int fill2 = -1;
-        if (fill2 < 0) {
-            const char* e = getenv("SSL4GIE_TN_FILL");
-            fill2 = e ? atoi(e) : 75;
-            if (fill2 < 10) fill2 = 10;
-            if (fill2 > 200) fill2 = 200;
-        }
-        fill = fill2;
+        fill = TN_FILL_PAIR;
     } else if (tiles * 10 >= cus * 7) {
         return 1;  // group: >= 70 % of the CUs busy with whole-K tiles: no slabs at all
     }
@@ -668,9 +647,6 @@ int ssl4gie_internal_tn256_launch(const ssl4gie_gemm_desc* descs, int n, int spl
         any_colsum = any_colsum || d2->colsum_a != nullptr;
     }
     sec.n = n - 1;
-    static int m_inner = -1;  // SSL4GIE_TN_INNER=n: the row-by-row tile walk of rounds 1-2 (A/B)
-    if (m_inner < 0) { const char* s = getenv("SSL4GIE_TN_INNER"); m_inner = (s && (s[0] == 'n' || s[0] == 'N')) ? 0 : 1; }
-    sec.m_inner = m_inner;
     dim3 grid((tm * tn + sec.total_tiles) * splits);
     ConvK ck{};
     if (d->conv) {
@@ -686,18 +662,14 @@ int ssl4gie_internal_tn256_launch(const ssl4gie_gemm_desc* descs, int n, int spl
                                          (float*)d->C, d->ldc, slabs, d->M, d->N, d->K, tn, tm * tn, splits,
                                          d->alpha, d->accumulate, d->colsum_a, colsum_part, tail...);
     };
-    // plain operands, no skipped fragment blocks: the k-split kernel (SSL4GIE_TN256K=0: the column-split one of
-    // rounds 1-4; the results are bit-identical, the knob exists for A/B timing)
-    static int ksplit = -1;
-    if (ksplit < 0) { const char* s = getenv("SSL4GIE_TN256K"); ksplit = (s && s[0] == '0') ? 0 : 1; }
-    if (ksplit && cv == 0 && !partial)
+    // plain operands, no skipped fragment blocks: the k-split kernel
+    if (cv == 0 && !partial)
         return any_colsum ? run(P_KERNEL<gemm_bf16_tn256k_kernel<true>>{}, sec)
                           : run(P_KERNEL<gemm_bf16_tn256k_kernel<false>>{}, sec);
-    // the column-split kernel, (COLSUM, CONV, PARTIAL): PARTIAL exists for plain operands only
+    // the column-split kernel, (COLSUM, CONV, PARTIAL): the partial tiles of plain operands, or a patch matrix
     auto column_split = [&](auto cs) {
         constexpr bool CS = decltype(cs)::value;
         if (partial) return run(P_KERNEL<gemm_bf16_tn256_kernel<CS, 0, true>>{}, ck, sec);
-        if (cv == 0) return run(P_KERNEL<gemm_bf16_tn256_kernel<CS, 0, false>>{}, ck, sec);
         if (cv == 1) return run(P_KERNEL<gemm_bf16_tn256_kernel<CS, 1, false>>{}, ck, sec);
         return run(P_KERNEL<gemm_bf16_tn256_kernel<CS, 2, false>>{}, ck, sec);
     };

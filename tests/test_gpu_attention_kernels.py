@@ -5,7 +5,7 @@ bite: tests/test_attn_checks_cpu.py), through ssl4gie_amd.ops.
 The case list puts a case on every branch of the dispatch:
   whole-head kernels   NKT = 2 ... 16 at the bucket's first N, the last half-tail N, the first N with one key in the
                        last tile and the full bucket (HT variants: forward at hd 32, backward at hd 64; AttnFwdQG and
-                       U = 2 from NKT = 10 at hd 64; the persistent prefetching backward and its fall-back), `gauss`
+                       U = 2 from NKT = 10 at hd 64, where the backward is the persistent prefetching kernel), `gauss`
                        at every scale; then EVERY N from 1 to 256 in the exact families `uniform` and `onehot`, where
                        a dropped, duplicated or leaked key or a fragment-layout slip cannot hide in the rounding;
   streaming kernels    the first block over the whole-head limit, one key and 127 keys in the last block, MASK and

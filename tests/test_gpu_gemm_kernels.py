@@ -28,14 +28,15 @@ GEMM / reduction kernels; `route` labels every case and the last test prints the
     gemm_bf16_tn_kernel; slab_reduce_kernel, slab_reduce_wide_kernel<4>, <16>
     gemm_bf16_tn256k_kernel<CS>             CS false and true (lone products, pair, group)
     gemm_bf16_tn256_kernel<CS, 0, PART=true>  CS false and true (the partial kernel)
-  Reachable in the default environment and not reached: none.  Not reachable without a knob, hence not here:
-    (*)  bf16 MODE 0 / 1 on NJ 2 without streaming stores: the heuristic wants 128 tiles, one column tile means
-         M >= 32513, and streaming starts at M = 16384 (SSL4GIE_NT256=1 or SSL4GIE_NT_STREAM_M would reach it);
-    (**) MODE 2 / 5 on NJ 4 in the polynomial form (SSL4GIE_GELU_TABLE=0);
-    gemm_bf16_tn256_kernel<CS, 0, PART=false>, the column-split kernel for full tiles (SSL4GIE_TN256K=0);
-    (the loader-wave and four-phase forms of the NT kernel and the five-stage ring of the k-split TN kernel, which a
-    debug build of the library used to hold, no longer exist: profiles/HISTORY.md, "Retired knobs");
-    CONV 1 / 2 and MODE 7 (the implicit-convolution operand): tests/test_gpu_conv.py.
+  Reachable in the default environment and not reached: none.  Every GEMM kernel the library holds is reached here or,
+  for CONV 1 / 2 and MODE 7 (the implicit-convolution operand), in tests/test_gpu_conv.py, with one exception:
+    (**) MODE 2 / 5 on NJ 4 in the polynomial form, which the supported switch SSL4GIE_GELU_TABLE=0 (README.md) selects.
+  Kernels that used to sit behind A/B knobs no longer exist (profiles/HISTORY.md, "Retired knobs"):
+    (*)  bf16 MODE 0 / 1 on NJ 2 has the streaming-store form only: the heuristic wants 128 tiles, one column tile means
+         M >= 32513, and streaming starts at M = 16384 (nt256_exists in gemm_nt256.hip states it);
+    column-split: gemm_bf16_tn256_kernel<CS, 0, PART=false> is gone, full tiles of plain operands always take the k-split
+    kernel; so are the loader-wave and four-phase forms of the NT kernel and the five-stage ring of the k-split TN
+    kernel, which a debug build of the library used to hold.
   FULL is no instantiation of its own: gemm256.h takes the full / ragged epilogue per tile at run time, so every ragged
   shape with more than one tile runs both; the full-tile twins (16384, 32768 rows) run the full one alone.
   The 256 x 256 TN kernels take a product only from M N >= 65536 (and K >= 1024) on: the partial kernel's lone shape is

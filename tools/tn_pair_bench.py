@@ -18,7 +18,7 @@ PAIRS = [("enc.fc2+fc1", enc_T, (768, 3072), (3072, 768)), ("enc.proj+qkv", enc_
          ("dec.fc2+fc1", dec_T, (512, 2048), (2048, 512)), ("dec.proj+qkv", dec_T, (512, 512), (1536, 512))]
 ITERS = int(os.environ.get("TN_ITERS", "12"))
 CUS = int(os.environ.get("SSL4GIE_COMPUTE_CUS", "240"))
-FILL = int(os.environ.get("SSL4GIE_TN_FILL", "75"))
+FILL = 75  # TN_FILL_PAIR of csrc/gemm_tn256.hip
 
 
 def splits_of(T, a, b):

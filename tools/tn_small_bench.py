@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """the weight-gradient products of MoCo-R50 that sat on the round-1 128-tile TN kernel: long contractions over
-narrow outputs (layer1 1x1 convolutions) and short contractions over wide outputs (MLP heads); run with
-SSL4GIE_TN256=0 (old kernel) / unset (routing) / 1 (256 kernels always)"""
+narrow outputs (layer1 1x1 convolutions) and short contractions over wide outputs (MLP heads), as
+ssl4gie_internal_tn256_ok routes them (profiles/r05_tn_small_routing.log has the same shapes with every product forced
+onto the 128-tile kernel and onto the 256-tile ones, through a switch that is retired: profiles/HISTORY.md)"""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch

@@ -3,7 +3,7 @@
 geometry alone: the tile walk and xcd_remap of csrc/gemm_tn256.hip (consecutive logical workgroups share an XCD
 and its L2: a chunk that holds r m-tiles and c n-tiles of one K-split reads r + c operand slabs), plus the fp32
 slabs (written by the GEMM, read and written once more by slab_reduce_kernel).  Prints, per paired launch, the
-prediction for the shipped split count (SSL4GIE_TN_FILL = 75 % of 240 CUs) and for every other split count.
+prediction for the shipped split count (TN_FILL_PAIR of that file: 75 % of 240 CUs) and for every other split count.
 Checked against the PMC measurement: 405 MB per launch predicted, 397 MB measured (profiles/pmc_traffic.json)."""
 import math
 
