@@ -19,7 +19,10 @@
  *     metrics ssl4gie_seg_{counts,scores} / ssl4gie_confusion_{update,scores} / ssl4gie_lower_median_{workspace_bytes,f32} / ssl4gie_depth_eval{_workspace_bytes,}
  *     joined it the same way, and so did the detection input entry points ssl4gie_det_color{_workspace_bytes,} / ssl4gie_det_geometry / ssl4gie_det_boxes and the
  *     detection metric ssl4gie_det_map_{workspace_bytes,match,order,accumulate}, and the Faster R-CNN head entry points ssl4gie_nms_{workspace_bytes,segments} /
- *     ssl4gie_rpn_decode / ssl4gie_roi_decode / ssl4gie_roi_align_{fwd,bwd}; 11: before the sixteen BatchNorm entry points that had grown one per fusion (ssl4gie_bn_fwd / _fwd_partials / _fwd_partials_bits /
+ *     ssl4gie_rpn_decode / ssl4gie_roi_decode / ssl4gie_roi_align_{fwd,bwd}; revision 12 later LOST ssl4gie_conv3x3_direct_{fwd,wgrad}_affine,
+ *     ssl4gie_block_wgrad_descs, ssl4gie_wgrad_group and the SSL4GIE_BWD_DEFER_WGRAD flag of ssl4gie_block_bwd with the two opt-in paths of the Python
+ *     package that were their only callers (measured null or slower, profiles/HISTORY.md appendix 4) — the number is kept because the suite asserts 12
+ *     in nine places; a caller of those four entry points fails at symbol resolution instead; 11: before the sixteen BatchNorm entry points that had grown one per fusion (ssl4gie_bn_fwd / _fwd_partials / _fwd_partials_bits /
  *     _coef_partials / _coef_stats / _apply_bits, _stats / _stats_partials, _bwd / _bwd_xmask / _bwd_bits, _bwd_reduce / _reduce_xmask / _reduce_bits,
  *     _bwd_apply / _apply_xmask) were REPLACED by five with a source and a mask kind — the same launches, new signatures; 10: before the diagnostics entry point that read the 256x256 NT kernel's in-kernel
  *     time stamps was REMOVED with the debug build of the library — the one removal in this history; 9: before ssl4gie_infonce_{workspace_bytes,loss} / ssl4gie_cross_entropy{_workspace_bytes,} /
@@ -291,15 +294,12 @@ int ssl4gie_block_fwd(const ssl4gie_block_dims* d, const ssl4gie_block_weights* 
                       void* workspace, void* stream);
 /* dx_out fp32 (+ dx_out_lp, its operand-type copy; may be NULL in f32 mode) -> dx_in fp32 and
  * dx_in_lp; parameter grads overwritten or accumulated.  `accumulate` is a flag word:
- * SSL4GIE_BWD_ACCUMULATE (1) and SSL4GIE_BWD_DEFER_WGRAD (2): with the latter the four weight-gradient
- * products (and the bias gradients riding on them) are NOT launched; `workspace` then holds their
- * dY operands and must stay untouched until the caller has launched them (next two entries). */
+ * SSL4GIE_BWD_ACCUMULATE (1), SSL4GIE_BWD_NO_JOIN (4) and SSL4GIE_BWD_SLOT(s); bit 1 is unused. */
 #define SSL4GIE_BWD_ACCUMULATE 1
-#define SSL4GIE_BWD_DEFER_WGRAD 2
 /* SSL4GIE_BWD_NO_JOIN | SSL4GIE_BWD_SLOT(s), s in 0..3: `stream` does NOT wait for the block's weight-gradient
  * products at the end of the call (the default join makes the next block's first data-gradient GEMM wait for
  * this block's last weight gradient: 20 stalls per MAE step).  Instead their completion is recorded under slot s
- * (as ssl4gie_wgrad_group does): `workspace`, dx_out_lp and the gradient targets must stay untouched until
+ * on the side stream: `workspace`, dx_out_lp and the gradient targets must stay untouched until
  * ssl4gie_wgrad_wait(s, stream) has been called — the caller alternates two workspaces and slots. */
 #define SSL4GIE_BWD_NO_JOIN 4
 #define SSL4GIE_BWD_SLOT(s) (((s) & 3) << 4)
@@ -315,20 +315,8 @@ int ssl4gie_block_bwd(const ssl4gie_block_dims* d, const ssl4gie_block_weights* 
  * on = 0 folds them back onto `stream` (also: environment SSL4GIE_WGRAD_STREAM=0); bench.py does
  * that while it measures per-kernel durations. */
 int ssl4gie_set_wgrad_stream(int on);
-/* Deferred weight gradients: out4[0..3] = the dW_fc2, dW_fc1, dW_proj, dW_qkv product descriptors
- * of a block whose ssl4gie_block_bwd ran with SSL4GIE_BWD_DEFER_WGRAD on `workspace` (dy = the
- * dx_out_lp it was given; dx_out in f32 mode).  Collect the descriptors of several blocks and run
- * them as one ssl4gie_gemm_tn_group: */
-int ssl4gie_block_wgrad_descs(const ssl4gie_block_dims* d, const ssl4gie_block_act* a,
-                              const ssl4gie_block_grads* g, const void* dy, void* workspace,
-                              int accumulate, ssl4gie_gemm_desc* out4);
-/* ssl4gie_gemm_tn_group on the weight-gradient side stream: the side stream first waits for all
- * work enqueued on `stream` so far, and event `slot` (0..3) then marks the group's completion.
- * Nothing waits for the group until ssl4gie_wgrad_wait(slot, s) makes stream `s` do so — the caller
- * must issue that wait before anything reads the gradients or rewrites the operands (block
- * workspaces, activations).  Without a side stream the group simply runs on `stream`. */
-int ssl4gie_wgrad_group(const ssl4gie_gemm_desc* descs, int n, void* workspace, size_t workspace_bytes,
-                        int slot, void* stream);
+/* makes `stream` wait for the weight gradients of the latest ssl4gie_block_bwd(SSL4GIE_BWD_NO_JOIN | SSL4GIE_BWD_SLOT(slot));
+ * to be issued before anything reads those gradients or rewrites their operands (block workspace, activations). */
 int ssl4gie_wgrad_wait(int slot, void* stream);
 /* Number of CUs the persistent / one-workgroup-per-CU GEMM grids are sized for (8..256, default 240:
  * the weight-gradient side stream shares the chip; environment SSL4GIE_COMPUTE_CUS).  The 256x256 kernels hold all 160 KiB of a CU's LDS, so an RCCL
@@ -393,17 +381,6 @@ size_t ssl4gie_conv3x3_direct_wgrad_workspace_bytes(int B, int H, int W, int Cin
 int ssl4gie_conv3x3_direct_wgrad(const void* dy, const void* x, float* dw2, float* dbias,
                                  void* workspace, size_t workspace_bytes, int B, int H, int W, int Cin,
                                  int Cout, int relu_in, int accumulate, void* stream);
-/* The same two kernels with a training-mode BatchNorm (+ ReLU) applied to their input on the way in: the operand
- * is act(x in_coef[0][ci] + in_coef[1][ci]) rounded to bf16 (in_coef [2][Cin] as the coefficients-only ssl4gie_bn_fwd writes
- * it; act = ReLU if relu_in), zero-padded AFTER the normalisation — torchvision Bottleneck bn1 -> relu -> conv2
- * without a BatchNorm pass or a normalised map in memory (its backward: ssl4gie_bn_bwd with MASK_X on the data gradient).
- * Values equal ssl4gie_bn_fwd (FROM_PARTIALS) followed by the plain kernels bit for bit. */
-int ssl4gie_conv3x3_direct_fwd_affine(const void* x, const float* in_coef, const void* w2, const float* bias,
-                                      void* y, float* colstats, int B, int H, int W, int Cin, int Cout,
-                                      int relu_in, void* stream);
-int ssl4gie_conv3x3_direct_wgrad_affine(const void* dy, const void* x, const float* in_coef, float* dw2,
-                                        float* dbias, void* workspace, size_t workspace_bytes, int B, int H,
-                                        int W, int Cin, int Cout, int relu_in, int accumulate, void* stream);
 /* torchvision ResNet.conv1 = nn.Conv2d(3, 64, 7, stride 2, pad 3, bias=False) (reference
  * Models/models.py:63-69) WITHOUT a patch matrix (ssl4gie_stem_im2col7x7 + GEMM remain for fp32).
  *   pack:  img fp32 [B,3,H,W] -> packed bf16 [B, 2 Ho + 6, 2 Wo + 6, 4] (three channels + a zero,
@@ -493,7 +470,7 @@ int ssl4gie_subsample2(const void* x, void* y, int dtype, int B, int H, int W, i
  *   FROM_PARTIALS  the same statistics from `partial` [parts][2][C], the per-128-row sums the producing GEMM wrote
  *                  (ssl4gie_gemm_desc::colstats), instead of a pass over x.  Writes y (+ relu_bits), or — y, x, res
  *                  NULL — only the coefficients coef [2][C] with y = x coef[0][c] + coef[1][c], for a consumer that
- *                  applies them itself: ssl4gie_bn_maxpool3x3s2_fwd, ssl4gie_conv3x3_direct_*_affine, the
+ *                  applies them itself: ssl4gie_bn_maxpool3x3s2_fwd, the
  *                  SSL4GIE_EPI_AFFINE_AUX_RELU epilogue (MoCo's momentum encoder, moco/builder.py:127-135).
  *   FROM_STATS     mean / rstd are INPUTS (evaluation, or the GLOBAL statistics of a SyncBatchNorm exchange): no
  *                  reduction runs, running_* must be NULL.  Writes y, or — y, x, res, workspace NULL, only C > 0

@@ -14,20 +14,10 @@ from __future__ import annotations
 import torch
 import torch.nn as nn
 
-import os
-
 from ..dpt_engine import Conv3x3Fn
-
-# SSL4GIE_GRAD_JOIN=0: autograd sums the two gradient contributions of a block input itself
-_GRAD_JOIN = os.environ.get("SSL4GIE_GRAD_JOIN", "1") != "0"
-# SSL4GIE_BN_STATS_FUSED=0: BatchNorm statistics by their own pass over the map (A/B measurements)
-_BN_STATS = os.environ.get("SSL4GIE_BN_STATS_FUSED", "1") != "0"
-# SSL4GIE_BN_RECOMPUTE=0: the 1x1 convolutions that widen a map 4x (conv3, downsample) write their raw output and
-# a BatchNorm pass re-reads it under torch.no_grad() too (A/B measurements)
-_BN_RECOMPUTE = os.environ.get("SSL4GIE_BN_RECOMPUTE", "1") != "0"
 from ..engine import EngineModule, GradJoin, LinearFn
-from ..resnet_engine import (AvgPoolFn, BatchNormFn, BnReluConv3x3Fn, BnReluMaxPoolFn, MaxPoolFn, StemConvFn,
-                             Subsample2Fn, _count_batch, _sync_group, bn_relu_conv3x3_ok, bn_relu_maxpool_ok)
+from ..resnet_engine import (AvgPoolFn, BatchNormFn, BnReluMaxPoolFn, MaxPoolFn, StemConvFn, Subsample2Fn,
+                             _count_batch, _sync_group, bn_relu_maxpool_ok)
 
 
 class Bottleneck(nn.Module):
@@ -95,9 +85,8 @@ class ResNet50(EngineModule):
             x = Subsample2Fn.apply(x, join)  # the pixel pick deposits its scattered gradient in the join
             join = None  # ... and sits between x and the GEMM: the GEMM's gradient is not x's
         B, H, W, C = x.shape
-        r = LinearFn.apply(x.reshape(-1, C), conv.weight, None, self.dtype_, self.dtype_, self.sink(),
-                           self.lp_cache, _BN_STATS, join)
-        y, st = r if _BN_STATS else (r, None)
+        y, st = LinearFn.apply(x.reshape(-1, C), conv.weight, None, self.dtype_, self.dtype_, self.sink(),
+                               self.lp_cache, True, join)
         return y.view(B, H, W, -1), st
 
     def _c1_bn_nograd(self, x, conv, bn, relu, res=None):
@@ -134,7 +123,7 @@ class ResNet50(EngineModule):
 
     def _recompute_ok(self, x, conv, bn):
         from .. import ops
-        if not _BN_RECOMPUTE or torch.is_grad_enabled() or self.dtype_ != torch.bfloat16:
+        if torch.is_grad_enabled() or self.dtype_ != torch.bfloat16:
             return False
         from ..resnet_engine import _SYNC_FUSED
         if not (bn.training or bn.running_mean is None) or (_sync_group(bn)[0] and not _SYNC_FUSED):
@@ -148,17 +137,11 @@ class ResNet50(EngineModule):
         # every convolution hands the batch statistics of its output to the BatchNorm that follows
         # (column sums from the GEMM epilogue): no separate statistics pass over the maps
         # x feeds conv1 and the identity (or downsample) branch: one GradJoin, conv1 is the adder
-        join = GradJoin.for_tensor(x) if _GRAD_JOIN else None
+        join = GradJoin.for_tensor(x)
         out, st = self._c1(x, blk.conv1, join)
-        if bn_relu_conv3x3_ok(out, blk.bn1, st, blk.conv2, torch.is_grad_enabled()):
-            # bn1 -> relu applied inside the 3x3 convolution's halo staging: no BatchNorm pass, no normalised map
-            out, st = BnReluConv3x3Fn.apply(out, blk.bn1.weight, blk.bn1.bias, blk.bn1, st, blk.conv2.weight,
-                                            self.sink(), self.lp_cache, _BN_STATS)
-        else:
-            out = self._bn(out, blk.bn1, True, stats=st)
-            r = Conv3x3Fn.apply(out, blk.conv2.weight, None, blk.conv2.stride[0], False, self.sink(),
-                                self.lp_cache, _BN_STATS)
-            out, st = r if _BN_STATS else (r, None)
+        out = self._bn(out, blk.bn1, True, stats=st)
+        out, st = Conv3x3Fn.apply(out, blk.conv2.weight, None, blk.conv2.stride[0], False, self.sink(),
+                                  self.lp_cache, True)
         out = self._bn(out, blk.bn2, True, stats=st)
         identity = x
         if blk.downsample is not None:
@@ -177,18 +160,17 @@ class ResNet50(EngineModule):
         """build the per-batch stem operand (bf16: the packed image) on the CURRENT stream, so that two
         forward passes over the same batch on different streams only read it (moco/builder.py)"""
         from .. import ops
-        from ..resnet_engine import STEM_COLS, _STEM_DIRECT
+        from ..resnet_engine import STEM_COLS
         if imgs.dtype != torch.float32 or not imgs.is_contiguous():
             return  # StemConvFn makes its own copy: nothing is shared between the passes
-        if _STEM_DIRECT and self.dtype_ == torch.bfloat16 and self.conv1.weight.shape[0] == 64 and imgs.shape[1] == 3:
+        if self.dtype_ == torch.bfloat16 and self.conv1.weight.shape[0] == 64 and imgs.shape[1] == 3:
             STEM_COLS.get(imgs, self.dtype_, ops.stem7x7_pack)
         else:
             STEM_COLS.get(imgs, self.dtype_)   # the patch matrix (fp32 parity mode)
 
     def forward_maps(self, imgs, all_stages=False):
         self._prepare()
-        r = StemConvFn.apply(imgs, self.conv1.weight, self.dtype_, self.sink(), self.lp_cache, _BN_STATS)
-        x, st = r if _BN_STATS else (r, None)
+        x, st = StemConvFn.apply(imgs, self.conv1.weight, self.dtype_, self.sink(), self.lp_cache, True)
         if bn_relu_maxpool_ok(x, self.bn1, st):   # bn1 -> relu -> maxpool in one pass over the convolution output
             x = BnReluMaxPoolFn.apply(x, self.bn1.weight, self.bn1.bias, self.bn1, self.sink(), st)
         else:

@@ -17,7 +17,7 @@ ABI_VERSION = 12
 PROF_KINDS = 7  # SSL4GIE_PROF_KINDS: entries of the launch profiler's arrays
 
 F32, BF16 = 0, 1
-BWD_ACCUMULATE, BWD_DEFER_WGRAD, BWD_NO_JOIN = 1, 2, 4
+BWD_ACCUMULATE, BWD_NO_JOIN = 1, 4
 EPI_NONE, EPI_BIAS, EPI_BIAS_GELU, EPI_BIAS_RESIDUAL, EPI_DGELU, EPI_BIAS_GELU_GRAD, EPI_MUL_AUX, \
     EPI_RELU_MASK_AUX, EPI_ADD_AUX, EPI_AFFINE_AUX_RELU = range(10)
 BN_FROM_X, BN_FROM_PARTIALS, BN_FROM_STATS, BN_FROM_COEF = range(4)   # ssl4gie_bn_fwd: source of the normalisation
@@ -106,8 +106,6 @@ PROTOTYPES = {
     "ssl4gie_conv3x3_direct_wgrad_ok": (i32, [i32, i32, i32, i32, i32]),
     "ssl4gie_conv3x3_direct_wgrad_workspace_bytes": (sz, [i32, i32, i32, i32, i32]),
     "ssl4gie_conv3x3_direct_wgrad": (i32, [vp, vp, vp, vp, vp, sz, i32, i32, i32, i32, i32, i32, i32, vp]),
-    "ssl4gie_conv3x3_direct_wgrad_affine": (i32, [vp, vp, vp, vp, vp, vp, sz, i32, i32, i32, i32, i32, i32, i32, vp]),
-    "ssl4gie_conv3x3_direct_fwd_affine": (i32, [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp]),
     "ssl4gie_stem7x7_packed_bytes": (sz, [i32, i32, i32]),
     "ssl4gie_stem7x7_pack": (i32, [vp, vp, i32, i32, i32, vp]),
     "ssl4gie_stem7x7_tiles": (i32, [i32, i32, i32]),
@@ -177,9 +175,6 @@ PROTOTYPES = {
     "ssl4gie_gemm_tn_pair": (i32, [vp, vp, vp, sz, vp]),
     "ssl4gie_gemm_tn_group_workspace_bytes": (sz, [vp, i32]),
     "ssl4gie_gemm_tn_group": (i32, [vp, i32, vp, sz, vp]),
-    "ssl4gie_block_wgrad_descs": (i32, [C.POINTER(BlockDims), C.POINTER(BlockAct), C.POINTER(BlockGrads), vp, vp,
-                                        i32, vp]),
-    "ssl4gie_wgrad_group": (i32, [vp, i32, vp, sz, i32, vp]),
     "ssl4gie_wgrad_wait": (i32, [i32, vp]),
     "ssl4gie_set_wgrad_stream": (i32, [i32]),
     "ssl4gie_set_compute_cus": (i32, [i32]),

@@ -16,19 +16,12 @@ HIP.  Reference: Models/DPT_decoder.py (lines cited per node).
 from __future__ import annotations
 
 import contextlib
-import os
 import weakref
 
 import torch
 
 from . import ops
 from .engine import GradSink, LPCache, touched_since, weights_epoch, wgrad_fork
-
-
-# SSL4GIE_IMPLICIT_CONV=0 forces the materialised patch matrix (A/B measurements, parity tests)
-_IMPLICIT = os.environ.get("SSL4GIE_IMPLICIT_CONV", "1") != "0"
-# SSL4GIE_DIRECT_CONV=0 sends the narrow head convolutions through the GEMM paths again (A/B)
-_DIRECT = os.environ.get("SSL4GIE_DIRECT_CONV", "1") != "0"
 
 
 def _fills_chip(x, stride, n_out):
@@ -74,7 +67,7 @@ def refresh_conv_operands(lp: LPCache):
     each in front of its convolution.  Runs when the fused optimizers have moved the weights (the engine's
     weights epoch); images made stale any other way are re-packed lazily, one by one, as before."""
     rec = lp.__dict__.get("_conv_recipes")
-    if not rec or not _BATCH_PACK:
+    if not rec:
         return
     epoch = weights_epoch()
     seen = lp.__dict__.get("_conv_epoch")
@@ -107,10 +100,6 @@ def refresh_conv_operands(lp: LPCache):
                                              [it[4] for it in group])
         for it, t in zip(group, outs):
             lp._c[it[0]] = (it[1], t)
-
-
-# SSL4GIE_CONV_PACK_BATCH=0: every 3x3 operand image by its own launch again (A/B)
-_BATCH_PACK = os.environ.get("SSL4GIE_CONV_PACK_BATCH", "1") != "0"
 
 
 def _pad_cols(m: torch.Tensor, ld: int) -> torch.Tensor:
@@ -160,13 +149,13 @@ class Conv3x3Fn(torch.autograd.Function):
         b = bias.detach() if bias is not None else None
         ctx.save_for_backward(x, weight, bias)
         ctx.cfg = (stride, relu_in, sink, lp, ld)
-        implicit = _IMPLICIT and ld == 9 * Cin and ops.conv3x3_implicit_ok(x, stride, Cout)
+        implicit = ld == 9 * Cin and ops.conv3x3_implicit_ok(x, stride, Cout)
         Ho, Wo = ops.conv_out_hw(H, W, stride)
         stats = None
         # direct kernel: where it is ahead of the gathered GEMM (ops.conv3x3_direct_ok), and instead
         # of a materialised patch matrix where the gathered GEMM does not apply (layer1_rn: Cin = 96)
-        direct = _DIRECT and stride == 1 and (ops.conv3x3_direct_ok(x, Cout) or
-                                              (not implicit and ops.conv3x3_direct_supported(x, Cout)))
+        direct = stride == 1 and (ops.conv3x3_direct_ok(x, Cout) or
+                                  (not implicit and ops.conv3x3_direct_supported(x, Cout)))
         if direct and want_stats and b is None:
             # narrow ResNet layers (64 -> 64 @56, 128 -> 128 @28): direct kernel, statistics per tile
             y, stats = ops.conv3x3_direct_fwd(x, w2 if ld == 9 * Cin else _w_direct(lp, weight, dt), None,
@@ -208,18 +197,17 @@ class Conv3x3Fn(torch.autograd.Function):
         side = wgrad_fork(sink, (weight, bias), dy, x, weight, bias) if tw is not None else None
         with (torch.cuda.stream(side) if side is not None else contextlib.nullcontext()):
             Conv3x3Fn._wgrad(tw, tb, acc, dy2, x, stride, relu_in, ld, Cin, Cout)
-        dx = None
         if ctx.needs_input_grad[0]:
             return Conv3x3Fn._dgrad(ctx, dy, dy2, x, weight, stride, relu_in, lp, ld, B, H, W, Cin, Cout, dt, rets)
-        return dx, rets[0], rets[1], None, None, None, None, None
+        return None, rets[0], rets[1], None, None, None, None, None
 
     @staticmethod
     def _wgrad(tw, tb, acc, dy2, x, stride, relu_in, ld, Cin, Cout):
         if tw is not None:
             fuse_b = tb is not None and not acc  # the bias gradient rides on the same product
-            if _DIRECT and stride == 1 and ops.conv3x3_direct_wgrad_ok(x, Cout):
+            if stride == 1 and ops.conv3x3_direct_wgrad_ok(x, Cout):
                 dw2 = ops.conv3x3_direct_wgrad(dy2, x, relu_in, bias_out=tb if fuse_b else None)
-            elif _IMPLICIT and ops.conv3x3_implicit_ok(x, stride, Cout, wgrad=True):
+            elif ops.conv3x3_implicit_ok(x, stride, Cout, wgrad=True):
                 dw2 = ops.conv3x3_bwd_weight(dy2, x, stride, relu_in, bias_out=tb if fuse_b else None)
             else:
                 cols = ops.im2col3x3(x, stride, relu_in, ld)  # recomputed, not kept
@@ -236,33 +224,31 @@ class Conv3x3Fn(torch.autograd.Function):
 
     @staticmethod
     def _dgrad(ctx, dy, dy2, x, weight, stride, relu_in, lp, ld, B, H, W, Cin, Cout, dt, rets):
-        if True:
-            if stride == 1:
-                ld2 = ops.k_pad(9 * Cout, dt)
-                wd = _derived(lp, weight, f"c3d:{ld2}", dt, lambda w: ops.conv3x3_weight_pack(w, dt, 1, ld2),
-                              recipe=(1, ld2))
-                dy4 = dy.view(B, H, W, Cout)
-                if _DIRECT and ops.conv3x3_direct_ok(dy4, Cin):
-                    # the data gradient is the same direct kernel on dy with the flipped weight
-                    wdd = _derived(lp, weight, "c3dd", dt, lambda w: ops.conv3x3_weight_pack(w, dt, 1),
-                                   recipe=(1, None))
-                    dxr = ops.conv3x3_direct_fwd(dy4, wdd, None, relu_mask=x if relu_in else None)
-                    return dxr, rets[0], rets[1], None, None, None, None, None
-                if _IMPLICIT and ld2 == 9 * Cout and _fills_chip(dy4, 1, Cin) and \
-                        ops.conv3x3_implicit_ok(dy4, 1, Cin):
-                    # the ReLU in front of this convolution masks its data gradient in the epilogue
-                    dxr = ops.conv3x3_fwd(dy4, wd, None, 1, False, relu_mask=x if relu_in else None)
-                    return dxr, rets[0], rets[1], None, None, None, None, None
-                else:
-                    dcols = ops.im2col3x3(dy4, 1, False, ld2)
-                    dxr = ops.linear_fwd(dcols, wd, None, out_dtype=dt).view(B, H, W, Cin)
+        if stride == 1:
+            ld2 = ops.k_pad(9 * Cout, dt)
+            wd = _derived(lp, weight, f"c3d:{ld2}", dt, lambda w: ops.conv3x3_weight_pack(w, dt, 1, ld2),
+                          recipe=(1, ld2))
+            dy4 = dy.view(B, H, W, Cout)
+            if ops.conv3x3_direct_ok(dy4, Cin):
+                # the data gradient is the same direct kernel on dy with the flipped weight
+                wdd = _derived(lp, weight, "c3dd", dt, lambda w: ops.conv3x3_weight_pack(w, dt, 1),
+                               recipe=(1, None))
+                dxr = ops.conv3x3_direct_fwd(dy4, wdd, None, relu_mask=x if relu_in else None)
+                return dxr, rets[0], rets[1], None, None, None, None, None
+            if ld2 == 9 * Cout and _fills_chip(dy4, 1, Cin) and ops.conv3x3_implicit_ok(dy4, 1, Cin):
+                # the ReLU in front of this convolution masks its data gradient in the epilogue
+                dxr = ops.conv3x3_fwd(dy4, wd, None, 1, False, relu_mask=x if relu_in else None)
+                return dxr, rets[0], rets[1], None, None, None, None, None
             else:
-                w2 = _derived(lp, weight, f"c3:{ld}", dt, lambda w: ops.conv3x3_weight_pack(w, dt, 0, ld), recipe=(0, ld))
-                w2t = _derived(lp, weight, f"c3t:{ld}", dt, lambda w: ops.conv3x3_weight_pack(w, dt, 2, ld),
-                               recipe=(2, ld))
-                dcols = ops.linear_bwd_data(dy2, w2, w2t)  # [M_out, ld]
-                dxr = ops.col2im3x3(dcols, B, H, W, Cin, stride)
-            dx = ops.relu_bwd(x, dxr) if relu_in else dxr
+                dcols = ops.im2col3x3(dy4, 1, False, ld2)
+                dxr = ops.linear_fwd(dcols, wd, None, out_dtype=dt).view(B, H, W, Cin)
+        else:
+            w2 = _derived(lp, weight, f"c3:{ld}", dt, lambda w: ops.conv3x3_weight_pack(w, dt, 0, ld), recipe=(0, ld))
+            w2t = _derived(lp, weight, f"c3t:{ld}", dt, lambda w: ops.conv3x3_weight_pack(w, dt, 2, ld),
+                           recipe=(2, ld))
+            dcols = ops.linear_bwd_data(dy2, w2, w2t)  # [M_out, ld]
+            dxr = ops.col2im3x3(dcols, B, H, W, Cin, stride)
+        dx = ops.relu_bwd(x, dxr) if relu_in else dxr
         return dx, rets[0], rets[1], None, None, None, None, None
 
 

@@ -432,39 +432,10 @@ class BlockStackFn(torch.autograd.Function):
         dx = dx.contiguous()
         pending_tap = tap_g.pop(depth - 1, None)
         dx, dx_lp = ops.add_cast(dx, pending_tap, want_f32=True, lp_dtype=lp)
-        # Deferred weight gradients (bf16 engine, opt-in: _wgrad_group_size): a block's four dW
-        # products only have 48-108 output tiles, so alone (or in pairs) they must split K over the
-        # CUs and pay for fp32 slabs and their reduction.  Here the products of `grp` consecutive
-        # blocks are collected and run as ONE grouped launch with ~200 whole-K tiles — no slabs at
-        # all — on the weight-gradient side stream, beside the next blocks' data-gradient chain.
-        # Every block of a group keeps its own workspace (the products' dY operands live there)
-        # from a ring of 2 groups.
-        grp = _wgrad_group_size(dims, depth) if lp is not None else 0
-        if grp:
-            ring = [ctx.ws] + [torch.empty_like(ctx.ws) for _ in range(2 * grp - 1)]
-            descs = (_lib.GemmDesc * (4 * grp))()
-            gws_bytes, gws = 0, [None, None]
-            pending, keep, n_groups = [], [[], []], 0
-            flags = int(accumulate) | _lib.BWD_DEFER_WGRAD
-
-            def launch_group():
-                nonlocal n_groups, gws_bytes
-                n = 4 * len(pending)
-                slot = n_groups % 2
-                need = L.ssl4gie_gemm_tn_group_workspace_bytes(descs, n)
-                if need and (gws[slot] is None or gws[slot].numel() < need):
-                    gws[slot] = torch.empty(need, dtype=torch.uint8, device=x0.device)
-                _lib.check(L.ssl4gie_wgrad_group(descs, n, ops.ptr(gws[slot]), need, slot, st), "wgrad_group")
-                n_groups += 1
-                done = list(pending)
-                pending.clear()
-                if cfg.on_block_grads is not None:
-                    for j in done:
-                        cfg.on_block_grads(j)
-        nojoin = (not grp) and lp is not None and _BWD_NO_JOIN and depth > 1
+        nojoin = lp is not None and depth > 1
         if nojoin:
-            ring2 = [ctx.ws, torch.empty_like(ctx.ws)]
-            keep2 = [[], []]
+            ring = [ctx.ws, torch.empty_like(ctx.ws)]
+            keep = [[], []]
         for i in range(depth - 1, -1, -1):
             if i != depth - 1 and i in tap_g:
                 dx, dx_lp = ops.add_cast(dx, tap_g[i].contiguous(), want_f32=True, lp_dtype=lp)
@@ -481,36 +452,18 @@ class BlockStackFn(torch.autograd.Function):
             a = layout.struct(ctx.acts.data_ptr() + i * layout.total)
             dxn = torch.empty_like(x0)
             dxn_lp = torch.empty(x0.shape, dtype=lp, device=x0.device) if lp else None
-            if grp:
-                k = depth - 1 - i                      # blocks done so far
-                if k >= 2 * grp and k % grp == 0:      # about to reuse the workspaces of group k/grp - 2
-                    _lib.check(L.ssl4gie_wgrad_wait((k // grp) % 2, st), "wgrad_wait")
-                    keep[(k // grp) % 2].clear()
-                ws_i = ring[k % (2 * grp)]
-                _lib.check(L.ssl4gie_block_bwd(C.byref(dims), C.byref(ctx.wstructs[i]), C.byref(a),
-                                               C.byref(g), ctx.xs[i].data_ptr(), dx.data_ptr(),
-                                               ops.ptr(dx_lp), dxn.data_ptr(), ops.ptr(dxn_lp),
-                                               flags, ws_i.data_ptr(), st), f"block_bwd[{i}]")
-                _lib.check(L.ssl4gie_block_wgrad_descs(C.byref(dims), C.byref(a), C.byref(g), ops.ptr(dx_lp),
-                                                       ws_i.data_ptr(), int(accumulate),
-                                                       C.byref(descs, 4 * len(pending) * C.sizeof(_lib.GemmDesc))),
-                           f"block_wgrad_descs[{i}]")
-                pending.append(i)
-                keep[(k // grp) % 2] += [dx_lp, scratch]  # dY of dW_fc2 (+ frozen-parameter scratch)
-                if len(pending) == grp or i == 0:
-                    launch_group()
-            elif nojoin:
+            if nojoin:
                 # two workspaces in alternation: the caller's stream does not wait for this block's weight
                 # gradients (side stream) — only, two blocks later, before their operands are overwritten
                 k = (depth - 1 - i) % 2
                 _lib.check(L.ssl4gie_wgrad_wait(k, st), "wgrad_wait")
-                keep2[k].clear()
+                keep[k].clear()
                 _lib.check(L.ssl4gie_block_bwd(C.byref(dims), C.byref(ctx.wstructs[i]), C.byref(a),
                                                C.byref(g), ctx.xs[i].data_ptr(), dx.data_ptr(),
                                                ops.ptr(dx_lp), dxn.data_ptr(), ops.ptr(dxn_lp),
-                                               int(accumulate) | _lib.BWD_NO_JOIN | (k << 4), ring2[k].data_ptr(), st),
+                                               int(accumulate) | _lib.BWD_NO_JOIN | (k << 4), ring[k].data_ptr(), st),
                            f"block_bwd[{i}]")
-                keep2[k] += [dx, dx_lp, scratch]   # dY of dW_fc2 / frozen-parameter scratch: read on the side stream
+                keep[k] += [dx, dx_lp, scratch]   # dY of dW_fc2 / frozen-parameter scratch: read on the side stream
                 if cfg.on_block_grads is not None:
                     cfg.on_block_grads(i)
             else:
@@ -522,37 +475,12 @@ class BlockStackFn(torch.autograd.Function):
                 if cfg.on_block_grads is not None:
                     cfg.on_block_grads(i)
             dx, dx_lp = dxn, dxn_lp
-        if grp:  # the caller's stream continues after the last weight gradient; operands may go
-            for slot in range(min(n_groups, 2)):
-                _lib.check(L.ssl4gie_wgrad_wait(slot, st), "wgrad_wait")
-            keep[0].clear(); keep[1].clear()
         if nojoin:
             for slot in (0, 1):
                 _lib.check(L.ssl4gie_wgrad_wait(slot, st), "wgrad_wait")
-            keep2[0].clear(); keep2[1].clear()
+            keep[0].clear(); keep[1].clear()
         ctx.acts = ctx.xs = ctx.ws = ctx.keepalive = None
         return (dx, None) + tuple(returns)
-
-
-# SSL4GIE_BWD_NO_JOIN=0: every block's backward ends with the caller's stream waiting for its weight gradients
-# again (one workspace) — A/B
-_BWD_NO_JOIN = os.environ.get("SSL4GIE_BWD_NO_JOIN", "1") != "0"
-
-
-def _wgrad_group_size(dims, depth: int) -> int:
-    """blocks per grouped weight-gradient launch (SSL4GIE_WGRAD_GROUP = 1..4); 0 / unset = the
-    per-block paired launches.  Measured on the MAE ViT-B step (profiles/r02b_wgrad_group_ab.log):
-    with everything on one stream the grouped launches save 0.8 ms of slab traffic (25.55 -> 24.75 ms),
-    but beside the data-gradient chain the per-block pairs fill the CUs the chain leaves idle far
-    better (24.25 ms) than a burst of ~200 long workgroups every few blocks (24.6 ms) — so the
-    pairs stay the default and the groups are an option for single-stream runs."""
-    env = os.environ.get("SSL4GIE_WGRAD_GROUP", "").strip()
-    if not env:
-        return 0
-    D, F = dims.D, dims.F
-    if D % 4 or F % 4:
-        return 0
-    return max(0, min(int(env), 4, depth))
 
 
 def run_blocks(blocks: Sequence[nn.Module], x: torch.Tensor, heads: int, eps: float, dtype,

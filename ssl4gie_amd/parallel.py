@@ -317,8 +317,8 @@ class DataParallel(nn.Module):
             self._handles.append((h, g))
 
     def _wait_wgrad_stream(self):
-        """gradients of deferred weight-gradient groups are produced on the library's side stream
-        (ssl4gie_wgrad_group): the comm stream waits for the latest group of either slot"""
+        """the blocks' weight gradients are produced on the library's side stream without a join
+        (SSL4GIE_BWD_NO_JOIN): the comm stream waits for the latest block of either slot"""
         try:
             from . import _lib
             L = _lib.load()

@@ -9,6 +9,7 @@ Models/models.py:63-75 and Models/moco_v3/main_moco.py:185-187.
 """
 from __future__ import annotations
 
+import os
 import weakref
 
 import torch
@@ -52,8 +53,6 @@ class _StemCols:
 
 
 STEM_COLS = _StemCols()
-# SSL4GIE_STEM_DIRECT=0: the bf16 stem through the patch matrix again (A/B)
-_STEM_DIRECT = __import__("os").environ.get("SSL4GIE_STEM_DIRECT", "1") != "0"
 
 
 class StemConvFn(torch.autograd.Function):
@@ -65,7 +64,7 @@ class StemConvFn(torch.autograd.Function):
         imgs = imgs.contiguous().float()
         B = imgs.shape[0]
         Cout = weight.shape[0]
-        if _STEM_DIRECT and dtype == torch.bfloat16 and Cout == 64 and imgs.shape[1] == 3:
+        if dtype == torch.bfloat16 and Cout == 64 and imgs.shape[1] == 3:
             # bf16: no patch matrix — the image is packed once per batch (bf16, 4 channels, padded) and
             # read by the direct stem kernels (csrc/conv_direct.hip): 43 + 179 us instead of 740 + 454
             H, W = imgs.shape[2:]
@@ -307,11 +306,10 @@ def flush_batch_counts(model):
 # SSL4GIE_SYNCBN_FUSED=0: under SyncBatchNorm (world_size > 1) the bit-map backward, the stem's bn -> relu -> maxpool
 # pass and the momentum encoder's statistics-only + affine-epilogue products fall back to the separate passes
 # (rounds 4-5 behaviour: A/B of what BASELINE config 3 costs in its multi-rank form)
-_SYNC_FUSED = __import__("os").environ.get("SSL4GIE_SYNCBN_FUSED", "1") != "0"
-# SSL4GIE_BN_BITS=0: BatchNorm + residual + ReLU backward reads the ReLU output for its mask again (A/B)
-_BN_BITS = __import__("os").environ.get("SSL4GIE_BN_BITS", "1") != "0"
-# SSL4GIE_BN_XMASK=0: read the ReLU output for the mask of residual-free BatchNorm + ReLU layers again (A/B)
-_XMASK = __import__("os").environ.get("SSL4GIE_BN_XMASK", "1") != "0"
+_SYNC_FUSED = os.environ.get("SSL4GIE_SYNCBN_FUSED", "1") != "0"
+# SSL4GIE_BN_XMASK=0: read the ReLU output for the mask of residual-free BatchNorm + ReLU layers again (the remedy
+# BatchNormFn.backward names when an optimizer steps between a forward and its backward)
+_XMASK = os.environ.get("SSL4GIE_BN_XMASK", "1") != "0"
 
 
 def _bn_params_moved(epoch, gamma, beta):
@@ -384,7 +382,7 @@ class BatchNormFn(torch.autograd.Function):
         sync, group = _sync_group(bn)
         total = None  # SyncBatchNorm: 0-d device tensor, rows over all ranks
         bits = None
-        if training and not sync and _BN_BITS and relu and r2 is not None and stats is not None \
+        if training and not sync and relu and r2 is not None and stats is not None \
                 and x2.dtype == torch.bfloat16 and any(ctx.needs_input_grad):
             # bn3 of a bottleneck: the backward gets its ReLU mask as a bit map (1/16 of the output's bytes)
             mom = bn.momentum if bn.momentum is not None else 0.1
@@ -396,7 +394,7 @@ class BatchNormFn(torch.autograd.Function):
         elif training:
             mean_l, var_l = ops.bn_stats(x2, partials=stats)
             mean, rstd, total = sync_batch_stats(mean_l, var_l, x2.shape[0], bn, group)
-            if _BN_BITS and _SYNC_FUSED and relu and r2 is not None and x2.dtype == torch.bfloat16 \
+            if _SYNC_FUSED and relu and r2 is not None and x2.dtype == torch.bfloat16 \
                     and any(ctx.needs_input_grad):
                 # bn3 of a bottleneck under SyncBatchNorm: the same bit-map form as on one rank, fed with the
                 # GLOBAL statistics the exchange returned (round 6)
@@ -511,100 +509,9 @@ def bn_relu_maxpool_ok(x, bn, stats):
             and (_SYNC_FUSED or not _sync_group(bn)[0]) and x.shape[-1] % (8 if x.dtype == torch.bfloat16 else 4) == 0)
 
 
-# SSL4GIE_STEM_POOL_FUSED=0: bn1 / relu / maxpool of the ResNet stem as separate passes again (A/B)
-_STEM_POOL_FUSED = __import__("os").environ.get("SSL4GIE_STEM_POOL_FUSED", "1") != "0"
-
-
-class BnReluConv3x3Fn(torch.autograd.Function):
-    """torchvision Bottleneck's bn1 -> relu -> conv2 (3x3, stride 1, no bias) with the BatchNorm applied inside the
-    direct convolution kernels: the statistics come from conv1's epilogue partials, the forward and the weight
-    gradient normalise (+ ReLU) their halo between its global load and its LDS write, the normalised map is never
-    written; the data gradient of conv2 goes through BatchNorm + ReLU backward with the mask rebuilt from the
-    BatchNorm input (ops.bn_bwd_xmask).  Values equal BatchNormFn + Conv3x3Fn bit for bit.
-    Returns (y, statistics of y or None)."""
-
-    @staticmethod
-    def forward(ctx, x, gamma, beta, bn, in_stats, weight, sink: GradSink, lp: LPCache, want_stats):
-        from .dpt_engine import _derived
-        B, H, W, Cin = x.shape
-        dt = x.dtype
-        mom = bn.momentum if bn.momentum is not None else 0.1
-        coef, mean, rstd = ops.bn_coef_partials(in_stats, B * H * W, gamma.detach() if gamma is not None else None,
-                                                beta.detach() if beta is not None else None, bn.running_mean,
-                                                bn.running_var, mom, bn.eps)
-        if bn.num_batches_tracked is not None:
-            _count_batch(bn)
-        w2 = _derived(lp, weight, f"c3:{9 * Cin}", dt, lambda w: ops.conv3x3_weight_pack(w, dt, 0, 9 * Cin),
-                      recipe=(0, 9 * Cin))
-        x = x.contiguous()
-        r = ops.conv3x3_direct_fwd(x, w2, None, True, colstats=want_stats, in_coef=coef)
-        y, stats = r if want_stats else (r, None)
-        ctx.save_for_backward(x, gamma, beta, mean, rstd, coef, weight)
-        ctx.cfg = (sink, lp)
-        ctx.wepoch = weights_epoch()   # dx rebuilds the ReLU mask from gamma / beta, dW uses the saved `coef`
-        if stats is not None:
-            ctx.mark_non_differentiable(stats)
-        ctx.set_materialize_grads(False)
-        return y, stats
-
-    @staticmethod
-    def backward(ctx, dy, *unused):
-        if dy is None:
-            return (None,) * 9
-        from .dpt_engine import _derived, _write_grad
-        x, gamma, beta, mean, rstd, coef, weight = ctx.saved_tensors
-        sink, lp = ctx.cfg
-        if _bn_params_moved(ctx.wepoch, gamma, beta):
-            raise RuntimeError("BatchNorm parameters were updated between this forward and its backward: the ReLU "
-                               "mask rebuilt from them would disagree with the forward (set SSL4GIE_BN_CONV_FUSED=0)")
-        B, H, W, Cin = x.shape
-        Cout = weight.shape[0]
-        dt = x.dtype
-        dy = dy.contiguous()
-        (tw, tg, tb), acc, rets = sink.plan([weight, gamma, beta])
-        if tw is not None:  # dW against the normalised operand, rebuilt on the way in
-            dw2 = ops.conv3x3_direct_wgrad(dy.view(-1, Cout), x, True, in_coef=coef)
-            if tw.is_contiguous():
-                ops.conv3x3_wgrad_unpack(dw2, tw, acc)
-            else:
-                _write_grad(tw, dw2.view(Cout, 3, 3, Cin).permute(0, 3, 1, 2), acc)
-        dx = None
-        if ctx.needs_input_grad[0]:
-            wdd = _derived(lp, weight, "c3dd", dt, lambda w: ops.conv3x3_weight_pack(w, dt, 1), recipe=(1, None))
-            dz = ops.conv3x3_direct_fwd(dy.view(B, H, W, Cout), wdd, None)   # gradient at the ReLU's output
-            dx = _bn_backward(dz.view(-1, Cin), x.view(-1, Cin), ("x", None), gamma, beta, mean, rstd, False, (tg, tb),
-                              acc)[0].view(B, H, W, Cin)
-        return dx, rets[1], rets[2], None, None, rets[0], None, None, None
-
-
-def bn_relu_conv3x3_ok(x, bn, in_stats, conv, need_grad):
-    """whether BnReluConv3x3Fn applies: bf16 map on the direct kernels (forward, data gradient and — when a
-    backward pass will run — weight gradient), stride 1, no bias, training-mode statistics from the producing
-    GEMM's partials, one process (SyncBatchNorm exchanges between statistics and apply)"""
-    from .dpt_engine import _DIRECT
-    if not (_BN_CONV_FUSED and _DIRECT and in_stats is not None and conv.bias is None and conv.stride[0] == 1):
-        return False
-    if not (bn.training or bn.running_mean is None) or _sync_group(bn)[0]:
-        return False
-    Cout, Cin = conv.weight.shape[:2]
-    # Cout <= 128 (layer1 / layer2): a workgroup of the direct kernel owns 64 couts and stages the whole halo, so
-    # Cout / 64 workgroups would each normalise the same halo again — measured at 256 / 512 couts the kernels lose
-    # more (+20 us per launch) than the BatchNorm pass costs (profiles/r04at)
-    if x.dtype != torch.bfloat16 or Cin % 64 != 0 or Cout > 128 or not ops.conv3x3_direct_ok(x.contiguous(), Cout):
-        return False
-    if need_grad:
-        B, H, W, _ = x.shape
-        dy_like = torch.empty((B, H, W, Cout), dtype=x.dtype, device="meta")  # shape / dtype only
-        return ops.conv3x3_direct_wgrad_ok(x.contiguous(), Cout) and ops.conv3x3_direct_ok(dy_like, Cin)
-    return True
-
-
-# SSL4GIE_BN_CONV_FUSED=1 (opt-in): bn1 / relu applied inside the Bottleneck's 3x3 convolution.  Correct (bit-identical,
-# tests/test_gpu_resnet.py) and measured NULL on the MoCo-R50 step (62.02 vs 61.96 ms, profiles/r04av): the
-# BatchNorm pass it removes is pure HBM streaming (19 us per launch on these narrow maps), while the normalisation
-# inside the halo staging is VALU work serialised with the MFMA phases of a kernel that is LDS- / issue-bound
-# (+11 .. +21 us per launch, forward and weight gradient) — so the default stays the separate pass.
-_BN_CONV_FUSED = __import__("os").environ.get("SSL4GIE_BN_CONV_FUSED", "0") == "1"
+# SSL4GIE_STEM_POOL_FUSED=0: bn1 / relu / maxpool of the ResNet stem as separate passes again (the remedy
+# BnReluMaxPoolFn.backward names when an optimizer steps between a forward and its backward)
+_STEM_POOL_FUSED = os.environ.get("SSL4GIE_STEM_POOL_FUSED", "1") != "0"
 
 
 class AvgPoolFn(torch.autograd.Function):

@@ -32,6 +32,22 @@ def test_library_exports_every_declared_symbol():
     assert _lib.load().ssl4gie_abi_version() == _lib.ABI_VERSION
 
 
+def test_readme_lists_exactly_the_environment_switches_that_are_read():
+    """README's "Environment switches" table == the SSL4GIE_* names in os.environ / getenv reads under ssl4gie_amd/"""
+    read = set()
+    for d, _, files in os.walk(os.path.join(ROOT, "ssl4gie_amd")):
+        for f in files:
+            if f.endswith((".py", ".hip", ".h")):
+                with open(os.path.join(d, f), encoding="utf-8") as fh:
+                    read |= set(re.findall(r'(?:environ|getenv)[^\n"]*"(SSL4GIE_[A-Z0-9_]+)"', fh.read()))
+    with open(os.path.join(ROOT, "README.md"), encoding="utf-8") as fh:
+        section = fh.read().split("## Environment switches")[1].split("\n## ")[0]
+    listed = set()
+    for row in re.findall(r"^\|([^|]*(?:\\\|[^|]*)*)\|", section, re.M):
+        listed |= set(re.findall(r"SSL4GIE_[A-Z0-9_]+", row))
+    assert read and read == listed, (sorted(read - listed), sorted(listed - read))
+
+
 def test_graft_entry_build_runs_clean():
     """the documented build command (README) must exit 0: make is a no-op when up to date"""
     sys.path.insert(0, ROOT)

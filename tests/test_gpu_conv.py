@@ -114,22 +114,28 @@ def test_conv3x3_relu_mask_epilogue():
     assert rel_err(dx, xr.grad.permute(0, 2, 3, 1)) < 4e-3
 
 
-def test_conv3x3_fn_matches_materialised_path(monkeypatch):
-    """Conv3x3Fn forward + backward: implicit path vs SSL4GIE_IMPLICIT_CONV=0 on one layer"""
-    from ssl4gie_amd import dpt_engine
+def test_conv3x3_fn_matches_materialised_path():
+    """Conv3x3Fn forward + backward on one layer vs the same layer through materialised patch matrices"""
+    from ssl4gie_amd import dpt_engine, ops
     from ssl4gie_amd.engine import GradSink, LPCache
     x, w, b = _case(4, 16, 16, 64, 128, 30)
     dy = torch.randn(4, 16, 16, 128, generator=G(33)).to(BF).to(DEV)
-    out = {}
-    for flag in (True, False):
-        monkeypatch.setattr(dpt_engine, "_IMPLICIT", flag)
-        wp = torch.nn.Parameter(w.float().to(DEV))
-        bp = torch.nn.Parameter(b.to(DEV))
-        xp = x.to(DEV).requires_grad_(True)
-        y = dpt_engine.Conv3x3Fn.apply(xp, wp, bp, 1, True, GradSink(None), LPCache())
-        y.backward(dy)
-        out[flag] = (y.detach().float(), xp.grad.float(), wp.grad, bp.grad)
-    for a, c in zip(out[True], out[False]):
+    wp = torch.nn.Parameter(w.float().to(DEV))
+    bp = torch.nn.Parameter(b.to(DEV))
+    xp = x.to(DEV).requires_grad_(True)
+    y = dpt_engine.Conv3x3Fn.apply(xp, wp, bp, 1, True, GradSink(None), LPCache())
+    y.backward(dy)
+    got = (y.detach().float(), xp.grad.float(), wp.grad, bp.grad)
+    # the materialised side: patch matrix + GEMM for y, dW (+ db on the same product) and dx
+    xd, wf, dy2 = x.to(DEV), w.float().to(DEV), dy.view(-1, 128)
+    cols = ops.im2col3x3(xd, 1, True, 9 * 64)
+    ym = ops.linear_fwd(cols, ops.conv3x3_weight_pack(wf, BF, 0, 9 * 64), b.to(DEV), out_dtype=BF).view(4, 16, 16, 128)
+    db = torch.empty(128, device=DEV)
+    dw = ops.linear_bwd_weight(dy2, cols, bias_out=db).view(128, 3, 3, 64).permute(0, 3, 1, 2)
+    dcols = ops.im2col3x3(dy, 1, False, 9 * 128)
+    dxr = ops.linear_fwd(dcols, ops.conv3x3_weight_pack(wf, BF, 1, 9 * 128), None, out_dtype=BF).view(4, 16, 16, 64)
+    want = (ym.float(), ops.relu_bwd(xd, dxr).float(), dw, db)
+    for a, c in zip(got, want):
         assert rel_err(a, c) < 3e-3
 
 

@@ -551,36 +551,6 @@ def test_weight_gradient_group_matches_single_products(T, shapes):
             assert torch.equal(b.cpu().double(), 2 * rb)
 
 
-@pytest.mark.parametrize("group", [1, 2, 3])
-def test_block_stack_deferred_weight_gradients_match_inline(group, monkeypatch):
-    """BlockStackFn with the weight gradients of `group` blocks collected into one launch on the side
-    stream (SSL4GIE_WGRAD_GROUP) == the per-block paired launches: same outputs, same gradients
-    (bf16 engine; the products are the same sums in a different split-K order)"""
-    import torch.nn as nn
-    from ssl4gie_amd import engine
-    from ssl4gie_amd.Models.vit_layers import Block
-    B, N, D, H, depth = 8, 64, 128, 4, 5
-    torch.manual_seed(3)
-    blocks = nn.ModuleList([Block(D, H, 4.0, qkv_bias=True, norm_layer=lambda d: nn.LayerNorm(d, eps=1e-6))
-                            for _ in range(depth)]).to(DEV)
-    x = torch.randn(B, N, D, generator=G(5)).to(DEV)
-    wgt = torch.randn(B, N, D, generator=G(6)).to(DEV)
-    res = {}
-    for g in (0, group):
-        monkeypatch.setenv("SSL4GIE_WGRAD_GROUP", str(g))
-        for p in blocks.parameters():
-            p.grad = None
-        xi = x.clone().requires_grad_(True)
-        y, taps = engine.run_blocks(blocks, xi, H, 1e-6, BF, engine.GradSink(None), taps=(1,))
-        ((y * wgt).sum() + taps[0].sum()).backward()
-        torch.cuda.synchronize()
-        res[g] = (y.detach().clone(), xi.grad.clone(), [p.grad.clone() for p in blocks.parameters()])
-    assert torch.equal(res[0][0], res[group][0])
-    assert rel_err(res[group][1], res[0][1]) < 1e-6
-    for a, b in zip(res[group][2], res[0][2]):
-        assert rel_err(a, b) < 2e-5
-
-
 def test_compute_cus_setting_changes_grids_not_results():
     from ssl4gie_amd import _lib, ops
     L = _lib.load()
