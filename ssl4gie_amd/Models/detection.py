@@ -27,7 +27,7 @@ import torch.nn as nn
 import torch.nn.functional as F_
 
 from .. import ops
-from ..engine import EngineModule, LinearFn, weights_epoch
+from ..engine import EngineModule, LinearFn
 from ..dpt_engine import _write_grad
 
 BBOX_XFORM_CLIP = math.log(1000.0 / 16)
@@ -254,24 +254,17 @@ class PairLinearFn(torch.autograd.Function):
         assert x2.dtype == dtype
         n1, n2, k = w1.shape[0], w2.shape[0], x2.shape[1]
         npad = -(-(n1 + n2) // 8) * 8
-        key = (id(w1), "pair")
-        ver = (w1._version, w1.data_ptr(), w2._version, w2.data_ptr(), b1._version, b2._version, dtype, weights_epoch())
-        ent = lp._c.get(key)
-        if ent is None or ent[0] != ver:
-            with torch.no_grad():
-                w = torch.zeros(npad, k, dtype=torch.float32, device=x2.device)
-                w[:n1] = w1.detach().view(n1, k)
-                w[n1:n1 + n2] = w2.detach().view(n2, k)
-                b = torch.zeros(npad, dtype=torch.float32, device=x2.device)
-                b[:n1] = b1.detach()
-                b[n1:n1 + n2] = b2.detach()
-                if dtype != torch.float32:
-                    w = ops.cast(w, dtype)
-            ent = (ver, w, b)
-            lp._c[key] = ent
+
+        def pack(w1, w2, b1, b2):
+            w = torch.zeros(npad, k, dtype=torch.float32, device=x2.device)
+            w[:n1], w[n1:n1 + n2] = w1.view(n1, k), w2.view(n2, k)
+            b = torch.zeros(npad, dtype=torch.float32, device=x2.device)
+            b[:n1], b[n1:n1 + n2] = b1, b2
+            return (w if dtype == torch.float32 else ops.cast(w, dtype)), b
+        wcat, bcat = lp.derived((w1, w2, b1, b2), "pair", dtype, pack)
         ctx.save_for_backward(x2, w1, b1, w2, b2)
-        ctx.cfg = (ent[1], dtype, sink, x.shape, n1, n2)
-        return ops.linear_fwd(x2, ent[1], ent[2], out_dtype=torch.float32)
+        ctx.cfg = (wcat, dtype, sink, x.shape, n1, n2)
+        return ops.linear_fwd(x2, wcat, bcat, out_dtype=torch.float32)
 
     @staticmethod
     def backward(ctx, dy):

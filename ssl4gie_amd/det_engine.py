@@ -14,7 +14,7 @@ from __future__ import annotations
 import torch
 
 from . import ops
-from .dpt_engine import _derived, _write_grad
+from .dpt_engine import _write_grad
 from .engine import GradSink, LPCache
 
 
@@ -54,7 +54,7 @@ def _hwc(lp, p):
     v = p.detach().permute(1, 2, 0)
     if v.is_contiguous() and v.dtype == torch.float32:
         return v
-    return _derived(lp, p, "mapln", torch.float32, lambda q: q.permute(1, 2, 0))
+    return lp.derived(p, "mapln", torch.float32, lambda q: q.permute(1, 2, 0))
 
 
 class MapLayerNormFn(torch.autograd.Function):

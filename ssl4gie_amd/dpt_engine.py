@@ -1,105 +1,36 @@
 """Autograd nodes of the DPT dense decoder on the HIP engine.
 
 Maps are channels-last ([B, H, W, C], the token-major layout of the ViT carried to the upsampled
-resolutions) in the engine's operand type.  Every convolution is a GEMM of libssl4gie_hip.so:
+resolutions) in the engine's operand type.  Every convolution runs on libssl4gie_hip.so:
   * Conv2d(k=1)            -> engine.LinearFn on [B*H*W, Cin]
   * ConvTranspose2d(k = s) -> GEMM against W[(i, j, co), ci] + pixel-shuffle scatter
-  * Conv2d(k=3, pad=1)     -> GEMM over the (dy, dx, ci) patch matrix (ssl4gie_im2col3x3); the data
-                              gradient is the same product against the flipped kernel (stride 1)
-                              or the patch-matrix transpose (stride 2); the weight gradient is the
-                              split-K TN product dY^T cols with the bias gradient fused in.
-The patch matrix is recomputed in backward instead of being kept (it is 9x the activation).
-Weight re-layouts (a few MB, once per optimizer step) and the scatter of dW back into the
-parameter's [Cout, Cin, 3, 3] layout are host-side tensor plumbing; all activation-sized work is
-HIP.  Reference: Models/DPT_decoder.py (lines cited per node).
+  * Conv2d(k=3, pad=1)     -> Conv3x3Fn, every 3x3 layer of the package (ResNet-50 bottlenecks, this decoder, ConvStem,
+                              FPN and RPN heads) on one of three kernel families: direct halo-in-LDS kernels, 256x256
+                              GEMMs that gather the (dy, dx, ci) patch matrix in the kernel, plain GEMMs over a
+                              materialised one (recomputed in backward: it is 9x the activation).  Which one the
+                              forward, the weight gradient (bias gradient fused in) and the data gradient (flipped
+                              kernel at stride 1, patch-matrix transpose at stride 2) take: conv_plan.conv3x3_plan.
+Weight re-layouts (a few MB, once per optimizer step: LPCache.derived) and the scatter of dW back into the parameter's
+[Cout, Cin, 3, 3] layout are small launches; all activation-sized work is HIP.  Reference: Models/DPT_decoder.py.
 """
 from __future__ import annotations
 
 import contextlib
-import weakref
 
 import torch
 
 from . import ops
-from .engine import GradSink, LPCache, touched_since, weights_epoch, wgrad_fork
+from .conv_plan import conv3x3_plan
+from .engine import GradSink, LPCache, wgrad_fork
 
 
-def _fills_chip(x, stride, n_out):
-    """the gathered NT kernel only exists with 256x256 tiles: below ~100 tiles (ResNet layer4's
-    7x7 maps) the 128x128 kernel over a (small) materialised patch matrix keeps more CUs busy"""
-    B, H, W, _ = x.shape
-    Ho, Wo = ops.conv_out_hw(H, W, stride)
-    return ((B * Ho * Wo + 255) // 256) * ((n_out + 255) // 256) >= 96
-
-
-def _w_direct(lp, weight, dtype):
-    """[Cout, 9 Cin] operand of the direct kernels (taps row-major, channels innermost, unpadded)"""
-    Cout = weight.shape[0]
-    return _derived(lp, weight, "c3x", dtype, lambda w: ops.conv3x3_weight_pack(w, dtype, 0), recipe=(0, None))
-
-
-def _derived(lp: LPCache, p: torch.Tensor, tag: str, dtype, fn, recipe=None):
-    """operand-type tensor derived from parameter `p` by `fn`, cached until p changes.
-    recipe = (mode, ld) of ops.conv3x3_weight_pack when `fn` is exactly that: the image is then also refreshed,
-    together with every other stale one, by ONE launch at the top of the next forward (refresh_conv_operands)."""
-    key = (id(p), tag)
-    ver = (p._version, p.data_ptr(), dtype, weights_epoch())
-    if recipe is not None:
-        rec = lp.__dict__.setdefault("_conv_recipes", {})
-        if key not in rec:
-            rec[key] = (weakref.ref(p), recipe[0], recipe[1], dtype)
-    ent = lp._c.get(key)
-    if ent is None or ent[0] != ver:
-        with torch.no_grad():
-            t = fn(p.detach())
-            if t.dtype != dtype:
-                t = ops.cast(t.contiguous(), dtype)
-            else:
-                t = t.contiguous()
-        ent = (ver, t)
-        lp._c[key] = ent
-    return ent[1]
-
-
-def refresh_conv_operands(lp: LPCache):
-    """Re-pack every stale 3x3-convolution operand image registered with _derived(recipe=...) in ONE launch
-    (ssl4gie_conv3x3_weight_pack_batch) — a ResNet-50 otherwise issues ~60 small pack kernels per optimizer step,
-    each in front of its convolution.  Runs when the fused optimizers have moved the weights (the engine's
-    weights epoch); images made stale any other way are re-packed lazily, one by one, as before."""
-    rec = lp.__dict__.get("_conv_recipes")
-    if not rec:
-        return
-    epoch = weights_epoch()
-    seen = lp.__dict__.get("_conv_epoch")
-    if seen == epoch:
-        return
-    lp.__dict__["_conv_epoch"] = epoch
-    moved = touched_since(seen) if seen is not None else None   # None: any parameter may have moved
-    items, dead = [], []
-    for key, (ref, mode, ld, dtype) in rec.items():
-        p = ref()
-        if p is None:
-            dead.append(key)
-            continue
-        ver = (p._version, p.data_ptr(), dtype, epoch)
-        ent = lp._c.get(key)
-        if ent is not None and ent[0] == ver:
-            continue
-        if ent is not None and moved is not None and key[0] not in moved and ent[0][:3] == ver[:3]:
-            lp._c[key] = (ver, ent[1])   # only the epoch moved, and not for this parameter: the image stands
-            continue
-        if not p.is_cuda or p.dtype != torch.float32 or not p.is_contiguous() or p.dim() != 4:
-            continue
-        items.append((key, ver, p, mode, ld, dtype))
-    for key in dead:
-        rec.pop(key, None)
-        lp._c.pop(key, None)
-    for dtype in {it[5] for it in items}:
-        group = [it for it in items if it[5] == dtype]
-        outs = ops.conv3x3_weight_pack_batch([it[2].detach() for it in group], dtype, [it[3] for it in group],
-                                             [it[4] for it in group])
-        for it, t in zip(group, outs):
-            lp._c[it[0]] = (it[1], t)
+def _operand(lp: LPCache, weight, dtype, mode, ld=None):
+    """cached operand image ops.conv3x3_weight_pack(weight, dtype, mode, ld); ld None: unpadded rows, what the direct
+    kernels read — for mode 0 that is the GEMM's image itself wherever its rows need no padding"""
+    if ld is None and mode == 0 and ops.k_pad(9 * weight.shape[1], dtype) == 9 * weight.shape[1]:
+        ld = 9 * weight.shape[1]
+    tag = ("c3x", "c3dd")[mode] if ld is None else f"{('c3', 'c3d', 'c3t')[mode]}:{ld}"
+    return lp.derived(weight, tag, dtype, lambda w: ops.conv3x3_weight_pack(w, dtype, mode, ld), recipe=(mode, ld))
 
 
 def _pad_cols(m: torch.Tensor, ld: int) -> torch.Tensor:
@@ -135,51 +66,32 @@ class TokensToMapFn(torch.autograd.Function):
 class Conv3x3Fn(torch.autograd.Function):
     """y = conv3x3(act(x)) + bias, pad 1, stride 1 or 2; act = ReLU if relu_in
     (layer*_rn :412-447, ResidualConvUnit_custom :212-233, output_conv.0/.2 :469-478,
-    act_postprocess42.1 :397-403)."""
+    act_postprocess42.1 :397-403).  Kernels as conv_plan.conv3x3_plan says."""
 
     @staticmethod
     def forward(ctx, x, weight, bias, stride, relu_in, sink: GradSink, lp: LPCache, want_stats=False):
         """want_stats: also return BatchNorm partial statistics of y (see engine.LinearFn) or None"""
         B, H, W, Cin = x.shape
-        Cout = weight.shape[0]
-        dt = x.dtype
-        ld = ops.k_pad(9 * Cin, dt)
-        w2 = _derived(lp, weight, f"c3:{ld}", dt, lambda w: ops.conv3x3_weight_pack(w, dt, 0, ld), recipe=(0, ld))
+        Cout, dt = weight.shape[0], x.dtype
+        plan = conv3x3_plan(B, H, W, Cin, Cout, stride, dt, bias is not None, bool(want_stats))
+        w2 = _operand(lp, weight, dt, 0, plan.ld)
         x = x.contiguous()
         b = bias.detach() if bias is not None else None
         ctx.save_for_backward(x, weight, bias)
-        ctx.cfg = (stride, relu_in, sink, lp, ld)
-        implicit = ld == 9 * Cin and ops.conv3x3_implicit_ok(x, stride, Cout)
-        Ho, Wo = ops.conv_out_hw(H, W, stride)
-        stats = None
-        # direct kernel: where it is ahead of the gathered GEMM (ops.conv3x3_direct_ok), and instead
-        # of a materialised patch matrix where the gathered GEMM does not apply (layer1_rn: Cin = 96)
-        direct = stride == 1 and (ops.conv3x3_direct_ok(x, Cout) or
-                                  (not implicit and ops.conv3x3_direct_supported(x, Cout)))
-        if direct and want_stats and b is None:
-            # narrow ResNet layers (64 -> 64 @56, 128 -> 128 @28): direct kernel, statistics per tile
-            y, stats = ops.conv3x3_direct_fwd(x, w2 if ld == 9 * Cin else _w_direct(lp, weight, dt), None,
-                                              relu_in, colstats=True)
-            ctx.mark_non_differentiable(stats)
-            ctx.set_materialize_grads(False)  # no zero tensor for the statistics' (absent) gradient
-        elif want_stats and b is None and dt == torch.bfloat16 and Cout % 8 == 0 and ld % 64 == 0:
-            # the statistics only exist in the 256x256 kernel: taken whatever the tile count
-            if implicit:
-                y, stats = ops.conv3x3_fwd(x, w2, None, stride, relu_in, colstats=True)
-            else:
-                y, stats = ops.linear_fwd(ops.im2col3x3(x, stride, relu_in, ld), w2, None, out_dtype=dt,
-                                          colstats=True)
-                y = y.view(B, Ho, Wo, Cout)
-            ctx.mark_non_differentiable(stats)
-            ctx.set_materialize_grads(False)  # no zero tensor for the statistics' (absent) gradient
-        elif direct:
-            # narrow layer (output_conv.2: 128 -> 32): halo-in-LDS kernel instead of a GEMM tile that
-            # would be 7/8 padding
-            y = ops.conv3x3_direct_fwd(x, w2 if ld == 9 * Cin else _w_direct(lp, weight, dt), b, relu_in)
-        elif implicit and _fills_chip(x, stride, Cout):
-            y = ops.conv3x3_fwd(x, w2, b, stride, relu_in)  # patch matrix gathered in the GEMM
+        ctx.cfg = (stride, relu_in, sink, lp, plan)
+        if plan.fwd == "direct":
+            out = ops.conv3x3_direct_fwd(x, _operand(lp, weight, dt, 0), b, relu_in, colstats=plan.fwd_stats)
+        elif plan.fwd == "gather":  # patch matrix gathered in the GEMM
+            out = ops.conv3x3_fwd(x, w2, b, stride, relu_in, colstats=plan.fwd_stats)
         else:
-            y = ops.linear_fwd(ops.im2col3x3(x, stride, relu_in, ld), w2, b, out_dtype=dt).view(B, Ho, Wo, Cout)
+            out = ops.linear_fwd(ops.im2col3x3(x, stride, relu_in, plan.ld), w2, b, out_dtype=dt,
+                                 colstats=plan.fwd_stats)
+        y, stats = out if plan.fwd_stats else (out, None)
+        if plan.fwd_stats:
+            ctx.mark_non_differentiable(stats)
+            ctx.set_materialize_grads(False)  # no zero tensor for the statistics' (absent) gradient
+        if y.dim() == 2:  # the plain GEMM's [pixels, Cout]
+            y = y.view(B, *ops.conv_out_hw(H, W, stride), Cout)
         return (y, stats) if want_stats else y
 
     @staticmethod
@@ -187,32 +99,28 @@ class Conv3x3Fn(torch.autograd.Function):
         if dy is None:  # the map itself was not used downstream (gradients are not materialised)
             return (None,) * 8
         x, weight, bias = ctx.saved_tensors
-        stride, relu_in, sink, lp, ld = ctx.cfg
-        B, H, W, Cin = x.shape
-        Cout = weight.shape[0]
-        dt = x.dtype
+        stride, relu_in, sink, lp, plan = ctx.cfg
         dy = dy.contiguous()
-        dy2 = dy.view(-1, Cout)
         (tw, tb), acc, rets = sink.plan([weight, bias])
         side = wgrad_fork(sink, (weight, bias), dy, x, weight, bias) if tw is not None else None
         with (torch.cuda.stream(side) if side is not None else contextlib.nullcontext()):
-            Conv3x3Fn._wgrad(tw, tb, acc, dy2, x, stride, relu_in, ld, Cin, Cout)
-        if ctx.needs_input_grad[0]:
-            return Conv3x3Fn._dgrad(ctx, dy, dy2, x, weight, stride, relu_in, lp, ld, B, H, W, Cin, Cout, dt, rets)
-        return None, rets[0], rets[1], None, None, None, None, None
+            Conv3x3Fn._wgrad(tw, tb, acc, dy.view(-1, weight.shape[0]), x, stride, relu_in, plan)
+        dx = Conv3x3Fn._dgrad(dy, x, weight, stride, relu_in, lp, plan) if ctx.needs_input_grad[0] else None
+        return dx, rets[0], rets[1], None, None, None, None, None
 
     @staticmethod
-    def _wgrad(tw, tb, acc, dy2, x, stride, relu_in, ld, Cin, Cout):
+    def _wgrad(tw, tb, acc, dy2, x, stride, relu_in, plan):
         if tw is not None:
+            Cout, Cin = tw.shape[:2]
             fuse_b = tb is not None and not acc  # the bias gradient rides on the same product
-            if stride == 1 and ops.conv3x3_direct_wgrad_ok(x, Cout):
-                dw2 = ops.conv3x3_direct_wgrad(dy2, x, relu_in, bias_out=tb if fuse_b else None)
-            elif ops.conv3x3_implicit_ok(x, stride, Cout, wgrad=True):
-                dw2 = ops.conv3x3_bwd_weight(dy2, x, stride, relu_in, bias_out=tb if fuse_b else None)
+            bias_out = tb if fuse_b else None
+            if plan.wgrad == "direct":
+                dw2 = ops.conv3x3_direct_wgrad(dy2, x, relu_in, bias_out=bias_out)
+            elif plan.wgrad == "gather":
+                dw2 = ops.conv3x3_bwd_weight(dy2, x, stride, relu_in, bias_out=bias_out)
             else:
-                cols = ops.im2col3x3(x, stride, relu_in, ld)  # recomputed, not kept
-                dw2 = ops.linear_bwd_weight(dy2, cols, bias_out=tb if fuse_b else None)
-                del cols
+                dw2 = ops.linear_bwd_weight(dy2, ops.im2col3x3(x, stride, relu_in, plan.ld),  # recomputed, not kept
+                                            bias_out=bias_out)
             if tb is not None and not fuse_b:
                 ops.colsum(dy2, out=tb, accumulate=True)
             if dw2.dtype == torch.float32 and dw2.stride(1) == 1 and tw.is_contiguous():
@@ -223,33 +131,22 @@ class Conv3x3Fn(torch.autograd.Function):
             ops.colsum(dy2, out=tb, accumulate=acc)
 
     @staticmethod
-    def _dgrad(ctx, dy, dy2, x, weight, stride, relu_in, lp, ld, B, H, W, Cin, Cout, dt, rets):
-        if stride == 1:
-            ld2 = ops.k_pad(9 * Cout, dt)
-            wd = _derived(lp, weight, f"c3d:{ld2}", dt, lambda w: ops.conv3x3_weight_pack(w, dt, 1, ld2),
-                          recipe=(1, ld2))
-            dy4 = dy.view(B, H, W, Cout)
-            if ops.conv3x3_direct_ok(dy4, Cin):
-                # the data gradient is the same direct kernel on dy with the flipped weight
-                wdd = _derived(lp, weight, "c3dd", dt, lambda w: ops.conv3x3_weight_pack(w, dt, 1),
-                               recipe=(1, None))
-                dxr = ops.conv3x3_direct_fwd(dy4, wdd, None, relu_mask=x if relu_in else None)
-                return dxr, rets[0], rets[1], None, None, None, None, None
-            if ld2 == 9 * Cout and _fills_chip(dy4, 1, Cin) and ops.conv3x3_implicit_ok(dy4, 1, Cin):
-                # the ReLU in front of this convolution masks its data gradient in the epilogue
-                dxr = ops.conv3x3_fwd(dy4, wd, None, 1, False, relu_mask=x if relu_in else None)
-                return dxr, rets[0], rets[1], None, None, None, None, None
-            else:
-                dcols = ops.im2col3x3(dy4, 1, False, ld2)
-                dxr = ops.linear_fwd(dcols, wd, None, out_dtype=dt).view(B, H, W, Cin)
-        else:
-            w2 = _derived(lp, weight, f"c3:{ld}", dt, lambda w: ops.conv3x3_weight_pack(w, dt, 0, ld), recipe=(0, ld))
-            w2t = _derived(lp, weight, f"c3t:{ld}", dt, lambda w: ops.conv3x3_weight_pack(w, dt, 2, ld),
-                           recipe=(2, ld))
-            dcols = ops.linear_bwd_data(dy2, w2, w2t)  # [M_out, ld]
+    def _dgrad(dy, x, weight, stride, relu_in, lp, plan):
+        B, H, W, Cin = x.shape
+        Cout, dt = weight.shape[0], x.dtype
+        if plan.dgrad == "col2im":
+            w2, w2t = _operand(lp, weight, dt, 0, plan.ld), _operand(lp, weight, dt, 2, plan.ld)
+            dcols = ops.linear_bwd_data(dy.view(-1, Cout), w2, w2t)  # [M_out, ld]
             dxr = ops.col2im3x3(dcols, B, H, W, Cin, stride)
-        dx = ops.relu_bwd(x, dxr) if relu_in else dxr
-        return dx, rets[0], rets[1], None, None, None, None, None
+        else:
+            wd = _operand(lp, weight, dt, 1, plan.ld2)
+            dy4 = dy.view(B, H, W, Cout)
+            if plan.dgrad == "direct":  # the same direct kernel on dy with the flipped weight
+                return ops.conv3x3_direct_fwd(dy4, _operand(lp, weight, dt, 1), None, relu_mask=x if relu_in else None)
+            if plan.dgrad == "gather":  # the ReLU in front of this convolution masks its data gradient in the epilogue
+                return ops.conv3x3_fwd(dy4, wd, None, 1, False, relu_mask=x if relu_in else None)
+            dxr = ops.linear_fwd(ops.im2col3x3(dy4, 1, False, plan.ld2), wd, None, out_dtype=dt).view(B, H, W, Cin)
+        return ops.relu_bwd(x, dxr) if relu_in else dxr
 
 
 class ConvTransposeFn(torch.autograd.Function):
@@ -266,11 +163,11 @@ class ConvTransposeFn(torch.autograd.Function):
             # Cin = 96 (act_postprocess1) is not a whole number of the bf16 GEMM's 64-deep K-tiles: with
             # zero-padded operand copies (6 MB) the product runs on the MFMA bf16 kernel instead of the
             # generic fp32 one (164 -> ~20 us)
-            w2 = _derived(lp, weight, f"ct:{ld}", dt,
+            w2 = lp.derived(weight, f"ct:{ld}", dt,
                           lambda w: _pad_cols(w.permute(2, 3, 1, 0).reshape(k * k * Cout, Cin), ld))
             g = ops.linear_fwd(_pad_cols(x2, ld), w2, None, out_dtype=dt)
         else:
-            w2 = _derived(lp, weight, "ct", dt, lambda w: w.permute(2, 3, 1, 0).reshape(k * k * Cout, Cin))
+            w2 = lp.derived(weight, "ct", dt, lambda w: w.permute(2, 3, 1, 0).reshape(k * k * Cout, Cin))
             g = ops.linear_fwd(x2, w2, None, out_dtype=dt)
         y = ops.pixel_shuffle(g, bias.detach(), B, H, W, k, Cout)
         ctx.save_for_backward(x2, weight, bias)
@@ -293,8 +190,8 @@ class ConvTransposeFn(torch.autograd.Function):
             ops.colsum(dy.view(-1, Cout), out=tb, accumulate=acc)
         dx = None
         if ctx.needs_input_grad[0]:
-            w2 = _derived(lp, weight, "ct", dt, lambda w: w.permute(2, 3, 1, 0).reshape(k * k * Cout, Cin))
-            w2t = _derived(lp, weight, "ct_t", dt,
+            w2 = lp.derived(weight, "ct", dt, lambda w: w.permute(2, 3, 1, 0).reshape(k * k * Cout, Cin))
+            w2t = lp.derived(weight, "ct_t", dt,
                            lambda w: w.permute(2, 3, 1, 0).reshape(k * k * Cout, Cin).t())
             dx = ops.linear_bwd_data(dg, w2, w2t)
         return dx, rets[0], rets[1], None, None, None, None, None
@@ -383,7 +280,7 @@ class SegHeadFn(torch.autograd.Function):
             out = w.new_zeros(ncp, C)
             out[:nc] = w.reshape(nc, C)
             return out
-        w8 = _derived(lp, weight, f"seg:{ncp}", dt, pad_w)
+        w8 = lp.derived(weight, f"seg:{ncp}", dt, pad_w)
         b8 = torch.zeros(ncp, dtype=torch.float32, device=x.device)
         b8[:nc] = bias.detach()
         y = ops.linear_fwd(x2, w8, b8, out_dtype=dt)
@@ -414,6 +311,6 @@ class SegHeadFn(torch.autograd.Function):
                 out = w.new_zeros(ncp, C)
                 out[:nc] = w.reshape(nc, C)
                 return out
-            w8 = _derived(lp, weight, f"seg:{ncp}", dt, pad_w)
+            w8 = lp.derived(weight, f"seg:{ncp}", dt, pad_w)
             dx = ops.linear_bwd_data(dy8, w8).view(B, H, W, C)
         return dx, rets[0], rets[1], None, None

@@ -180,7 +180,7 @@ def weights_epoch() -> int:
 
 # epoch -> ids of the parameters that moved when it was entered, or None for "any of them" (an optimizer step);
 # lets a cache that holds derived images of MANY parameters re-stamp the untouched ones instead of rebuilding
-# them (dpt_engine.refresh_conv_operands: MoCo's EMA update moves the momentum encoder only).  Short history.
+# them (LPCache.refresh_conv_operands: MoCo's EMA update moves the momentum encoder only).  Short history.
 _EPOCH_TOUCHED = {}
 
 
@@ -224,6 +224,8 @@ class LPCache:
     def __init__(self, arena_fn=None):
         self._c = {}
         self._arena_fn = arena_fn  # -> ParamArena whose shadow copies serve its own parameters
+        # 3x3 operand images (derived(recipe=)): key -> (weakref(p), mode, ld, dtype); the epoch of the last refresh
+        self._conv_recipes, self._conv_epoch = {}, None
 
     def get(self, p: torch.Tensor, dtype, need_t: bool = True):
         w2d = p.detach()
@@ -249,6 +251,60 @@ class LPCache:
             ent = (ver, w, wt, weakref.ref(p))
             self._c[key] = ent
         return ent[1], ent[2]
+
+    def derived(self, params, tag: str, dtype, fn, recipe=None):
+        """operand-type tensor derived from a parameter (or a tuple of them) by `fn`, cached until any of them changes;
+        a tuple of tensors from `fn` is kept as returned.  recipe = (mode, ld) of ops.conv3x3_weight_pack when `fn` is
+        exactly that: the image is then also refreshed, with every other stale one, by refresh_conv_operands."""
+        ps = params if isinstance(params, tuple) else (params,)
+        key = (id(ps[0]), tag)
+        ver = (tuple((p._version, p.data_ptr()) for p in ps), dtype, weights_epoch())
+        if recipe is not None and key not in self._conv_recipes:
+            self._conv_recipes[key] = (weakref.ref(ps[0]), recipe[0], recipe[1], dtype)
+        ent = self._c.get(key)
+        if ent is None or ent[0] != ver:
+            with torch.no_grad():
+                t = fn(*[p.detach() for p in ps])
+                if isinstance(t, torch.Tensor):
+                    t = ops.cast(t.contiguous(), dtype) if t.dtype != dtype else t.contiguous()
+            ent = self._c[key] = (ver, t)
+        return ent[1]
+
+    def refresh_conv_operands(self):
+        """Re-pack every stale 3x3-convolution operand image registered with derived(recipe=...) in ONE launch
+        (ssl4gie_conv3x3_weight_pack_batch; a ResNet-50 otherwise issues ~60 small pack kernels per optimizer step) when
+        the weights epoch has moved; images made stale any other way are re-packed lazily, one by one, by derived()."""
+        epoch = weights_epoch()
+        seen = self._conv_epoch
+        if not self._conv_recipes or seen == epoch:
+            return
+        self._conv_epoch = epoch
+        moved = touched_since(seen) if seen is not None else None   # None: any parameter may have moved
+        items, dead = [], []
+        for key, (ref, mode, ld, dtype) in self._conv_recipes.items():
+            p = ref()
+            if p is None:
+                dead.append(key)
+                continue
+            ver = (((p._version, p.data_ptr()),), dtype, epoch)
+            ent = self._c.get(key)
+            if ent is not None and ent[0] == ver:
+                continue
+            if ent is not None and moved is not None and key[0] not in moved and ent[0][:2] == ver[:2]:
+                self._c[key] = (ver, ent[1])   # only the epoch moved, and not for this parameter: the image stands
+                continue
+            if not p.is_cuda or p.dtype != torch.float32 or not p.is_contiguous() or p.dim() != 4:
+                continue
+            items.append((key, ver, p, mode, ld, dtype))
+        for key in dead:
+            self._conv_recipes.pop(key, None)
+            self._c.pop(key, None)
+        for dtype in {it[5] for it in items}:
+            group = [it for it in items if it[5] == dtype]
+            outs = ops.conv3x3_weight_pack_batch([it[2].detach() for it in group], dtype, [it[3] for it in group],
+                                                 [it[4] for it in group])
+            for it, t in zip(group, outs):
+                self._c[it[0]] = (it[1], t)
 
 
 _GLOBAL_LP = LPCache()
@@ -907,9 +963,7 @@ class EngineModule(nn.Module):
         _lib.load()
         self.arena()
         self.sink().new_pass()
-        if self.lp_cache.__dict__.get("_conv_recipes"):   # 3x3 operand images: one launch for all stale ones
-            from .dpt_engine import refresh_conv_operands
-            refresh_conv_operands(self.lp_cache)
+        self.lp_cache.refresh_conv_operands()   # 3x3 operand images: one launch for all stale ones
 
     def sink(self) -> GradSink:
         if self._root is not None:

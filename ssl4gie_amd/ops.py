@@ -14,6 +14,7 @@ import torch
 
 from . import _lib
 from ._lib import BF16, F32, GemmDesc
+from .conv_plan import colstats_ok, conv_out_hw, gather_fwd_ok, gather_wgrad_ok, k_pad  # noqa: F401 (ops.k_pad, ...)
 
 _TORCH2CODE = {torch.float32: F32, torch.bfloat16: BF16}
 _CODE2TORCH = {F32: torch.float32, BF16: torch.bfloat16}
@@ -121,11 +122,6 @@ def _desc(M, N, K, dt_ab, dt_c):
     d.M, d.N, d.K, d.batch1, d.batch2 = M, N, K, 1, 1
     d.dtype_ab, d.dtype_c, d.alpha, d.epilogue = dt_ab, dt_c, 1.0, _lib.EPI_NONE
     return d
-
-
-def colstats_ok(T, n_out, k_in, dtype):
-    """whether the producing GEMM can emit BatchNorm partial statistics (256x256 NT kernel rules)"""
-    return dtype == torch.bfloat16 and k_in % 64 == 0 and n_out % 8 == 0 and T > 0
 
 
 def linear_fwd(x2d, w, bias=None, out_dtype=None, epilogue=None, residual=None, colstats=False):
@@ -555,15 +551,6 @@ def _nhwc(x):
     return x.shape
 
 
-def conv_out_hw(H, W, stride):
-    return (H - 1) // stride + 1, (W - 1) // stride + 1
-
-
-def k_pad(k, dtype):
-    """row stride of a patch matrix: the bf16 MFMA GEMM wants whole 64-deep K-tiles"""
-    return (k + 63) // 64 * 64 if dtype == torch.bfloat16 else k
-
-
 def im2col3x3(x, stride=1, relu=False, ld=None):
     B, H, W, C = _nhwc(x)
     Ho, Wo = conv_out_hw(H, W, stride)
@@ -575,17 +562,8 @@ def im2col3x3(x, stride=1, relu=False, ld=None):
 
 
 def conv3x3_implicit_ok(x, stride, n_out=None, wgrad=False):
-    """whether the gathered 256x256 GEMM kernels take this map (ssl4gie_conv3x3_geom limits)"""
-    if x.dtype != torch.bfloat16 or not x.is_contiguous():
-        return False
-    B, H, W, C = x.shape
-    Ho, Wo = conv_out_hw(H, W, stride)
-    if stride not in (1, 2) or Wo < 2 or (B * H + 1) * W * C * 2 >= 2 ** 31:
-        return False
-    if wgrad:  # contraction over pixels in whole K-tiles; dy rows addressed with 32-bit offsets
-        return C % 8 == 0 and (B * Ho * Wo) % 64 == 0 and n_out % 8 == 0 and \
-            B * Ho * Wo * n_out * 2 < 2 ** 32
-    return C % 64 == 0 and n_out % 8 == 0
+    """whether the gathered 256x256 GEMM kernels take this map: conv_plan's limits for a tensor"""
+    return x.is_contiguous() and (gather_wgrad_ok if wgrad else gather_fwd_ok)(*x.shape, n_out, stride, x.dtype)
 
 
 def _geom(x, stride, relu):
@@ -655,27 +633,6 @@ def conv3x3_bwd_weight(dy2d, x, stride=1, relu=False, bias_out=None):
     return out
 
 
-def conv3x3_direct_supported(x, n_out):
-    """whether the direct kernel CAN take this stride-1 map (bf16, Cin % 32 == 0, Cout % 8 == 0)"""
-    if x.dtype != torch.bfloat16 or not x.is_contiguous():
-        return False
-    B, H, W, Cin = x.shape
-    return bool(_lib.load().ssl4gie_conv3x3_direct_ok(B, H, W, Cin, n_out))
-
-
-def conv3x3_direct_ok(x, n_out):
-    """whether the direct (halo-in-LDS) kernel takes this map: narrow layers the 256-wide GEMM tiles
-    would mostly pad (ssl4gie_conv3x3_direct_fwd)"""
-    if x.dtype != torch.bfloat16 or not x.is_contiguous():
-        return False
-    B, H, W, Cin = x.shape
-    # measured (tools/conv_bench.py): ahead of the gathered GEMM wherever its 256-wide tiles are
-    # mostly padding — narrow layers — and on small maps (<= 16 wide: 256 -> 256 @14, 512 -> 512 @7),
-    # where the GEMM has too few tiles to fill the chip
-    return (n_out <= 128 or Cin == 32 or W <= 16) and \
-        bool(_lib.load().ssl4gie_conv3x3_direct_ok(B, H, W, Cin, n_out))
-
-
 def conv3x3_direct_fwd(x, w2, bias=None, relu=False, relu_mask=None, colstats=False):
     """stride-1 3x3 convolution of the bf16 map x [B,H,W,Cin] with w2 [Cout, 9 Cin] on the direct
     kernel; semantics of conv3x3_fwd (bias and relu_mask may be combined with relu here).
@@ -698,14 +655,6 @@ def conv3x3_direct_fwd(x, w2, bias=None, relu=False, relu_mask=None, colstats=Fa
     _lib.check(L.ssl4gie_conv3x3_direct_fwd(ptr(x), ptr(w2), ptr(bias), ptr(relu_mask), ptr(y), ptr(stats),
                                             B, H, W, Cin, Cout, int(relu), stream()), "conv3x3_direct_fwd")
     return (y, stats) if colstats else y
-
-
-def conv3x3_direct_wgrad_ok(x, n_out):
-    """narrow layers only (n_out <= 128): from 256 couts on the gathered TN GEMM has full tiles"""
-    if x.dtype != torch.bfloat16 or not x.is_contiguous():
-        return False
-    B, H, W, Cin = x.shape
-    return n_out <= 128 and bool(_lib.load().ssl4gie_conv3x3_direct_wgrad_ok(B, H, W, Cin, n_out))
 
 
 def conv3x3_direct_wgrad(dy, x, relu=False, bias_out=None):
@@ -741,16 +690,20 @@ def stem7x7_pack(imgs):
     return out
 
 
+def _pack_shape(w, mode, ld):
+    """(Cout, Cin, row length, shape) of the mode-`mode` operand image of w [Cout, Cin, 3, 3]; ld None = unpadded"""
+    Cout, Cin = w.shape[:2]
+    ld = 9 * (Cout if mode == 1 else Cin) if ld is None else ld
+    return Cout, Cin, ld, ((Cout, ld) if mode == 0 else ((Cin, ld) if mode == 1 else (ld, Cout)))
+
+
 def conv3x3_weight_pack(weight, dtype, mode, ld=None):
     """operand image of a Conv2d(k=3) weight [Cout, Cin, 3, 3] fp32 in one launch (cast included):
     mode 0 -> [Cout, ld] rows (tap, ci); mode 1 -> [Cin, ld] rows (flipped tap, co); mode 2 -> [ld, Cout]"""
     _dev(weight)
     assert weight.dtype == torch.float32 and weight.dim() == 4 and weight.shape[2:] == (3, 3)
     w = weight.contiguous()
-    Cout, Cin = w.shape[:2]
-    need = 9 * (Cout if mode == 1 else Cin)
-    ld = need if ld is None else ld
-    shape = (Cout, ld) if mode == 0 else ((Cin, ld) if mode == 1 else (ld, Cout))
+    Cout, Cin, ld, shape = _pack_shape(w, mode, ld)
     out = torch.empty(shape, dtype=dtype, device=w.device)
     _lib.check(_lib.load().ssl4gie_conv3x3_weight_pack(ptr(w), ptr(out), code(dtype), Cout, Cin, mode, ld, stream()),
                "conv3x3_weight_pack")
@@ -760,7 +713,6 @@ def conv3x3_weight_pack(weight, dtype, mode, ld=None):
 def conv3x3_weight_pack_batch(weights, dtype, modes, lds):
     """conv3x3_weight_pack for a list of weights in one launch (ssl4gie_conv3x3_weight_pack_batch); lds[i] None =
     the unpadded row length"""
-    import ctypes as C
     n = len(weights)
     if n == 0:
         return []
@@ -768,10 +720,7 @@ def conv3x3_weight_pack_batch(weights, dtype, modes, lds):
     for w, mode, ld in zip(weights, modes, lds):
         _dev(w)
         assert w.dtype == torch.float32 and w.dim() == 4 and w.shape[2:] == (3, 3) and w.is_contiguous()
-        Cout, Cin = w.shape[:2]
-        need = 9 * (Cout if mode == 1 else Cin)
-        ld = need if ld is None else ld
-        shape = (Cout, ld) if mode == 0 else ((Cin, ld) if mode == 1 else (ld, Cout))
+        Cout, Cin, ld, shape = _pack_shape(w, mode, ld)
         outs.append(torch.empty(shape, dtype=dtype, device=w.device))
         geo.append((Cout, Cin, mode, ld))
     vp_arr = C.c_void_p * n

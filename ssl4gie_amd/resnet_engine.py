@@ -15,7 +15,7 @@ import weakref
 import torch
 
 from . import ops
-from .dpt_engine import _derived, _pad_cols, _write_grad
+from .dpt_engine import _pad_cols, _write_grad
 from .engine import touched_since, weights_epoch, GradSink, LPCache
 
 
@@ -69,7 +69,7 @@ class StemConvFn(torch.autograd.Function):
             # read by the direct stem kernels (csrc/conv_direct.hip): 43 + 179 us instead of 740 + 454
             H, W = imgs.shape[2:]
             packed = STEM_COLS.get(imgs, dtype, ops.stem7x7_pack)
-            w2s = _derived(lp, weight, "stem7", dtype, ops.stem7x7_weight)
+            w2s = lp.derived(weight, "stem7", dtype, ops.stem7x7_weight)
             ctx.save_for_backward(imgs, weight)
             ctx.cfg = (dtype, sink)
             ctx.direct = True
@@ -82,7 +82,7 @@ class StemConvFn(torch.autograd.Function):
         ctx.direct = False
         cols, Ho, Wo = STEM_COLS.get(imgs, dtype)
         ld = cols.shape[1]
-        w2 = _derived(lp, weight, f"stem:{ld}", dtype,
+        w2 = lp.derived(weight, f"stem:{ld}", dtype,
                       lambda w: _pad_cols(w.permute(0, 2, 3, 1).reshape(Cout, 147), ld))
         ctx.save_for_backward(imgs, weight)
         ctx.cfg = (dtype, sink)

@@ -12,6 +12,8 @@ Models/DPT_decoder.py:396-482, Models/moco_v3/moco/builder.py:75-96."""
 import pytest
 import torch
 
+from conv_path_checks import conv_ref, conv_wgrad_ref, ints, mm64
+
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
 BF, F32, F64 = torch.bfloat16, torch.float32, torch.float64
@@ -23,23 +25,6 @@ def _need_gpu():
         pytest.skip("no GPU")
     from ssl4gie_amd import _lib
     _lib.load()
-
-
-def ints(shape, seed, lo=-1, hi=2):
-    """small integers drawn on the device (hundreds of millions of them: a host generator would take minutes)"""
-    g = torch.Generator(DEV).manual_seed(seed)
-    return torch.randint(lo, hi, shape, generator=g, device=DEV, dtype=torch.int8).to(BF)
-
-
-def mm64(a, b):
-    """fp64 product of two integer-valued bf16 matrices in row chunks (an [M, K] fp64 copy of a 800k-row operand
-    would be gigabytes)"""
-    out = torch.empty(a.shape[0], b.shape[1], dtype=F64, device=a.device)
-    step = 1 << 18
-    b64 = b.double()
-    for i in range(0, a.shape[0], step):
-        out[i:i + step] = a[i:i + step].double() @ b64
-    return out
 
 
 def colstats_ref(y_bf, rows=128):
@@ -98,40 +83,6 @@ def test_r50_1x1_products_full_batch_exact(M, N, K):
 # configs[3]: the 3x3 convolutions of the DPT depth decoder at B = 128 THROUGH the layer op
 # (dpt_engine.Conv3x3Fn: direct / gathered / materialised path chosen per geometry, data gradient on the flipped
 # weight, weight gradient + bias gradient), fp64 reference from nine shifted rocBLAS products
-def conv_ref(x, w, stride):
-    """x [B,H,W,Ci] (integer-valued bf16), w [Co,Ci,3,3] fp64 -> fp64 [B,Ho,Wo,Co], pad 1"""
-    B, H, W, Ci = x.shape
-    Co = w.shape[0]
-    Ho, Wo = (H - 1) // stride + 1, (W - 1) // stride + 1
-    xp = torch.zeros(B, H + 2, W + 2, Ci, dtype=BF, device=x.device)
-    xp[:, 1:H + 1, 1:W + 1] = x
-    out = torch.zeros(B * Ho * Wo, Co, dtype=F64, device=x.device)
-    for dy in range(3):
-        for dx in range(3):
-            tap = xp[:, dy:dy + stride * (Ho - 1) + 1:stride, dx:dx + stride * (Wo - 1) + 1:stride].reshape(-1, Ci)
-            out += mm64(tap, w[:, :, dy, dx].t().to(BF))
-    return out.view(B, Ho, Wo, Co)
-
-
-def conv_wgrad_ref(dy, x, stride):
-    """dW[Co,Ci,3,3] fp64 = sum over output pixels of dy x patch"""
-    B, H, W, Ci = x.shape
-    _, Ho, Wo, Co = dy.shape
-    xp = torch.zeros(B, H + 2, W + 2, Ci, dtype=BF, device=x.device)
-    xp[:, 1:H + 1, 1:W + 1] = x
-    dw = torch.zeros(Co, Ci, 3, 3, dtype=F64, device=x.device)
-    d2 = dy.reshape(-1, Co)
-    step = 1 << 18
-    for ky in range(3):
-        for kx in range(3):
-            tap = xp[:, ky:ky + stride * (Ho - 1) + 1:stride, kx:kx + stride * (Wo - 1) + 1:stride].reshape(-1, Ci)
-            acc = torch.zeros(Co, Ci, dtype=F64, device=x.device)
-            for i in range(0, d2.shape[0], step):
-                acc += d2[i:i + step].double().t() @ tap[i:i + step].double()
-            dw[:, :, ky, kx] = acc
-    return dw
-
-
 DPT_CONVS = [  # (name, B, H, W, Cin, Cout, stride, relu_in, bias)
     ("refinenet1.resConfUnit.conv", 128, 56, 56, 256, 256, 1, True, True),
     ("refinenet2.resConfUnit.conv", 128, 28, 28, 256, 256, 1, True, True),

@@ -210,7 +210,8 @@ def test_conv_operand_images_in_one_launch_equal_the_single_packs(monkeypatch):
     """ssl4gie_conv3x3_weight_pack_batch against ssl4gie_conv3x3_weight_pack: all three modes, padded and unpadded
     rows, 70 weights (two kernel-argument batches); and a ResNet-50 step after a fused optimizer step gives the
     same output with the batched refresh as with the lazy single packs"""
-    from ssl4gie_amd import dpt_engine, ops
+    from ssl4gie_amd import ops
+    from ssl4gie_amd.engine import LPCache
     g = G(55)
     ws, modes, lds = [], [], []
     for i in range(70):
@@ -226,7 +227,7 @@ def test_conv_operand_images_in_one_launch_equal_the_single_packs(monkeypatch):
     res = []
     for batched in (True, False):
         if not batched:   # no refresh at the top of the forward: every stale image is re-packed by its own launch
-            monkeypatch.setattr(dpt_engine, "refresh_conv_operands", lambda lp: None)
+            monkeypatch.setattr(LPCache, "refresh_conv_operands", lambda self: None)
         m, _ = _resnet_pair(5)
         m.to(DEV).set_precision("bf16")
         m.train()

@@ -4,7 +4,7 @@ decoder / ResNet-50 geometries of the benchmark configurations.  python tools/co
 import sys, os
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
-from ssl4gie_amd import ops, _lib
+from ssl4gie_amd import conv_plan, ops
 
 CASES = [  # name, B, H, W, Cin, Cout, stride
     ("dpt refinenet 256>256 @112 b64", 64, 112, 112, 256, 256, 1),
@@ -40,18 +40,20 @@ def main():
         fl = 2.0 * B * Ho * Wo * Co * 9 * Ci
         fi = timeit(lambda: ops.conv3x3_fwd(x, w2, bias, s, True))
         fm = timeit(lambda: ops.linear_fwd(ops.im2col3x3(x, s, True), w2, bias))
-        if ops.conv3x3_implicit_ok(x, s, Co, wgrad=True):
+        if conv_plan.gather_wgrad_ok(B, H, W, Ci, Co, s, x.dtype):
             wi = timeit(lambda: ops.conv3x3_bwd_weight(dy, x, s, True, bias_out=bias))
         else:
             wi = float("nan")
         wm = timeit(lambda: ops.linear_bwd_weight(dy, ops.im2col3x3(x, s, True), bias_out=bias))
         fd = wd = float("nan")
-        if s == 1 and _lib.load().ssl4gie_conv3x3_direct_ok(B, H, W, Ci, Co):
+        if s == 1 and conv_plan.direct_fwd_ok(B, H, W, Ci, Co, x.dtype):
             fd = timeit(lambda: ops.conv3x3_direct_fwd(x, w2, bias, relu=True))
-        if s == 1 and _lib.load().ssl4gie_conv3x3_direct_wgrad_ok(B, H, W, Ci, Co):
+        if s == 1 and conv_plan.direct_wgrad_ok(B, H, W, Ci, Co, x.dtype):
             wd = timeit(lambda: ops.conv3x3_direct_wgrad(dy.view(B, Ho, Wo, Co), x, relu=True, bias_out=bias))
+        p = conv_plan.conv3x3_plan(B, H, W, Ci, Co, s, x.dtype, True, False)
         print(f"{name:36s} {fi:9.1f} {fm:9.1f} {fl / fi / 1e6:8.1f} | {wi:9.1f} {wm:9.1f} {fl / wi / 1e6:8.1f}"
-              f" | direct fwd {fd:8.1f} ({fl / fd / 1e6:6.1f} TF/s) wgrad {wd:8.1f} ({fl / wd / 1e6:6.1f})", flush=True)
+              f" | direct fwd {fd:8.1f} ({fl / fd / 1e6:6.1f} TF/s) wgrad {wd:8.1f} ({fl / wd / 1e6:6.1f})"
+              f" | layer op takes {p.fwd} / {p.wgrad} / {p.dgrad}", flush=True)
         del x, w2, dy
         torch.cuda.empty_cache()
 

@@ -12,6 +12,7 @@ import torch
 if not torch.cuda.is_available():
     sys.exit("convstem_bench: needs the GPU (there is no CPU path to measure)")
 from ssl4gie_amd import ops  # noqa: E402
+from ssl4gie_amd.conv_plan import conv3x3_plan  # noqa: E402
 from ssl4gie_amd.engine import GradSink, LPCache, LinearFn  # noqa: E402
 from ssl4gie_amd.dpt_engine import Conv3x3Fn  # noqa: E402
 from ssl4gie_amd.resnet_engine import BatchNormFn, StemConv3x3Fn  # noqa: E402
@@ -102,7 +103,7 @@ for i in range(4):
 
     tf, tfb = timeit(fwd_only, 0.3), timeit(fwd_bwd, 0.3)
     tot_f, tot_b = tot_f + tf, tot_b + tfb - tf
-    kind = "direct stem kernels" if i == 0 else ("patch matrix" if cin % 64 else "gathered GEMM")
+    kind = "direct stem kernels" if i == 0 else conv3x3_plan(B, hw, hw, cin, cout, 2, BF, False, True).fwd
     print(f"layer {i + 1}: {cin:3d} -> {cout:3d} @ {hw:3d}^2  conv + BatchNorm + ReLU   forward {tf:8.1f} us   backward "
           f"{tfb - tf:8.1f} us   ({kind})", flush=True)
     del xin, gout

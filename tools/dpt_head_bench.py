@@ -4,7 +4,7 @@ forward, data gradient and weight gradient of output_conv.0 (256->128 @112^2) an
 import sys, os
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
-from ssl4gie_amd import ops, _lib
+from ssl4gie_amd import conv_plan, ops
 
 B = int(sys.argv[1]) if len(sys.argv) > 1 else 128
 CASES = [("output_conv.0 256>128 @112", 112, 256, 128), ("output_conv.2 128>32 @224", 224, 128, 32),
@@ -28,8 +28,9 @@ for name, HW, Ci, Co in CASES:
     bias = torch.zeros(Co, device="cuda")
     dy = torch.randn(B, HW, HW, Co, device="cuda").bfloat16()
     fl = 2.0 * B * HW * HW * Co * 9 * Ci
+    plan = conv_plan.conv3x3_plan(B, HW, HW, Ci, Co, 1, x.dtype, True, False)
     f = timeit(lambda: ops.conv3x3_fwd(x, w2, bias, 1, True))
-    if ops.conv3x3_implicit_ok(dy, 1, Ci):
+    if conv_plan.gather_fwd_ok(B, HW, HW, Co, Ci, 1, dy.dtype):
         d = timeit(lambda: ops.conv3x3_fwd(dy, wd, None, 1, False, relu_mask=x))
         how = "implicit"
     else:
@@ -42,17 +43,18 @@ for name, HW, Ci, Co in CASES:
     if os.environ.get('FORCE_DIRECT'):
         fd = timeit(lambda: ops.conv3x3_direct_fwd(x, w2, bias, relu=True))
         print(f'{name:30s} B={B}: DIRECT(forced) fwd {fd:8.1f} us ({fl / fd / 1e6:6.1f} TF/s)', flush=True)
-    if os.environ.get('FORCE_DIRECT') and _lib.load().ssl4gie_conv3x3_direct_wgrad_ok(B, HW, HW, Ci, Co):
+    if os.environ.get('FORCE_DIRECT') and conv_plan.direct_wgrad_ok(B, HW, HW, Ci, Co, x.dtype):
         wf = timeit(lambda: ops.conv3x3_direct_wgrad(dy, x, relu=True, bias_out=bias))
         print(f'{name:30s} B={B}: DIRECT(forced) wgrad {wf:8.1f} us ({fl / wf / 1e6:6.1f} TF/s)', flush=True)
-    if ops.conv3x3_direct_ok(x, Co):
+    if plan.fwd == "direct":
         fd = timeit(lambda: ops.conv3x3_direct_fwd(x, w2, bias, relu=True))
         dd = timeit(lambda: ops.conv3x3_direct_fwd(dy, wd, None, relu_mask=x))
-        wdd = timeit(lambda: ops.conv3x3_direct_wgrad(dy, x, relu=True, bias_out=bias)) if ops.conv3x3_direct_wgrad_ok(x, Co) else float('nan')
+        wdd = timeit(lambda: ops.conv3x3_direct_wgrad(dy, x, relu=True, bias_out=bias)) if plan.wgrad == "direct" else float('nan')
         cs = timeit(lambda: ops.colsum(dy.view(-1, Co), out=bias))
         print(f"{name:30s} B={B}: DIRECT fwd {fd:8.1f} us ({fl / fd / 1e6:6.1f} TF/s) | dgrad {dd:8.1f} us "
               f"({fl / dd / 1e6:6.1f}) | wgrad {wdd:8.1f} us ({fl / wdd / 1e6:6.1f}) + colsum {cs:7.1f} us", flush=True)
     print(f"{name:30s} B={B}: fwd {f:8.1f} us ({fl / f / 1e6:6.1f} TF/s) | dgrad[{how}] {d:8.1f} us "
-          f"({fl / d / 1e6:6.1f}) | wgrad {w:8.1f} us ({fl / w / 1e6:6.1f})", flush=True)
+          f"({fl / d / 1e6:6.1f}) | wgrad {w:8.1f} us ({fl / w / 1e6:6.1f})"
+          f" | layer op takes {plan.fwd} / {plan.wgrad} / {plan.dgrad}", flush=True)
     del x, dy
     torch.cuda.empty_cache()
