@@ -423,6 +423,42 @@ int ssl4gie_bilinear2x_fwd(const void* x, void* y, int dtype, int B, int H, int 
                            void* stream);
 int ssl4gie_bilinear2x_bwd(const void* dy, void* dx, int dtype, int B, int H, int W, int C,
                            void* stream);
+/* ---------------------------------------------------------------- atrous glue of DeepLabV3+ (channels-last)
+ * What segmentation_models_pytorch 0.3.2 (not vendored, not installed: restated from its published source) runs
+ * around the 1x1 convolutions of smp.DeepLabV3Plus(encoder_name="resnet50").  Maps are [B, H, W, C] in `dtype`,
+ * accumulation is fp32, nothing uses float atomics (results repeat bit for bit), and a tap outside the map is never
+ * turned into an address.  These entry points joined revision 12 (added symbols, nothing existing changed).
+ *
+ * im2col3x3_dil: the patch matrix of nn.Conv2d(k = 3, stride 1, padding = dilation = d) — what the encoder's
+ *   make_dilated() turns layer4's 3x3 convolutions into at output stride 16 (d = 2).  Same [B H W, ld] layout, (ky, kx, c)
+ *   column order and zero pad columns as ssl4gie_im2col3x3, so ssl4gie_conv3x3_weight_pack (modes 0 / 1) and
+ *   ssl4gie_gemm give the forward, the data gradient (the same call on dy with the flipped image) and, with
+ *   ssl4gie_conv3x3_wgrad_unpack, the weight gradient.  C % 8 == 0 (bf16) / % 4 == 0 (fp32), d >= 1, ld >= 9 C.
+ * dwconv3x3_fwd: the depthwise half of the decoder's SeparableConv2d (nn.Conv2d(C, C, 3, padding = dilation = d,
+ *   groups = C, bias = False): the three ASPPSeparableConv branches at rates 12 / 24 / 36, aspp.1 and block2.0 at d = 1),
+ *   weight fp32 [C, 3, 3] (the parameter's [C, 1, 3, 3]), C % 8 == 0.  flip = 1 reads the weight as w[c, 2-ky, 2-kx]:
+ *   the data gradient is this call on dy.
+ * dwconv3x3_wgrad: dweight [C, 3, 3] fp32 (+)= sum over pixels of dy[b,y,x,c] x[b, y + (ky-1) d, x + (kx-1) d, c];
+ *   fp32 partials in `workspace`, summed in a fixed order by a second kernel.
+ * bilinear_up_ac_fwd / _bwd: nn.UpsamplingBilinear2d(scale_factor = s) (align_corners=True; the decoder's `up` and the
+ *   SegmentationHead's up-sampling, s = 4): x [B,H,W,C] -> y [B, sH, sW, C], source coordinate o (H-1) / (sH-1);
+ *   integer s >= 2, any C >= 1 (16-byte accesses when C allows them); the backward gathers per input pixel.
+ * chan_copy: torch.cat((...), dim=1) of ASPP.forward / DeepLabV3PlusDecoder.forward and its gradient:
+ *   dst[r, 0:C) = src[r / rep, 0:C) for `rows` rows with row strides lds / ldd in elements (the caller offsets the
+ *   pointers to the channel slice); rep = H W broadcasts a per-image row (ASPPPooling's F.interpolate from 1x1). */
+int ssl4gie_im2col3x3_dil(const void* x, void* cols, int dtype, int B, int H, int W, int C, int dilation,
+                          long long ld, void* stream);
+int ssl4gie_dwconv3x3_fwd(const void* x, const float* w, void* y, int dtype, int B, int H, int W, int C,
+                          int dilation, int flip, void* stream);
+size_t ssl4gie_dwconv3x3_wgrad_workspace_bytes(int dtype, int B, int H, int W, int C);
+int ssl4gie_dwconv3x3_wgrad(const void* dy, const void* x, float* dweight, void* workspace, size_t workspace_bytes,
+                            int dtype, int B, int H, int W, int C, int dilation, int accumulate, void* stream);
+int ssl4gie_bilinear_up_ac_fwd(const void* x, void* y, int dtype, int B, int H, int W, int C, int scale,
+                               void* stream);
+int ssl4gie_bilinear_up_ac_bwd(const void* dy, void* dx, int dtype, int B, int H, int W, int C, int scale,
+                               void* stream);
+int ssl4gie_chan_copy(const void* src, long long lds, void* dst, long long ldd, int dtype, long long rows, int C,
+                      long long rep, void* stream);
 /* ConvTranspose2d(k = s) (:345-354, :371-380) = GEMM + scatter: g [B*H*W, k*k*C] with columns
  * ordered (i, j, c) -> y[b, k*y+i, k*x+j, c] = g + bias[c]; unshuffle is its inverse (gradient) */
 int ssl4gie_pixel_shuffle(const void* g, const float* bias, void* y, int dtype, int B, int H, int W,

@@ -89,6 +89,10 @@ class ResNet50(EngineModule):
                                self.lp_cache, True, join)
         return y.view(B, H, W, -1), st
 
+    def _c3(self, x, conv):
+        """3x3 convolution (Bottleneck.conv2) -> (map, BatchNorm partial statistics of the map or None)"""
+        return Conv3x3Fn.apply(x, conv.weight, None, conv.stride[0], False, self.sink(), self.lp_cache, True)
+
     def _c1_bn_nograd(self, x, conv, bn, relu, res=None):
         """1x1 convolution + training-mode BatchNorm (+ residual) (+ ReLU) when nothing is kept for a backward pass
         (torch.no_grad(): MoCo's momentum encoder, moco/builder.py:127-135) and the map gets WIDER (conv3,
@@ -140,8 +144,7 @@ class ResNet50(EngineModule):
         join = GradJoin.for_tensor(x)
         out, st = self._c1(x, blk.conv1, join)
         out = self._bn(out, blk.bn1, True, stats=st)
-        out, st = Conv3x3Fn.apply(out, blk.conv2.weight, None, blk.conv2.stride[0], False, self.sink(),
-                                  self.lp_cache, True)
+        out, st = self._c3(out, blk.conv2)
         out = self._bn(out, blk.bn2, True, stats=st)
         identity = x
         if blk.downsample is not None:

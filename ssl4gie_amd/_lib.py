@@ -118,6 +118,13 @@ PROTOTYPES = {
     "ssl4gie_stem3x3_wgrad": (i32, [vp, vp, vp, vp, sz, i32, i32, i32, i32, i32, i32, vp]),
     "ssl4gie_bilinear2x_fwd": (i32, [vp, vp, i32, i32, i32, i32, i32, vp]),
     "ssl4gie_bilinear2x_bwd": (i32, [vp, vp, i32, i32, i32, i32, i32, vp]),
+    "ssl4gie_im2col3x3_dil": (i32, [vp, vp, i32, i32, i32, i32, i32, i32, i64, vp]),
+    "ssl4gie_dwconv3x3_fwd": (i32, [vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp]),
+    "ssl4gie_dwconv3x3_wgrad_workspace_bytes": (sz, [i32, i32, i32, i32, i32]),
+    "ssl4gie_dwconv3x3_wgrad": (i32, [vp, vp, vp, vp, sz, i32, i32, i32, i32, i32, i32, i32, vp]),
+    "ssl4gie_bilinear_up_ac_fwd": (i32, [vp, vp, i32, i32, i32, i32, i32, i32, vp]),
+    "ssl4gie_bilinear_up_ac_bwd": (i32, [vp, vp, i32, i32, i32, i32, i32, i32, vp]),
+    "ssl4gie_chan_copy": (i32, [vp, i64, vp, i64, i32, i64, i32, i64, vp]),
     "ssl4gie_pixel_shuffle": (i32, [vp, vp, vp, i32, i32, i32, i32, i32, i32, vp]),
     "ssl4gie_pixel_unshuffle": (i32, [vp, vp, i32, i32, i32, i32, i32, i32, vp]),
     "ssl4gie_tokens_to_map": (i32, [vp, vp, i32, i32, i32, i32, vp]),

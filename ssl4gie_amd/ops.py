@@ -163,6 +163,26 @@ def linear_fwd(x2d, w, bias=None, out_dtype=None, epilogue=None, residual=None, 
     return (y, out2) if out2 is not None else y
 
 
+def linear_fwd_kblocks(x2d, w, block):
+    """y = x2d @ w^T in fp32, the contraction taken `block` columns at a time and the partial products added in
+    fp32 (accumulate): a rounding chain of k_in / block + block / 4 steps instead of k_in / 4 — the parity mode's
+    product over a 3x3 patch matrix, one tap per block"""
+    _dev(x2d, w)
+    _f32(x2d, w)
+    T, k_in = x2d.shape
+    n_out = w.shape[0]
+    assert w.shape[1] == k_in and block >= 1 and k_in % block == 0, (x2d.shape, w.shape, block)
+    y = torch.empty(T, n_out, dtype=torch.float32, device=x2d.device)
+    for k0 in range(0, k_in, block):
+        d = _desc(T, n_out, block, F32, F32)
+        d.A, d.sAm, d.sAk = ptr(x2d) + 4 * k0, k_in, 1
+        d.B, d.sBk, d.sBn = ptr(w) + 4 * k0, 1, k_in
+        d.C, d.ldc = ptr(y), n_out
+        d.accumulate = int(k0 > 0)
+        gemm_raw(d, x2d.device)
+    return y
+
+
 def linear_colstats_only(x2d, w):
     """the BatchNorm partial statistics [ceil(T/128), 2, n_out] of y = x2d @ w^T (of its bf16-rounded values, as
     linear_fwd(colstats=True) returns them) WITHOUT writing y: the first half of the BatchNorm-fused 1x1
@@ -843,6 +863,115 @@ def bilinear2x_bwd(dy):
     _lib.check(_lib.load().ssl4gie_bilinear2x_bwd(ptr(dy), ptr(dx), code(dy.dtype), B, Ho // 2,
                                                   Wo // 2, C, stream()), "bilinear2x_bwd")
     return dx
+
+
+# ------------------------------------------------------------------ atrous glue of DeepLabV3+ (channels-last)
+def _map(x, what):
+    B, H, W, C = _nhwc(x)
+    code(x.dtype)
+    if C % (8 if x.dtype == torch.bfloat16 else 4):
+        raise ValueError(f"{what}: {C} channels are not a whole number of 16-byte chunks of {x.dtype}")
+    return B, H, W, C
+
+
+def im2col3x3_dil(x, dilation, ld=None):
+    """patch matrix [B H W, ld] of a Conv2d(k=3, stride 1, padding = dilation): im2col3x3's layout"""
+    B, H, W, C = _map(x, "im2col3x3_dil")
+    assert int(dilation) >= 1, dilation
+    ld = ld or k_pad(9 * C, x.dtype)
+    assert ld >= 9 * C and ld % (8 if x.dtype == torch.bfloat16 else 4) == 0, ld
+    cols = torch.empty(B * H * W, ld, dtype=x.dtype, device=x.device)
+    _lib.check(_lib.load().ssl4gie_im2col3x3_dil(ptr(x), ptr(cols), code(x.dtype), B, H, W, C, int(dilation), ld,
+                                                 stream()), "im2col3x3_dil")
+    return cols
+
+
+def _dw_weight(w, C):
+    _f32(w)
+    if w.numel() != 9 * C or w.shape[0] != C or tuple(w.shape[-2:]) != (3, 3):
+        raise ValueError(f"depthwise weight {tuple(w.shape)} does not fit {C} channels ([C, 1, 3, 3] or [C, 3, 3])")
+
+
+def dwconv3x3_fwd(x, w, dilation, flip=False):
+    """depthwise Conv2d(C, C, 3, padding = dilation, groups = C, bias=False) on x [B,H,W,C]; w fp32 [C,1,3,3] / [C,3,3];
+    flip: with the weight rotated by 180 degrees (the data gradient, called on dy)"""
+    _dev(w)
+    B, H, W, C = _map(x, "dwconv3x3_fwd")
+    assert C % 8 == 0 and int(dilation) >= 1, (C, dilation)
+    _dw_weight(w, C)
+    y = torch.empty_like(x)
+    _lib.check(_lib.load().ssl4gie_dwconv3x3_fwd(ptr(x), ptr(w), ptr(y), code(x.dtype), B, H, W, C, int(dilation),
+                                                 int(bool(flip)), stream()), "dwconv3x3_fwd")
+    return y
+
+
+def dwconv3x3_wgrad(dy, x, dilation, out=None, accumulate=False):
+    """weight gradient [C, 1, 3, 3] fp32 (+)= of the depthwise convolution from dy and x [B,H,W,C]; deterministic"""
+    _dev(dy, out)
+    B, H, W, C = _map(x, "dwconv3x3_wgrad")
+    assert C % 8 == 0 and int(dilation) >= 1 and dy.shape == x.shape and dy.dtype == x.dtype, (dy.shape, x.shape)
+    if out is None:
+        assert not accumulate
+        out = torch.empty(C, 1, 3, 3, dtype=torch.float32, device=x.device)
+    _dw_weight(out, C)
+    L = _lib.load()
+    nb = L.ssl4gie_dwconv3x3_wgrad_workspace_bytes(code(x.dtype), B, H, W, C)
+    ws = torch.empty(max(nb, 16), dtype=torch.uint8, device=x.device)
+    _lib.check(L.ssl4gie_dwconv3x3_wgrad(ptr(dy), ptr(x), ptr(out), ptr(ws), nb, code(x.dtype), B, H, W, C,
+                                         int(dilation), int(bool(accumulate)), stream()), "dwconv3x3_wgrad")
+    return out
+
+
+def _up_scale(scale):
+    if int(scale) != scale or int(scale) < 2:
+        raise ValueError(f"bilinear_up_ac: integer scale >= 2, got {scale}")
+    return int(scale)
+
+
+def bilinear_up_ac_fwd(x, scale):
+    """nn.UpsamplingBilinear2d(scale_factor=scale) (align_corners=True): [B,H,W,C] -> [B, scale H, scale W, C]; any C"""
+    B, H, W, C = _nhwc(x)
+    s = _up_scale(scale)
+    y = torch.empty(B, s * H, s * W, C, dtype=x.dtype, device=x.device)
+    _lib.check(_lib.load().ssl4gie_bilinear_up_ac_fwd(ptr(x), ptr(y), code(x.dtype), B, H, W, C, s, stream()),
+               "bilinear_up_ac_fwd")
+    return y
+
+
+def bilinear_up_ac_bwd(dy, scale):
+    """gradient of bilinear_up_ac_fwd: dy [B, scale H, scale W, C] -> dx [B,H,W,C] (gather form, no atomics)"""
+    B, Ho, Wo, C = _nhwc(dy)
+    s = _up_scale(scale)
+    assert Ho % s == 0 and Wo % s == 0, (dy.shape, s)
+    dx = torch.empty(B, Ho // s, Wo // s, C, dtype=dy.dtype, device=dy.device)
+    _lib.check(_lib.load().ssl4gie_bilinear_up_ac_bwd(ptr(dy), ptr(dx), code(dy.dtype), B, Ho // s, Wo // s, C, s,
+                                                      stream()), "bilinear_up_ac_bwd")
+    return dx
+
+
+def chan_write(dst, offset, src):
+    """dst[..., offset : offset + C] = src: one operand of a channel concatenation.  dst [B,H,W,Ct] contiguous; src
+    [B,H,W,C], or [B,C] — then every pixel of image b gets row b (the up-sampling of a 1x1 map)"""
+    _dev(dst, src)
+    B, H, W, Ct = _nhwc(dst)
+    C = src.shape[-1]
+    assert src.dtype == dst.dtype and 0 <= offset and offset + C <= Ct, (src.shape, dst.shape, offset)
+    assert tuple(src.shape) in ((B, H, W, C), (B, C)), (src.shape, dst.shape)
+    rep = H * W if src.dim() == 2 else 1
+    _lib.check(_lib.load().ssl4gie_chan_copy(ptr(src), C, dst.data_ptr() + offset * dst.element_size(), Ct,
+                                             code(dst.dtype), B * H * W, C, rep, stream()), "chan_copy")
+    return dst
+
+
+def chan_read(src, offset, C):
+    """src[..., offset : offset + C] of a contiguous [B,H,W,Ct] map as a dense [B,H,W,C] one"""
+    _dev(src)
+    B, H, W, Ct = _nhwc(src)
+    assert 0 <= offset and offset + C <= Ct, (src.shape, offset, C)
+    out = torch.empty(B, H, W, C, dtype=src.dtype, device=src.device)
+    _lib.check(_lib.load().ssl4gie_chan_copy(src.data_ptr() + offset * src.element_size(), Ct, ptr(out), C,
+                                             code(src.dtype), B * H * W, C, 1, stream()), "chan_copy")
+    return out
 
 
 def pixel_shuffle(g, bias, B, H, W, k, C):
