@@ -51,7 +51,8 @@ int vn(int dt) { return dt == SSL4GIE_BF16 ? 8 : 4; }
 
 // ------------------------------------------------------------------ MaxPool2d(kernel 2, stride 2)
 // x [B, H, W, C] -> y [B, H/2, W/2, C]; backward routes dy to the FIRST maximum of the window in
-// scan order (ATen's tie rule), recomputed from x (no index tensor)
+// scan order (ATen's tie rule), recomputed from x (no index tensor); the selection is ATen's
+// `v > best || isnan(v)`: a NaN anywhere in the window is the output and receives the gradient
 template <typename T>
 __global__ void maxpool2_fwd_kernel(const T* __restrict__ x, T* __restrict__ y, int H, int W, int C,
                                     long long total) {
@@ -72,7 +73,7 @@ __global__ void maxpool2_fwd_kernel(const T* __restrict__ x, T* __restrict__ y, 
         float v[V];
         un<T>(*(const raw_t*)(x + ((b * H + 2 * oy + (t >> 1)) * W + 2 * ox + (t & 1)) * C + c), v);
 #pragma unroll
-        for (int j = 0; j < V; ++j) best[j] = v[j] > best[j] ? v[j] : best[j];
+        for (int j = 0; j < V; ++j) best[j] = (v[j] > best[j] || v[j] != v[j]) ? v[j] : best[j];
     }
     *(raw_t*)(y + (size_t)p * C + c) = pk<T>(best);
 }
@@ -100,7 +101,7 @@ __global__ void maxpool2_bwd_kernel(const T* __restrict__ x, const T* __restrict
         float best = v[0][j];
 #pragma unroll
         for (int t = 1; t < 4; ++t)
-            if (v[t][j] > best) { best = v[t][j]; win[j] = t; }
+            if (v[t][j] > best || v[t][j] != v[t][j]) { best = v[t][j]; win[j] = t; }
     }
 #pragma unroll
     for (int t = 0; t < 4; ++t) {

@@ -506,7 +506,9 @@ __global__ void bn_bwd_apply_kernel(const T* __restrict__ dy, const T* __restric
 }
 
 // ------------------------------------------------------------------ MaxPool2d(3, 2, 1)
-// arg = window position (dy*3+dx) of the first maximum in row-major scan order (ATen's choice)
+// arg = window position (dy*3+dx) of the first maximum in row-major scan order (ATen's choice); ATen's selection is
+// `v > best || isnan(v)`: a NaN anywhere in the window becomes the output, the arg points at it and the backward
+// routes the gradient to it
 template <typename T>
 __global__ void maxpool_fwd_kernel(const T* __restrict__ x, T* __restrict__ y,
                                    unsigned char* __restrict__ arg, int H, int W, int C, int Ho,
@@ -527,7 +529,7 @@ __global__ void maxpool_fwd_kernel(const T* __restrict__ x, T* __restrict__ y,
             const int ix = 2 * ox + dx - 1;
             if (ix < 0 || ix >= W) continue;
             const float v = Elem<T>::ld(x + ((b * H + iy) * W + ix) * C + c);
-            if (!found || v > best) {  // first maximum in scan order
+            if (!found || v > best || v != v) {  // first maximum in scan order; a NaN wins from anywhere (ATen)
                 best = v;
                 bi = dy * 3 + dx;
                 found = true;
@@ -615,7 +617,7 @@ __global__ void maxpool_fwd_vec_kernel(const T* __restrict__ x, T* __restrict__ 
             }
 #pragma unroll
             for (int j = 0; j < V; ++j) {
-                if (!found || v[j] > best[j]) {  // first maximum in scan order
+                if (!found || v[j] > best[j] || v[j] != v[j]) {  // first maximum in scan order; a NaN wins (ATen)
                     best[j] = v[j];
                     bi[j] = (unsigned char)(dy * 3 + dx);
                 }
