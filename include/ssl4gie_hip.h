@@ -19,7 +19,8 @@
  *     metrics ssl4gie_seg_{counts,scores} / ssl4gie_confusion_{update,scores} / ssl4gie_lower_median_{workspace_bytes,f32} / ssl4gie_depth_eval{_workspace_bytes,}
  *     joined it the same way, and so did the detection input entry points ssl4gie_det_color{_workspace_bytes,} / ssl4gie_det_geometry / ssl4gie_det_boxes and the
  *     detection metric ssl4gie_det_map_{workspace_bytes,match,order,accumulate}, and the Faster R-CNN head entry points ssl4gie_nms_{workspace_bytes,segments} /
- *     ssl4gie_rpn_decode / ssl4gie_roi_decode / ssl4gie_roi_align_{fwd,bwd}; revision 12 later LOST ssl4gie_conv3x3_direct_{fwd,wgrad}_affine,
+ *     ssl4gie_rpn_decode / ssl4gie_roi_decode / ssl4gie_roi_align_{fwd,bwd}, and the fine-tuning recipe's ssl4gie_block_{dp_workspace_bytes,fwd_dp,bwd_dp} /
+ *     ssl4gie_drop_path_{add,scale_cast} / ssl4gie_mixup{,_target} / ssl4gie_soft_cross_entropy{_workspace_bytes,}; revision 12 later LOST ssl4gie_conv3x3_direct_{fwd,wgrad}_affine,
  *     ssl4gie_block_wgrad_descs, ssl4gie_wgrad_group and the SSL4GIE_BWD_DEFER_WGRAD flag of ssl4gie_block_bwd with the two opt-in paths of the Python
  *     package that were their only callers (measured null or slower, profiles/HISTORY.md appendix 4) — the number is kept because the suite asserts 12
  *     in nine places; a caller of those four entry points fails at symbol resolution instead; 11: before the sixteen BatchNorm entry points that had grown one per fusion (ssl4gie_bn_fwd / _fwd_partials / _fwd_partials_bits /
@@ -308,6 +309,47 @@ int ssl4gie_block_bwd(const ssl4gie_block_dims* d, const ssl4gie_block_weights* 
                       const float* x_in, const float* dx_out, const void* dx_out_lp,
                       float* dx_in, void* dx_in_lp, int accumulate, void* workspace,
                       void* stream);
+/* Stochastic depth (timm's drop_path with scale_by_keep, main_finetune.py:57; joined ABI 12 as additions).
+ * s_attn / s_mlp: fp32 [B] device tables of the per-sample factor, 0 for a dropped sample and 1 / keep_prob for a
+ * kept one, or NULL for a branch that runs exactly as in ssl4gie_block_fwd / _bwd (same launches):
+ *   x_mid = x_in  + s_attn[b] (proj(attn(ln1 x_in)) + b_proj)
+ *   x_out = x_mid + s_mlp[b]  (fc2(gelu(fc1(ln2 x_mid))) + b_fc2)
+ * The scaled add runs beside the GEMM (product + bias into an fp32 scratch slot, then ssl4gie_drop_path_add), the
+ * backward feeds each branch the operand-type copy s[b] dx (ssl4gie_drop_path_scale_cast) and both LayerNorm
+ * backward passes keep the unscaled residual gradient.  A dropped sample's rows are copies: x_out[b] == x_in[b] and
+ * dx_in[b] == dx_out[b] bit for bit when both branches drop it.  `workspace` is sized by
+ * ssl4gie_block_dp_workspace_bytes (the plain layout plus three [T, D] slots) whether or not a table is NULL; with
+ * s_mlp given dx_out_lp is not read and may be NULL. */
+size_t ssl4gie_block_dp_workspace_bytes(const ssl4gie_block_dims* d);
+int ssl4gie_block_fwd_dp(const ssl4gie_block_dims* d, const ssl4gie_block_weights* w,
+                         const ssl4gie_block_act* a, const float* x_in, float* x_out,
+                         const float* s_attn, const float* s_mlp, void* workspace, void* stream);
+int ssl4gie_block_bwd_dp(const ssl4gie_block_dims* d, const ssl4gie_block_weights* w,
+                         const ssl4gie_block_act* a, const ssl4gie_block_grads* g,
+                         const float* x_in, const float* dx_out, const void* dx_out_lp,
+                         float* dx_in, void* dx_in_lp, const float* s_attn, const float* s_mlp,
+                         int accumulate, void* workspace, void* stream);
+/* the two element-wise kernels behind them; res / t / dx / out fp32 [B, per_sample] (16-byte aligned, per_sample % 4
+ * == 0), s fp32 [B]:  out = s[b] != 0 ? res + s[b] t : res  (t is not read for a dropped sample);
+ * out (out_dtype) = s[b] != 0 ? cast(s[b] dx) : 0  (dx is not read for a dropped sample). */
+int ssl4gie_drop_path_add(const float* res, const float* t, const float* s, float* out, int B,
+                          long long per_sample, void* stream);
+int ssl4gie_drop_path_scale_cast(const float* dx, const float* s, void* out, int out_dtype, int B,
+                                 long long per_sample, void* stream);
+/* Mixup / CutMix of timm.data.Mixup (main_finetune.py:221-226) on a resident fp32 batch x [B, C, H, W], IN PLACE, one
+ * launch.  Sample i is mixed with sample B - 1 - i (an odd B's middle sample with itself); per-sample device tables
+ * lam fp32 [B], box int32 [B, 4] = (y0, y1, x0, x1), use_cutmix uint8 [B]:
+ *   use_cutmix[i] == 0:  x_i = x_i lam_i + x_j (1 - lam_i), each product rounded to fp32, one addition (bit-equal to
+ *                        x.mul(lam).add(x.flip(0).mul(1 - lam)));
+ *   use_cutmix[i] != 0:  x_i[:, y0:y1, x0:x1] = x_j[:, y0:y1, x0:x1].
+ * Both originals are read before either result is written.  A box is only compared against coordinates, never used
+ * in an address; one that is not inside the image (or a NaN lam) turns its sample into NaN.
+ * ssl4gie_mixup_target: out fp32 [B, C], row i = onehot(target_i) lam_i + onehot(target_{B-1-i}) (1 - lam_i) with
+ * one-hot values on / off; a label outside [0, C) gives a NaN row and is never an index. */
+int ssl4gie_mixup(float* x, const float* lam, const int* box, const unsigned char* use_cutmix, int B, int C,
+                  int H, int W, void* stream);
+int ssl4gie_mixup_target(const long long* target, const float* lam, float* out, int B, int C,
+                         float on, float off, void* stream);
 /* The four weight-gradient products of ssl4gie_block_bwd are enqueued on a library-owned
  * non-blocking side stream (one per device, created on first use) and ordered against `stream`
  * with events only: each waits for its dY producer, and `stream` waits for the last of them
@@ -875,6 +917,16 @@ int ssl4gie_infonce_loss(const float* q, const float* k, float* loss, float* dq,
 size_t ssl4gie_cross_entropy_workspace_bytes(int B, int C);
 int ssl4gie_cross_entropy(const float* logits, const long long* target, const float* weight, float* loss,
                           float* dlogits, int B, int C, void* workspace, void* stream);
+/* soft-target cross-entropy (timm's SoftTargetCrossEntropy / LabelSmoothingCrossEntropy, main_finetune.py:292-294;
+ * joined ABI 12 as an addition): loss = mean_b sum_c -t[b,c] log_softmax(x[b])[c], dlogits (may be NULL) =
+ * (softmax(x[b]) sum_c t[b,c] - t[b]) / B.  Exactly one of soft_target fp32 [B, C] and label int64 [B] is given; with a
+ * label t[b,c] = conf [c == label_b] + off (conf = 1 - smoothing, off = smoothing / C), and a label outside [0, C) is
+ * never an index: the loss and that row of dlogits are NaN.  One wave per row, per-block partials summed in fp64 in a
+ * fixed order, no atomics.  Two launches. */
+size_t ssl4gie_soft_cross_entropy_workspace_bytes(int B, int C);
+int ssl4gie_soft_cross_entropy(const float* logits, const float* soft_target, const long long* label,
+                               float conf, float off, float* loss, float* dlogits, int B, int C,
+                               void* workspace, void* stream);
 size_t ssl4gie_bt_loss_workspace_bytes(int D);
 int ssl4gie_bt_loss(const float* c, float* loss, int D, float lambd, void* workspace, void* stream);
 int ssl4gie_bt_loss_grad(const float* c, const float* scale, void* w, void* wt, int dtype, int D, float lambd,

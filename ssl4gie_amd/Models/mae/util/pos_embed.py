@@ -24,3 +24,23 @@ def get_2d_sincos_pos_embed(embed_dim: int, grid_size: int, cls_token: bool = Fa
     if cls_token:
         table = np.concatenate([np.zeros((1, embed_dim)), table], axis=0)
     return table
+
+
+def interpolate_pos_embed(model, checkpoint_model):
+    """Resize a checkpoint's position table to the model's patch grid, in place in the checkpoint dict (reference
+    Models/mae/util/pos_embed.py:75-96, called at main_finetune.py:245): the extra (cls) rows are kept, the grid rows
+    are resampled bicubically with align_corners=False.  Torch ops on one table, at load time."""
+    import torch
+    if "pos_embed" not in checkpoint_model:
+        return
+    table = checkpoint_model["pos_embed"]
+    dim = table.shape[-1]
+    num_patches = model.patch_embed.num_patches
+    extra = model.pos_embed.shape[-2] - num_patches
+    old = int((table.shape[-2] - extra) ** 0.5)
+    new = int(num_patches ** 0.5)
+    if old == new:
+        return
+    grid = table[:, extra:].reshape(-1, old, old, dim).permute(0, 3, 1, 2)
+    grid = torch.nn.functional.interpolate(grid, size=(new, new), mode="bicubic", align_corners=False)
+    checkpoint_model["pos_embed"] = torch.cat((table[:, :extra], grid.permute(0, 2, 3, 1).flatten(1, 2)), dim=1)

@@ -47,9 +47,11 @@ class Mlp(nn.Module):
 
 
 class Block(nn.Module):
-    """Pre-LN block container: norm1, attn.{qkv,proj}, norm2, mlp.{fc1,fc2}."""
+    """Pre-LN block container: norm1, attn.{qkv,proj}, norm2, mlp.{fc1,fc2}.  `drop_path` is timm's stochastic-depth
+    rate of both residual branches, kept as a plain float (no parameter, no buffer: the state_dict is unchanged);
+    engine.run_blocks reads it in training mode."""
 
-    def __init__(self, dim, num_heads, mlp_ratio=4.0, qkv_bias=True, norm_layer=nn.LayerNorm):
+    def __init__(self, dim, num_heads, mlp_ratio=4.0, qkv_bias=True, norm_layer=nn.LayerNorm, drop_path=0.0):
         super().__init__()
         if not qkv_bias:
             raise NotImplementedError("the reference always passes qkv_bias=True")
@@ -58,3 +60,4 @@ class Block(nn.Module):
         self.norm2 = norm_layer(dim)
         self.mlp = Mlp(dim, int(dim * mlp_ratio))
         self.num_heads = num_heads
+        self.drop_path = float(drop_path)

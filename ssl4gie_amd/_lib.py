@@ -239,6 +239,18 @@ PROTOTYPES = {
     "ssl4gie_block_bwd": (i32, [C.POINTER(BlockDims), C.POINTER(BlockWeights),
                                 C.POINTER(BlockAct), C.POINTER(BlockGrads), vp, vp, vp, vp, vp,
                                 i32, vp, vp]),
+    "ssl4gie_block_dp_workspace_bytes": (sz, [C.POINTER(BlockDims)]),
+    "ssl4gie_block_fwd_dp": (i32, [C.POINTER(BlockDims), C.POINTER(BlockWeights),
+                                   C.POINTER(BlockAct), vp, vp, vp, vp, vp, vp]),
+    "ssl4gie_block_bwd_dp": (i32, [C.POINTER(BlockDims), C.POINTER(BlockWeights),
+                                   C.POINTER(BlockAct), C.POINTER(BlockGrads), vp, vp, vp, vp, vp,
+                                   vp, vp, i32, vp, vp]),
+    "ssl4gie_drop_path_add": (i32, [vp, vp, vp, vp, i32, i64, vp]),
+    "ssl4gie_drop_path_scale_cast": (i32, [vp, vp, vp, i32, i32, i64, vp]),
+    "ssl4gie_mixup": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, vp]),
+    "ssl4gie_mixup_target": (i32, [vp, vp, vp, i32, i32, f32, f32, vp]),
+    "ssl4gie_soft_cross_entropy_workspace_bytes": (sz, [i32, i32]),
+    "ssl4gie_soft_cross_entropy": (i32, [vp, vp, vp, f32, f32, vp, vp, i32, i32, vp, vp]),
 }
 
 _lib = None

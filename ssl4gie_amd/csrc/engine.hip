@@ -175,6 +175,28 @@ BwdLayout bwd_layout(const ssl4gie_block_dims* d) {
     return L;
 }
 
+// Stochastic depth (ssl4gie_block_{fwd,bwd}_dp) keeps three more slots behind the plain layout, so that
+// ssl4gie_block_workspace_bytes is unchanged and the no-table path never sees them:
+//   t        fp32 [T, D]   the branch's last product (+ bias) before the scaled add (forward)
+//   dys_out  lp   [T, D]   s_mlp[b] dx_out: dY of fc2's data gradient and of dW_fc2 / db_fc2.  Read by the weight-gradient
+//                          pair on the side stream while the caller's stream goes on: nothing in the call rewrites it
+//                          (dh, which the chain rewrites twice, could not hold it)
+//   dys_mid  lp   [T, D]   s_attn[b] dxmid: dY of proj's data gradient and of dW_proj / db_proj (in f32 mode dxmid_lp
+//                          aliases dxmid, which LayerNorm-1 still needs unscaled as its residual gradient)
+struct DpLayout {
+    size_t t, dys_out, dys_mid, total;
+};
+DpLayout dp_layout(const ssl4gie_block_dims* d, const BwdLayout& L) {
+    const size_t T = (size_t)d->B * d->N, D = d->D, es = esize(d->dtype);
+    DpLayout P;
+    size_t o = L.total;
+    P.t = o; o += align_up(T * D * 4);
+    P.dys_out = o; o += align_up(T * D * es);
+    P.dys_mid = o; o += align_up(T * D * es);
+    P.total = o;
+    return P;
+}
+
 bool dims_ok(const ssl4gie_block_dims* d) {
     return d && d->B > 0 && d->N > 0 && d->D > 0 && d->H > 0 && d->F > 0 && d->D % d->H == 0 &&
            d->D % 4 == 0 && d->F % 4 == 0 &&
@@ -214,13 +236,28 @@ extern "C" size_t ssl4gie_block_workspace_bytes(const ssl4gie_block_dims* d) {
     return bwd_layout(d).total;  // forward only needs the attention workspace (subset)
 }
 
-extern "C" int ssl4gie_block_fwd(const ssl4gie_block_dims* d, const ssl4gie_block_weights* w,
-                                 const ssl4gie_block_act* a, const float* x_in, float* x_out,
-                                 void* workspace, void* stream) {
+namespace {
+// out = res + s[b] (x W^T + bias): the product with its bias into the fp32 scratch `t`, then the scaled add.  The
+// 256-tile NT kernel's epilogue is not touched: the price is one more pass over [T, D].
+int branch_out_dp(const void* x, const void* W, const float* bias, const float* res, const float* s, float* t,
+                  float* out, const ssl4gie_block_dims* d, int k_in, void* stream) {
+    const int T = d->B * d->N, D = d->D;
+    ssl4gie_gemm_desc e;
+    memset(&e, 0, sizeof(e));
+    e.C = t; e.ldc = D; e.dtype_c = SSL4GIE_F32; e.epilogue = SSL4GIE_EPI_BIAS; e.bias = bias;
+    RC(linear_fwd(x, W, T, D, k_in, d->dtype, e, stream));
+    return ssl4gie_drop_path_add(res, t, s, out, d->B, (long long)d->N * D, stream);
+}
+
+// the one forward: s_attn / s_mlp == NULL is the block as it always ran (same launches)
+int block_fwd_impl(const ssl4gie_block_dims* d, const ssl4gie_block_weights* w, const ssl4gie_block_act* a,
+                   const float* x_in, float* x_out, const float* s_attn, const float* s_mlp, void* workspace,
+                   void* stream) {
     REQUIRE(dims_ok(d) && w && a && x_in && x_out);
     const int T = d->B * d->N, D = d->D, F = d->F, dt = d->dtype;
     const BwdLayout L = bwd_layout(d);
-    REQUIRE(workspace || L.total == 0);
+    const DpLayout P = dp_layout(d, L);
+    REQUIRE(workspace || (L.total == 0 && !s_attn && !s_mlp));
     char* ws = (char*)workspace;
 
     RC(ssl4gie_layernorm_fwd(x_in, w->ln1_g, w->ln1_b, a->h1, dt, a->mean1, a->rstd1, T, D,
@@ -231,31 +268,60 @@ extern "C" int ssl4gie_block_fwd(const ssl4gie_block_dims* d, const ssl4gie_bloc
     RC(linear_fwd(a->h1, w->wqkv, T, 3 * D, D, dt, e, stream));
     RC(ssl4gie_attn_fwd(a->qkv, a->attn, a->lse, dt, d->B, d->N, d->H, D / d->H, ws + L.attn_ws,
                         stream));
-    memset(&e, 0, sizeof(e));
-    e.C = a->xmid; e.ldc = D; e.dtype_c = SSL4GIE_F32; e.epilogue = SSL4GIE_EPI_BIAS_RESIDUAL;
-    e.bias = w->bproj; e.residual = x_in; e.ldr = D;
-    RC(linear_fwd(a->attn, w->wproj, T, D, D, dt, e, stream));
+    if (s_attn) {
+        RC(branch_out_dp(a->attn, w->wproj, w->bproj, x_in, s_attn, (float*)(ws + P.t), a->xmid, d, D, stream));
+    } else {
+        memset(&e, 0, sizeof(e));
+        e.C = a->xmid; e.ldc = D; e.dtype_c = SSL4GIE_F32; e.epilogue = SSL4GIE_EPI_BIAS_RESIDUAL;
+        e.bias = w->bproj; e.residual = x_in; e.ldr = D;
+        RC(linear_fwd(a->attn, w->wproj, T, D, D, dt, e, stream));
+    }
     RC(ssl4gie_layernorm_fwd(a->xmid, w->ln2_g, w->ln2_b, a->h2, dt, a->mean2, a->rstd2, T, D,
                              d->eps, stream));
     memset(&e, 0, sizeof(e));
     e.C = a->u; e.ldc = F; e.dtype_c = dt; e.epilogue = SSL4GIE_EPI_BIAS_GELU_GRAD; e.bias = w->bfc1;
     e.out2 = a->g;
     RC(linear_fwd(a->h2, w->wfc1, T, F, D, dt, e, stream));
-    memset(&e, 0, sizeof(e));
-    e.C = x_out; e.ldc = D; e.dtype_c = SSL4GIE_F32; e.epilogue = SSL4GIE_EPI_BIAS_RESIDUAL;
-    e.bias = w->bfc2; e.residual = a->xmid; e.ldr = D;
-    RC(linear_fwd(a->g, w->wfc2, T, D, F, dt, e, stream));
+    if (s_mlp) {
+        RC(branch_out_dp(a->g, w->wfc2, w->bfc2, a->xmid, s_mlp, (float*)(ws + P.t), x_out, d, F, stream));
+    } else {
+        memset(&e, 0, sizeof(e));
+        e.C = x_out; e.ldc = D; e.dtype_c = SSL4GIE_F32; e.epilogue = SSL4GIE_EPI_BIAS_RESIDUAL;
+        e.bias = w->bfc2; e.residual = a->xmid; e.ldr = D;
+        RC(linear_fwd(a->g, w->wfc2, T, D, F, dt, e, stream));
+    }
     return 0;
 }
+}  // namespace
 
-extern "C" int ssl4gie_block_bwd(const ssl4gie_block_dims* d, const ssl4gie_block_weights* w,
-                                 const ssl4gie_block_act* a, const ssl4gie_block_grads* g,
-                                 const float* x_in, const float* dx_out, const void* dx_out_lp,
-                                 float* dx_in, void* dx_in_lp, int accumulate, void* workspace,
-                                 void* stream) {
+extern "C" size_t ssl4gie_block_dp_workspace_bytes(const ssl4gie_block_dims* d) {
+    if (!dims_ok(d)) return 0;
+    return dp_layout(d, bwd_layout(d)).total;
+}
+
+extern "C" int ssl4gie_block_fwd(const ssl4gie_block_dims* d, const ssl4gie_block_weights* w,
+                                 const ssl4gie_block_act* a, const float* x_in, float* x_out,
+                                 void* workspace, void* stream) {
+    return block_fwd_impl(d, w, a, x_in, x_out, nullptr, nullptr, workspace, stream);
+}
+
+// workspace: ssl4gie_block_dp_workspace_bytes (also when both tables are NULL)
+extern "C" int ssl4gie_block_fwd_dp(const ssl4gie_block_dims* d, const ssl4gie_block_weights* w,
+                                    const ssl4gie_block_act* a, const float* x_in, float* x_out,
+                                    const float* s_attn, const float* s_mlp, void* workspace, void* stream) {
+    return block_fwd_impl(d, w, a, x_in, x_out, s_attn, s_mlp, workspace, stream);
+}
+
+namespace {
+// the one backward: s_attn / s_mlp == NULL is the block as it always ran (same launches)
+int block_bwd_impl(const ssl4gie_block_dims* d, const ssl4gie_block_weights* w,
+                   const ssl4gie_block_act* a, const ssl4gie_block_grads* g,
+                   const float* x_in, const float* dx_out, const void* dx_out_lp,
+                   float* dx_in, void* dx_in_lp, const float* s_attn, const float* s_mlp, int accumulate,
+                   void* workspace, void* stream) {
     REQUIRE(dims_ok(d) && w && a && g && x_in && dx_out && dx_in && workspace);
     const int T = d->B * d->N, D = d->D, F = d->F, dt = d->dtype;
-    REQUIRE(dt == SSL4GIE_F32 || dx_out_lp);
+    REQUIRE(dt == SSL4GIE_F32 || dx_out_lp || s_mlp);
     // `accumulate` carries flags: bit 0 accumulate, SSL4GIE_BWD_NO_JOIN, SSL4GIE_BWD_SLOT(s)
     const bool no_join = (accumulate & SSL4GIE_BWD_NO_JOIN) != 0;
     const int slot = (accumulate >> 4) & 3;
@@ -272,6 +338,12 @@ extern "C" int ssl4gie_block_bwd(const ssl4gie_block_dims* d, const ssl4gie_bloc
     float* ln_ws1 = (float*)(ws + L.ln_ws1);
     void* gws = ws + L.gemm_ws;
     const void* dy = (dt == SSL4GIE_F32) ? (const void*)dx_out : dx_out_lp;
+    const DpLayout P = dp_layout(d, L);
+    const long long per_sample = (long long)d->N * D;
+    if (s_mlp) {  // the MLP branch saw s_mlp[b] dx_out; LayerNorm-2 below keeps the unscaled dx_out as its residual gradient
+        RC(ssl4gie_drop_path_scale_cast(dx_out, s_mlp, ws + P.dys_out, dt, d->B, per_sample, stream));
+        dy = ws + P.dys_out;
+    }
     ssl4gie_gemm_desc e, wg, wg2;
     // weight gradients go to the side stream when there is one (see SideStream)
     hipStream_t main_st = (hipStream_t)stream;
@@ -304,8 +376,12 @@ extern "C" int ssl4gie_block_bwd(const ssl4gie_block_dims* d, const ssl4gie_bloc
     // dgamma / dbeta partials: a 6-us launch the data-gradient chain would wait for, 40 per MAE step) runs there
     const bool ln_side = ss != nullptr;
     RC(ssl4gie_layernorm_bwd(dh, dt, a->xmid, w->ln2_g, a->mean2, a->rstd2, dx_out, dxmid,
-                             dt == SSL4GIE_F32 ? nullptr : dxmid_lp, dt, ln_side ? nullptr : g->ln2_g,
+                             (dt == SSL4GIE_F32 || s_attn) ? nullptr : dxmid_lp, dt, ln_side ? nullptr : g->ln2_g,
                              ln_side ? nullptr : g->ln2_b, accumulate, ln_ws, T, D, stream));
+    if (s_attn) {  // the attention branch saw s_attn[b] dxmid; LayerNorm-1 below keeps the unscaled dxmid
+        RC(ssl4gie_drop_path_scale_cast(dxmid, s_attn, ws + P.dys_mid, dt, d->B, per_sample, stream));
+        dxmid_lp = ws + P.dys_mid;
+    }
     // ---- proj
     memset(&e, 0, sizeof(e));
     e.C = dattn; e.ldc = D; e.dtype_c = dt; e.epilogue = SSL4GIE_EPI_NONE;
@@ -340,6 +416,26 @@ extern "C" int ssl4gie_block_bwd(const ssl4gie_block_dims* d, const ssl4gie_bloc
         HIP_RET(hipStreamWaitEvent(main_st, ss->ev[4], 0));
     }
     return 0;
+}
+}  // namespace
+
+extern "C" int ssl4gie_block_bwd(const ssl4gie_block_dims* d, const ssl4gie_block_weights* w,
+                                 const ssl4gie_block_act* a, const ssl4gie_block_grads* g,
+                                 const float* x_in, const float* dx_out, const void* dx_out_lp,
+                                 float* dx_in, void* dx_in_lp, int accumulate, void* workspace,
+                                 void* stream) {
+    return block_bwd_impl(d, w, a, g, x_in, dx_out, dx_out_lp, dx_in, dx_in_lp, nullptr, nullptr, accumulate,
+                          workspace, stream);
+}
+
+// workspace: ssl4gie_block_dp_workspace_bytes (also when both tables are NULL); with s_mlp given dx_out_lp is not read
+extern "C" int ssl4gie_block_bwd_dp(const ssl4gie_block_dims* d, const ssl4gie_block_weights* w,
+                                    const ssl4gie_block_act* a, const ssl4gie_block_grads* g,
+                                    const float* x_in, const float* dx_out, const void* dx_out_lp,
+                                    float* dx_in, void* dx_in_lp, const float* s_attn, const float* s_mlp,
+                                    int accumulate, void* workspace, void* stream) {
+    return block_bwd_impl(d, w, a, g, x_in, dx_out, dx_out_lp, dx_in, dx_in_lp, s_attn, s_mlp, accumulate,
+                          workspace, stream);
 }
 
 extern "C" int ssl4gie_wgrad_wait(int slot, void* stream) {

@@ -536,6 +536,73 @@ __global__ __launch_bounds__(256) void ce_apply_kernel(const float* __restrict__
     }
 }
 
+// ------------------------------------------------------------------ soft-target / label-smoothing cross-entropy
+// loss = mean_b sum_c -t[b, c] log_softmax(x[b])[c] with t either given ([B, C]: Mixup's soft targets, timm's
+// SoftTargetCrossEntropy) or built here from a label (timm's LabelSmoothingCrossEntropy: t = conf [c == y] + off).
+// One wave per row: max and sum in one online pass, then a second pass over the (cached) row for the loss terms and
+// dlogits = (softmax sum_c t - t) / B, which does not assume sum_c t = 1.  fp32 workspace: part [CE_MAXBLK].
+__global__ __launch_bounds__(256) void soft_ce_rows_kernel(const float* __restrict__ logits,
+                                                           const float* __restrict__ tsoft,
+                                                           const long long* __restrict__ label, float conf, float off,
+                                                           float* __restrict__ ws, float* __restrict__ dlogits, int B,
+                                                           int C) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    float total = 0.f;  // wave total, lane 0's copy is the one used
+    for (long long row = (long long)blockIdx.x * 4 + wave; row < B; row += (long long)gridDim.x * 4) {
+        const float* x = logits + (size_t)row * C;
+        float m = -INFINITY, s = 0.f;
+        for (int c = lane; c < C; c += 64) {
+            const float v = x[c];
+            if (v > m) { s = s * expf(m - v) + 1.f; m = v; }
+            else s += expf(v - m);
+        }
+        const float M = wave_max(m);
+        s = wave_sum(m == -INFINITY ? 0.f : s * expf(m - M));
+        const float logs = logf(s);
+        long long tg = 0;
+        bool ok = true;
+        if (!tsoft) {
+            tg = label[row];
+            ok = tg >= 0 && tg < C;  // a label outside [0, C) is never used as an index
+        }
+        const float* t = tsoft ? tsoft + (size_t)row * C : nullptr;
+        float tsum = 0.f, nll = 0.f;
+        for (int c = lane; c < C; c += 64) {
+            const float tc = t ? t[c] : (c == tg ? conf : 0.f) + off;
+            tsum += tc;
+            nll += tc * (logs - (x[c] - M));  // -t log_softmax
+        }
+        tsum = wave_sum(tsum);
+        nll = wave_sum(nll);
+        total += ok ? nll : NAN;
+        if (dlogits) {
+            float* d = dlogits + (size_t)row * C;
+            for (int c = lane; c < C; c += 64) {
+                const float tc = t ? t[c] : (c == tg ? conf : 0.f) + off;
+                d[c] = ok ? (expf((x[c] - M) - logs) * tsum - tc) / (float)B : NAN;
+            }
+        }
+    }
+    __shared__ float sh[4];
+    if (lane == 0) sh[wave] = total;
+    __syncthreads();
+    if (threadIdx.x == 0) ws[blockIdx.x] = (sh[0] + sh[1]) + (sh[2] + sh[3]);
+}
+__global__ __launch_bounds__(256) void soft_ce_finalize_kernel(const float* __restrict__ ws, float* __restrict__ loss,
+                                                               int B, int nblk) {
+    __shared__ double sh[256];
+    const int t = threadIdx.x;
+    double a = 0.0;
+    for (int p = t; p < nblk; p += 256) a += (double)ws[p];
+    sh[t] = a;
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) {
+        if (t < o) sh[t] += sh[t + o];
+        __syncthreads();
+    }
+    if (t == 0) *loss = (float)(sh[0] / (double)B);
+}
+
 // ------------------------------------------------------------------ Barlow Twins loss terms
 constexpr int BT_MAXBLK = 1024;
 constexpr int BT_TILE = 64;
@@ -735,6 +802,26 @@ extern "C" int ssl4gie_cross_entropy(const float* logits, const long long* targe
     hipLaunchKernelGGL(ce_rows_kernel, dim3(nblk), dim3(256), 0, st, logits, target, weight, ws, B, C);
     hipLaunchKernelGGL(ce_apply_kernel, dim3(dlogits ? nblk : 1), dim3(256), 0, st, logits, target, weight,
                        (const float*)ws, loss, dlogits, B, C, nblk);
+    LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" size_t ssl4gie_soft_cross_entropy_workspace_bytes(int B, int C) {
+    if (B < 1 || C < 1) return 0;
+    return (size_t)CE_MAXBLK * sizeof(float);
+}
+
+extern "C" int ssl4gie_soft_cross_entropy(const float* logits, const float* soft_target, const long long* label,
+                                          float conf, float off, float* loss, float* dlogits, int B, int C,
+                                          void* workspace, void* stream) {
+    REQUIRE(logits && loss && workspace && B >= 1 && C >= 1);
+    REQUIRE((soft_target != nullptr) != (label != nullptr));
+    hipStream_t st = (hipStream_t)stream;
+    float* ws = (float*)workspace;
+    const int nblk = ce_blocks(B);
+    hipLaunchKernelGGL(soft_ce_rows_kernel, dim3(nblk), dim3(256), 0, st, logits, soft_target, label, conf, off, ws,
+                       dlogits, B, C);
+    hipLaunchKernelGGL(soft_ce_finalize_kernel, dim3(1), dim3(256), 0, st, (const float*)ws, loss, B, nblk);
     LAUNCH_CHECK();
     return 0;
 }

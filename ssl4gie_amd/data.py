@@ -46,6 +46,14 @@ ops.det_geometry and ops.det_boxes.  `DetectionLoader` yields the reference's co
     for images, targets in loader:                                      # train_detection.py:67-69, as written
         images = list(image.cuda(rank) for image in images)             # already there
         targets = [{k: v.cuda(rank) for k, v in t.items()} for t in targets]
+
+The MAE fine-tuning recipe mixes batches that are already on the device (Models/mae/main_finetune.py:221-226,
+engine_finetune.py:53): `Mixup` takes timm.data.Mixup's keywords, draws lambda, the mixup / cutmix choice and the boxes
+on the host (`mixup_tables`, a pure function of a numpy RandomState), uploads them in one small copy and mixes the
+batch in place with one launch of ops.mixup; ops.mixup_target builds the soft targets.
+
+    mixup_fn = Mixup(mixup_alpha=0.8, cutmix_alpha=1.0, label_smoothing=0.1, num_classes=1000)
+    samples, targets = mixup_fn(samples, targets)                       # engine_finetune.py:53, as written
 """
 from __future__ import annotations
 
@@ -681,3 +689,160 @@ class DeviceLoader:
                 idx = []
         if idx and not self.drop_last:
             yield self._batch(idx)
+
+
+# ------------------------------------------------------------------------------------------------
+# Mixup / CutMix of the MAE fine-tuning recipe (timm.data.Mixup; reference Models/mae/main_finetune.py:221-226)
+# ------------------------------------------------------------------------------------------------
+def _cutmix_boxes(rs, H, W, lam, minmax, correct_lam):
+    """timm's rand_bbox / rand_bbox_minmax + the lambda correction for a vector of lambdas: (y0, y1, x0, x1) int
+    arrays and the lambdas that go with them, 1 - area / (H W) when corrected"""
+    n = lam.shape[0]
+    if minmax is not None:
+        ch = rs.randint(int(H * minmax[0]), int(H * minmax[1]), size=n)
+        cw = rs.randint(int(W * minmax[0]), int(W * minmax[1]), size=n)
+        y0 = rs.randint(0, H - ch)
+        x0 = rs.randint(0, W - cw)
+        y1, x1 = y0 + ch, x0 + cw
+    else:
+        ratio = np.sqrt(1.0 - lam.astype(np.float64))
+        ch, cw = (H * ratio).astype(np.int64), (W * ratio).astype(np.int64)
+        cy, cx = rs.randint(0, H, size=n), rs.randint(0, W, size=n)
+        y0, y1 = np.clip(cy - ch // 2, 0, H), np.clip(cy + ch // 2, 0, H)
+        x0, x1 = np.clip(cx - cw // 2, 0, W), np.clip(cx + cw // 2, 0, W)
+    if correct_lam or minmax is not None:
+        lam = 1.0 - ((y1 - y0) * (x1 - x0)) / float(H * W)
+    return y0, y1, x0, x1, lam
+
+
+def mixup_tables(rs, B, H, W, mixup_alpha=1.0, cutmix_alpha=0.0, cutmix_minmax=None, prob=1.0, switch_prob=0.5,
+                 mode="batch", correct_lam=True):
+    """The per-sample tables of one Mixup call, a pure function of a numpy RandomState (which it advances):
+    lam fp32 [B], box int32 [B, 4] = (y0, y1, x0, x1), use_cutmix uint8 [B].  Sample i is mixed with B - 1 - i.
+    use_cutmix[i] = 1 copies the partner's box into sample i (lam is then 1 - area / (H W)); an unmixed sample
+    (lam = 1) is the empty box, so it comes through bit for bit; use_cutmix[i] = 0 blends with lam[i].  The modes of
+    timm differ only in how the tables are filled: `batch` one draw repeated, `elem` one draw per sample, `pair` one
+    draw per pair, mirrored (an odd batch's middle sample stays unmixed)."""
+    if mode not in ("batch", "pair", "elem"):
+        raise ValueError(f"mode must be 'batch', 'pair' or 'elem', got {mode!r}")
+    if cutmix_minmax is not None:
+        assert len(cutmix_minmax) == 2
+        cutmix_alpha = 1.0   # as timm: the box is drawn from the range, lambda follows from its area
+    if not (mixup_alpha > 0.0 or cutmix_alpha > 0.0):
+        raise ValueError("one of mixup_alpha, cutmix_alpha, cutmix_minmax must be set")
+    n = {"batch": 1, "pair": B // 2, "elem": B}[mode]
+    on = rs.rand(n) < prob
+    if mixup_alpha > 0.0 and cutmix_alpha > 0.0:
+        cut = rs.rand(n) < switch_prob
+        lam = np.where(cut, rs.beta(cutmix_alpha, cutmix_alpha, size=n), rs.beta(mixup_alpha, mixup_alpha, size=n))
+    elif mixup_alpha > 0.0:
+        cut = np.zeros(n, dtype=bool)
+        lam = rs.beta(mixup_alpha, mixup_alpha, size=n)
+    else:
+        cut = np.ones(n, dtype=bool)
+        lam = rs.beta(cutmix_alpha, cutmix_alpha, size=n)
+    lam = np.where(on, lam, 1.0).astype(np.float32)
+    y0, y1, x0, x1, lam_box = _cutmix_boxes(rs, H, W, lam, cutmix_minmax, correct_lam)
+    cut = cut & on & (lam != 1.0)
+    lam = np.where(cut, lam_box, lam).astype(np.float32)
+    unmixed = lam == 1.0
+    box = np.stack([y0, y1, x0, x1], axis=1).astype(np.int32)
+    box[~cut] = 0
+    use = (cut | unmixed).astype(np.uint8)   # an unmixed sample: the empty box
+    if mode == "batch":
+        lam, box, use = np.repeat(lam, B), np.repeat(box, B, axis=0), np.repeat(use, B)
+    elif mode == "pair":
+        mid = B - 2 * n   # 1 for an odd batch
+        lam = np.concatenate([lam, np.ones(mid, np.float32), lam[::-1]])
+        box = np.concatenate([box, np.zeros((mid, 4), np.int32), box[::-1]])
+        use = np.concatenate([use, np.ones(mid, np.uint8), use[::-1]])
+    return np.ascontiguousarray(lam, np.float32), np.ascontiguousarray(box, np.int32), np.ascontiguousarray(use, np.uint8)
+
+
+def mixup_torch(x, lam, box, use_cutmix):
+    """the torch formulation of the image kernel on tensors of any device, out of place: x [B, C, H, W] fp32 and the
+    tables of mixup_tables as tensors -> the mixed batch (blend: x.mul(lam).add(x.flip(0).mul(1 - lam)))"""
+    B, _, H, W = x.shape
+    xf = x.flip(0)
+    l4 = lam.to(x.dtype).view(B, 1, 1, 1)
+    blend = x.mul(l4).add(xf.mul(1 - l4))
+    ys = torch.arange(H, device=x.device).view(1, H, 1)
+    xs = torch.arange(W, device=x.device).view(1, 1, W)
+    b = box.to(torch.int64)
+    inside = ((ys >= b[:, 0].view(B, 1, 1)) & (ys < b[:, 1].view(B, 1, 1)) &
+              (xs >= b[:, 2].view(B, 1, 1)) & (xs < b[:, 3].view(B, 1, 1))).unsqueeze(1)
+    return torch.where(use_cutmix.view(B, 1, 1, 1) != 0, torch.where(inside, xf, x), blend)
+
+
+def mixup_target_torch(target, lam, num_classes, smoothing):
+    """timm's mixup_target on tensors of any device: fp32 [B, C] = onehot(y) lam + onehot(y.flip(0)) (1 - lam) with
+    one-hot values off = smoothing / C and on = 1 - smoothing + off"""
+    off = smoothing / num_classes
+    on = 1.0 - smoothing + off
+    t = target.long().view(-1, 1)
+    y1 = torch.full((t.shape[0], num_classes), off, dtype=torch.float32, device=target.device).scatter_(1, t, on)
+    y2 = torch.full((t.shape[0], num_classes), off, dtype=torch.float32, device=target.device).scatter_(1, t.flip(0), on)
+    l2 = lam.to(torch.float32).view(-1, 1)
+    return y1 * l2 + y2 * (1.0 - l2)
+
+
+class Mixup:
+    """timm.data.Mixup with its constructor keywords, for batches that live on the device: `__call__(x, target) ->
+    (x, soft_target)` mixes x [B, C, H, W] fp32 IN PLACE (one launch of ops.mixup) and returns fp32 [B, num_classes]
+    soft targets (a second small launch).  lambda, the mixup / cutmix choice and the boxes are drawn on the host
+    from `rng` (a numpy RandomState; a few numbers per batch, mixup_tables) and reach the device in one small
+    non-blocking copy; nothing is read back.  CPU tensors take the torch formulation.  Unlike timm an odd batch is
+    accepted: its middle sample is mixed with itself."""
+
+    def __init__(self, mixup_alpha=1., cutmix_alpha=0., cutmix_minmax=None, prob=1.0, switch_prob=0.5, mode="batch",
+                 correct_lam=True, label_smoothing=0.1, num_classes=1000, rng=None):
+        self.mixup_alpha, self.cutmix_alpha, self.cutmix_minmax = mixup_alpha, cutmix_alpha, cutmix_minmax
+        self.mix_prob, self.switch_prob, self.mode, self.correct_lam = prob, switch_prob, mode, correct_lam
+        self.label_smoothing, self.num_classes = label_smoothing, num_classes
+        self.mixup_enabled = True   # timm's switch: set to False to pass batches through unmixed
+        self.rng = rng if rng is not None else np.random.RandomState()
+        self._staging = []          # [pinned buffer, event of its last copy] x 2, used in turn
+        self._turn = 0
+        mixup_tables(np.random.RandomState(0), 2, 8, 8, mixup_alpha, cutmix_alpha, cutmix_minmax, prob, switch_prob,
+                     mode, correct_lam)   # validates the keywords
+
+    def draw(self, B, H, W):
+        """the numpy tables of the next call (advances `rng`)"""
+        return mixup_tables(self.rng, B, H, W, self.mixup_alpha, self.cutmix_alpha, self.cutmix_minmax,
+                            self.mix_prob if self.mixup_enabled else 0.0, self.switch_prob, self.mode, self.correct_lam)
+
+    def _upload(self, lam, box, use, device):
+        """lam | box | use_cutmix through one pinned staging buffer and one non-blocking copy"""
+        B = lam.shape[0]
+        nbytes = 21 * B
+        if len(self._staging) < 2 or self._staging[0][0].numel() < nbytes:
+            self._staging = [[torch.empty(max(nbytes, 21 * 256), dtype=torch.uint8).pin_memory(), None] for _ in range(2)]
+        slot = self._staging[self._turn]
+        self._turn ^= 1
+        if slot[1] is not None:
+            slot[1].synchronize()   # the copy issued two calls ago: long done
+        host = slot[0].numpy()
+        host[:4 * B] = lam.view(np.uint8)
+        host[4 * B:20 * B] = box.reshape(-1).view(np.uint8)
+        host[20 * B:nbytes] = use
+        dev = slot[0][:nbytes].to(device, non_blocking=True)
+        slot[1] = torch.cuda.Event()
+        slot[1].record()
+        return dev[:4 * B].view(torch.float32), dev[4 * B:20 * B].view(torch.int32).view(B, 4), dev[20 * B:]
+
+    def apply_tables(self, x, target, lam, box, use_cutmix):
+        """mix with given tables (tensors on x's device)"""
+        if x.is_cuda:
+            ops.mixup(x, lam, box, use_cutmix)
+            return x, ops.mixup_target(target, lam, self.num_classes, self.label_smoothing)
+        x.copy_(mixup_torch(x, lam, box, use_cutmix))
+        return x, mixup_target_torch(target, lam, self.num_classes, self.label_smoothing)
+
+    def __call__(self, x, target):
+        B, _, H, W = x.shape
+        lam, box, use = self.draw(B, H, W)
+        if x.is_cuda:
+            tabs = self._upload(lam, box, use, x.device)
+        else:
+            tabs = (torch.from_numpy(lam), torch.from_numpy(box), torch.from_numpy(use))
+        return self.apply_tables(x, target, *tabs)

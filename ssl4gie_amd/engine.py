@@ -388,6 +388,10 @@ class StackCfg:
     lp: LPCache
     on_block_grads: Optional[Callable[[int], None]] = None  # optional per-block call-back (unused by
     # parallel.DataParallel, which takes readiness from autograd's post-accumulate-grad hooks)
+    # stochastic depth: None (the stack issues exactly the calls it always did), or (scales, use): fp32 device tensor
+    # [depth, 2, B] of per-sample factors (row 0 the attention branch, row 1 the MLP branch) and, per block, whether
+    # its tables are passed (False: NULL, the block runs as without the feature)
+    drop: Optional[tuple] = None
 
 
 def _block_params(blk):
@@ -445,7 +449,13 @@ class BlockStackFn(torch.autograd.Function):
         x = x.contiguous()
         es = 2 if cfg.dtype == torch.bfloat16 else 4
         dims = BlockDims(B, N, D, cfg.heads, F, ops.code(cfg.dtype), float(cfg.eps))
-        wsb = L.ssl4gie_block_workspace_bytes(C.byref(dims))
+        drop = cfg.drop
+        if drop is not None:
+            scales, use = drop
+            assert scales.is_cuda and scales.dtype == torch.float32 and scales.is_contiguous() and \
+                tuple(scales.shape) == (depth, 2, B) and len(use) == depth, "drop_scales: fp32 device [depth, 2, B]"
+            sptr = [(scales[i, 0].data_ptr(), scales[i, 1].data_ptr()) if use[i] else (0, 0) for i in range(depth)]
+        wsb = (L.ssl4gie_block_dp_workspace_bytes if drop is not None else L.ssl4gie_block_workspace_bytes)(C.byref(dims))
         assert wsb > 0
         ws = torch.empty(wsb, dtype=torch.uint8, device=x.device)
         layout = _ActArena(B, N, D, cfg.heads, F, es)
@@ -461,8 +471,13 @@ class BlockStackFn(torch.autograd.Function):
             wstructs.append(w)
             a = layout.struct(acts.data_ptr() + (i if cfg.need_bwd else 0) * layout.total)
             xo = torch.empty_like(x)
-            _lib.check(L.ssl4gie_block_fwd(C.byref(dims), C.byref(w), C.byref(a), xs[-1].data_ptr(),
-                                           xo.data_ptr(), ws.data_ptr(), st), f"block_fwd[{i}]")
+            if drop is not None:
+                _lib.check(L.ssl4gie_block_fwd_dp(C.byref(dims), C.byref(w), C.byref(a), xs[-1].data_ptr(),
+                                                  xo.data_ptr(), sptr[i][0], sptr[i][1], ws.data_ptr(), st),
+                           f"block_fwd_dp[{i}]")
+            else:
+                _lib.check(L.ssl4gie_block_fwd(C.byref(dims), C.byref(w), C.byref(a), xs[-1].data_ptr(),
+                                               xo.data_ptr(), ws.data_ptr(), st), f"block_fwd[{i}]")
             xs.append(xo)
         outs = [xs[depth]] + [xs[t + 1] for t in cfg.taps]
         if cfg.need_bwd:
@@ -471,6 +486,7 @@ class BlockStackFn(torch.autograd.Function):
             ctx.wstructs, ctx.keepalive = wstructs, keepalive
             ctx.params = params
             ctx.depth = depth
+            ctx.sptr = sptr if drop is not None else None   # (cfg.drop keeps the table alive)
         return tuple(outs)
 
     @staticmethod
@@ -490,8 +506,16 @@ class BlockStackFn(torch.autograd.Function):
         dx, dx_lp = ops.add_cast(dx, pending_tap, want_f32=True, lp_dtype=lp)
         nojoin = lp is not None and depth > 1
         if nojoin:
-            ring = [ctx.ws, torch.empty_like(ctx.ws)]
+            ring = [ctx.ws, torch.empty_like(ctx.ws)]   # (with stochastic depth: the larger workspace, both times)
             keep = [[], []]
+        sptr = ctx.sptr
+
+        def block_bwd(i, a, g, dx, dx_lp, dxn, dxn_lp, flags, ws):
+            head = (C.byref(dims), C.byref(ctx.wstructs[i]), C.byref(a), C.byref(g), ctx.xs[i].data_ptr(),
+                    dx.data_ptr(), ops.ptr(dx_lp), dxn.data_ptr(), ops.ptr(dxn_lp))
+            if sptr is not None:
+                return L.ssl4gie_block_bwd_dp(*head, sptr[i][0], sptr[i][1], flags, ws.data_ptr(), st)
+            return L.ssl4gie_block_bwd(*head, flags, ws.data_ptr(), st)
         for i in range(depth - 1, -1, -1):
             if i != depth - 1 and i in tap_g:
                 dx, dx_lp = ops.add_cast(dx, tap_g[i].contiguous(), want_f32=True, lp_dtype=lp)
@@ -507,27 +531,22 @@ class BlockStackFn(torch.autograd.Function):
                 setattr(g, name, t.data_ptr())
             a = layout.struct(ctx.acts.data_ptr() + i * layout.total)
             dxn = torch.empty_like(x0)
-            dxn_lp = torch.empty(x0.shape, dtype=lp, device=x0.device) if lp else None
+            # (a block with an MLP-branch table reads its own scaled copy of dx, not the operand copy)
+            next_scales_dx = sptr is not None and i > 0 and sptr[i - 1][1] != 0
+            dxn_lp = torch.empty(x0.shape, dtype=lp, device=x0.device) if lp and not next_scales_dx else None
             if nojoin:
                 # two workspaces in alternation: the caller's stream does not wait for this block's weight
                 # gradients (side stream) — only, two blocks later, before their operands are overwritten
                 k = (depth - 1 - i) % 2
                 _lib.check(L.ssl4gie_wgrad_wait(k, st), "wgrad_wait")
                 keep[k].clear()
-                _lib.check(L.ssl4gie_block_bwd(C.byref(dims), C.byref(ctx.wstructs[i]), C.byref(a),
-                                               C.byref(g), ctx.xs[i].data_ptr(), dx.data_ptr(),
-                                               ops.ptr(dx_lp), dxn.data_ptr(), ops.ptr(dxn_lp),
-                                               int(accumulate) | _lib.BWD_NO_JOIN | (k << 4), ring[k].data_ptr(), st),
-                           f"block_bwd[{i}]")
+                _lib.check(block_bwd(i, a, g, dx, dx_lp, dxn, dxn_lp, int(accumulate) | _lib.BWD_NO_JOIN | (k << 4),
+                                     ring[k]), f"block_bwd[{i}]")
                 keep[k] += [dx, dx_lp, scratch]   # dY of dW_fc2 / frozen-parameter scratch: read on the side stream
                 if cfg.on_block_grads is not None:
                     cfg.on_block_grads(i)
             else:
-                _lib.check(L.ssl4gie_block_bwd(C.byref(dims), C.byref(ctx.wstructs[i]), C.byref(a),
-                                               C.byref(g), ctx.xs[i].data_ptr(), dx.data_ptr(),
-                                               ops.ptr(dx_lp), dxn.data_ptr(), ops.ptr(dxn_lp),
-                                               int(accumulate), ctx.ws.data_ptr(), st),
-                           f"block_bwd[{i}]")
+                _lib.check(block_bwd(i, a, g, dx, dx_lp, dxn, dxn_lp, int(accumulate), ctx.ws), f"block_bwd[{i}]")
                 if cfg.on_block_grads is not None:
                     cfg.on_block_grads(i)
             dx, dx_lp = dxn, dxn_lp
@@ -539,16 +558,46 @@ class BlockStackFn(torch.autograd.Function):
         return (dx, None) + tuple(returns)
 
 
+_KEEP_TABLES = {}
+
+
+def draw_drop_scales(rates: Sequence[float], B: int, device) -> torch.Tensor:
+    """timm's drop_path (scale_by_keep=True) for a whole stack at once: fp32 [len(rates), 2, B] on `device`, entry
+    = bernoulli(keep) / keep with keep = 1 - rate of its block.  The keep table is uploaded once per (device, rates);
+    the draw is device work only (no host synchronisation)."""
+    rates = tuple(float(r) for r in rates)
+    assert all(0.0 <= r < 1.0 for r in rates), "drop_path rates must lie in [0, 1)"
+    key = (str(device), rates)
+    keep = _KEEP_TABLES.get(key)
+    if keep is None:
+        keep = _KEEP_TABLES[key] = torch.tensor([1.0 - r for r in rates], dtype=torch.float32).view(-1, 1, 1).to(
+            device, non_blocking=True)
+    return torch.bernoulli(keep.expand(len(rates), 2, B)).div_(keep).contiguous()
+
+
 def run_blocks(blocks: Sequence[nn.Module], x: torch.Tensor, heads: int, eps: float, dtype,
                sink: GradSink, taps: Sequence[int] = (), lp: LPCache = None,
-               on_block_grads=None):
-    """Run a list of Block parameter-holders; returns (x_out, [tap outputs])."""
+               on_block_grads=None, drop_scales: Optional[torch.Tensor] = None):
+    """Run a list of Block parameter-holders; returns (x_out, [tap outputs]).
+
+    drop_scales: fp32 device tensor [depth, 2, B] of per-sample stochastic-depth factors (0, or 1 / keep_prob),
+    [:, 0] for the attention branch and [:, 1] for the MLP branch, applied as given to every block.  When it is
+    None, gradients are needed and a block in training mode carries `drop_path` > 0, the factors are drawn here
+    (draw_drop_scales); blocks whose rate is 0 then run exactly as without the feature.  Otherwise — every rate 0,
+    eval(), no_grad — the stack issues the calls it always did."""
     params: List[torch.Tensor] = []
     for b in blocks:
         params += _block_params(b)
     need = torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in params))
+    drop = None
+    if drop_scales is not None:
+        drop = (drop_scales.contiguous(), (True,) * len(blocks))
+    elif need:
+        rates = [float(getattr(b, "drop_path", 0.0)) if b.training else 0.0 for b in blocks]
+        if any(r > 0.0 for r in rates):
+            drop = (draw_drop_scales(rates, x.shape[0], x.device), tuple(r > 0.0 for r in rates))
     cfg = StackCfg(heads=heads, eps=eps, dtype=dtype, taps=tuple(taps), need_bwd=need, sink=sink,
-                   lp=lp or _GLOBAL_LP, on_block_grads=on_block_grads)
+                   lp=lp or _GLOBAL_LP, on_block_grads=on_block_grads, drop=drop)
     outs = BlockStackFn.apply(x, cfg, *params)
     return outs[0], list(outs[1:])
 
@@ -985,11 +1034,11 @@ class EngineModule(nn.Module):
         return LinearFn.apply(x, lin.weight, lin.bias, self.dtype_, out_dtype or self.dtype_,
                               self.sink(), self._lp)
 
-    def _blocks(self, blocks, x, heads, eps, taps=()):
+    def _blocks(self, blocks, x, heads, eps, taps=(), drop_scales=None):
         sink = self.sink()
         hook = None
         if sink.tracker is not None:
             blist = list(blocks)
             hook = lambda i: sink.note_done(_block_params(blist[i]))
         return run_blocks(blocks, x, heads, eps, self.dtype_, sink, taps=taps, lp=self._lp,
-                          on_block_grads=hook)
+                          on_block_grads=hook, drop_scales=drop_scales)

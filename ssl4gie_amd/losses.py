@@ -3,7 +3,8 @@
 the torch formulations below are that path, and the parity reference.  On the HIP device the two
 module classes run fused device kernels instead (csrc/loss_ops.hip — value and
 gradient in five / three launches instead of ~100 small ones); SSL4GIE_FUSED_LOSS=0 or CPU tensors
-select the torch formulation.  The same file holds the loss heads of the other workloads: `CrossEntropyLoss`
+select the torch formulation.  The same file holds the loss heads of the other workloads: `SoftTargetCrossEntropy` /
+`LabelSmoothingCrossEntropy` (the MAE fine-tuning recipe, `Models/mae/main_finetune.py:292-294`), `CrossEntropyLoss`
 (the classification finetune's weighted cross-entropy, `Classification/train_classification.py:278`) and
 `info_nce` (MoCo-v3's contrastive loss, `Models/moco_v3/moco/builder.py:63-73`).  Same call signature and numerics as the reference's
 `Depth_estimation/Metrics/losses.py` (scale-and-shift-invariant depth loss, :120-146): per-image
@@ -249,3 +250,65 @@ def info_nce(q, k_all, T, label_offset=0):
         return _InfoNceFn.apply(q, k_all, T, label_offset)
     return info_nce_normalized(nn.functional.normalize(q, dim=1), nn.functional.normalize(k_all, dim=1), T,
                                label_offset)
+
+
+class _SoftCeFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, logits, soft_target, label, smoothing):
+        from . import _lib
+        from .ops import ptr, stream
+        L = _lib.load()
+        x = logits.contiguous().float()
+        B, C = x.shape
+        t = None if soft_target is None else soft_target.contiguous().float()
+        lab = None if label is None else label.contiguous()
+        conf, off = (1.0 - smoothing, smoothing / C) if label is not None else (0.0, 0.0)
+        ws = torch.empty(L.ssl4gie_soft_cross_entropy_workspace_bytes(B, C), dtype=torch.uint8, device=x.device)
+        loss = torch.empty((), dtype=torch.float32, device=x.device)
+        dx = torch.empty_like(x)
+        _lib.check(L.ssl4gie_soft_cross_entropy(ptr(x), ptr(t), ptr(lab), conf, off, ptr(loss), ptr(dx), B, C, ptr(ws),
+                                                stream()), "soft_cross_entropy")
+        ctx.save_for_backward(dx)
+        ctx.dtype = logits.dtype
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        (dx,) = ctx.saved_tensors
+        return (dx * g).to(ctx.dtype), None, None, None
+
+
+def _soft_ce_fused_ok(logits, other, other_dtype):
+    return (_fused_ok(logits, other) and logits.dim() == 2 and other.dtype == other_dtype
+            and logits.dtype in (torch.float32, torch.bfloat16))
+
+
+class SoftTargetCrossEntropy(nn.Module):
+    """timm's `SoftTargetCrossEntropy` (the criterion behind Mixup, `main_finetune.py:292`):
+    mean_b sum_c -target[b, c] log_softmax(x[b])[c]; the targets get no gradient.  One fused value-and-gradient
+    kernel pair for fp32 / bf16 logits [B, C] with fp32 targets [B, C] on the device; the torch formulation for CPU
+    tensors, SSL4GIE_FUSED_LOSS=0 and every other rank or dtype."""
+
+    def forward(self, x, target):
+        if _soft_ce_fused_ok(x, target, torch.float32) and target.shape == x.shape and not target.requires_grad:
+            return _SoftCeFn.apply(x, target, None, 0.0)
+        return torch.sum(-target * nn.functional.log_softmax(x, dim=-1), dim=-1).mean()
+
+
+class LabelSmoothingCrossEntropy(nn.Module):
+    """timm's `LabelSmoothingCrossEntropy` (`main_finetune.py:294`): (1 - smoothing) nll + smoothing mean_c(-log p),
+    mean over the batch — the soft-target kernel with the target row built from the int64 label inside it; the torch
+    formulation elsewhere (see SoftTargetCrossEntropy)."""
+
+    def __init__(self, smoothing=0.1):
+        super().__init__()
+        assert smoothing < 1.0
+        self.smoothing = smoothing
+        self.confidence = 1. - smoothing
+
+    def forward(self, x, target):
+        if _soft_ce_fused_ok(x, target, torch.int64) and target.dim() == 1 and target.shape[0] == x.shape[0]:
+            return _SoftCeFn.apply(x, None, target, float(self.smoothing))
+        logp = nn.functional.log_softmax(x, dim=-1)
+        nll = -logp.gather(dim=-1, index=target.unsqueeze(1)).squeeze(1)
+        return (self.confidence * nll + self.smoothing * -logp.mean(dim=-1)).mean()

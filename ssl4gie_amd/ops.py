@@ -2010,3 +2010,32 @@ def roi_align_bwd(dmaps, scales, rois, roi_batch, dy):
         _lib.check(_lib.load().ssl4gie_roi_align_bwd(hp, hw, sc, B, Cn, ptr(rois), ptr(roi_batch), K, ptr(dy),
                                                      code(dy.dtype), stream()), "roi_align_bwd")
     return dmaps
+
+
+# ------------------------------------------------------------------ Mixup / CutMix (fine-tuning recipe)
+def mixup(x, lam, box, use_cutmix):
+    """timm.data.Mixup's image step IN PLACE on x fp32 [B, C, H, W]: sample i against sample B - 1 - i by the
+    per-sample tables lam fp32 [B], box int32 [B, 4] = (y0, y1, x0, x1), use_cutmix uint8 [B] (data.mixup_tables)"""
+    _dev(x, lam, box, use_cutmix)
+    _f32(x, lam)
+    B, Cn, H, W = x.shape
+    if lam.shape != (B,) or tuple(box.shape) != (B, 4) or box.dtype != torch.int32 or use_cutmix.shape != (B,) \
+            or use_cutmix.dtype != torch.uint8:
+        raise ValueError("mixup needs lam fp32 [B], box int32 [B, 4], use_cutmix uint8 [B]")
+    _lib.check(_lib.load().ssl4gie_mixup(ptr(x), ptr(lam), ptr(box), ptr(use_cutmix), B, Cn, H, W, stream()), "mixup")
+    return x
+
+
+def mixup_target(target, lam, num_classes, smoothing=0.0):
+    """timm's mixup_target: int64 labels [B] + lam fp32 [B] -> fp32 soft targets [B, num_classes]"""
+    _dev(target, lam)
+    _f32(lam)
+    if target.dtype != torch.int64 or target.dim() != 1 or lam.shape != target.shape:
+        raise ValueError("mixup_target needs int64 labels [B] and lam fp32 [B]")
+    B = target.shape[0]
+    off = smoothing / num_classes
+    on = 1.0 - smoothing + off
+    out = torch.empty(B, num_classes, dtype=torch.float32, device=target.device)
+    _lib.check(_lib.load().ssl4gie_mixup_target(ptr(target), ptr(lam), ptr(out), B, num_classes, on, off, stream()),
+               "mixup_target")
+    return out
