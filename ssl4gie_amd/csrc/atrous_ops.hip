@@ -11,43 +11,9 @@
 #include "common.h"
 #include "ssl4gie_hip.h"
 #include "internal.h"
+#include "map_chunk.h"
 
 namespace {
-
-template <typename T, int V> struct Chunk;   // V consecutive channels of T <-> fp32 registers
-template <> struct Chunk<bf16_t, 8> {
-    static DEVI void ld(const bf16_t* p, float (&f)[8]) {
-        const u32x4 r = *(const u32x4*)p;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            f[2 * j] = __uint_as_float(r[j] << 16);
-            f[2 * j + 1] = __uint_as_float(r[j] & 0xffff0000u);
-        }
-    }
-    static DEVI void st(bf16_t* p, const float (&f)[8]) {
-        u32x4 r;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) r[j] = pack_bf2(f[2 * j], f[2 * j + 1]);
-        *(u32x4*)p = r;
-    }
-};
-template <> struct Chunk<float, 4> {
-    static DEVI void ld(const float* p, float (&f)[4]) {
-        const f32x4 r = *(const f32x4*)p;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) f[j] = r[j];
-    }
-    static DEVI void st(float* p, const float (&f)[4]) { *(f32x4*)p = f32x4{f[0], f[1], f[2], f[3]}; }
-};
-template <> struct Chunk<bf16_t, 1> {
-    static DEVI void ld(const bf16_t* p, float (&f)[1]) { f[0] = bf2f(*p); }
-    static DEVI void st(bf16_t* p, const float (&f)[1]) { *p = f2bf(f[0]); }
-};
-template <> struct Chunk<float, 1> {
-    static DEVI void ld(const float* p, float (&f)[1]) { f[0] = *p; }
-    static DEVI void st(float* p, const float (&f)[1]) { *p = f[0]; }
-};
-template <typename T> struct Wide { static constexpr int N = 16 / sizeof(T); };   // channels per 16-byte access
 
 // ------------------------------------------------------------------ dilated 3x3 patch matrix (stride 1, pad = d)
 // cols[(b, y, x), (ky*3 + kx)*C + c] = x[b, y + (ky-1) d, x + (kx-1) d, c] (0 outside); columns [9C, ld) are zeros:
@@ -55,7 +21,7 @@ template <typename T> struct Wide { static constexpr int N = 16 / sizeof(T); }; 
 template <typename T>
 __global__ __launch_bounds__(256) void im2col3x3_dil_kernel(const T* __restrict__ x, T* __restrict__ cols, int H,
                                                             int W, int C, int dil, long long ld, long long total) {
-    constexpr int V = Wide<T>::N;
+    constexpr int V = V16<T>::N;
     const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
     if (idx >= total) return;
     const int cpr = (int)(ld / V);
@@ -85,7 +51,7 @@ template <typename T>
 __global__ __launch_bounds__(256) void dwconv3x3_fwd_kernel(const T* __restrict__ x, const float* __restrict__ w,
                                                             T* __restrict__ y, int H, int W, int C, int dil,
                                                             int flip) {
-    constexpr int V = Wide<T>::N;
+    constexpr int V = V16<T>::N;
     const unsigned cpr = (unsigned)(C / V);
     const unsigned t = blockIdx.x * 256u + threadIdx.x;
     const unsigned ux = t / cpr;
@@ -139,7 +105,7 @@ template <typename T>
 __global__ __launch_bounds__(256) void dwconv3x3_wgrad_kernel(const T* __restrict__ dy, const T* __restrict__ x,
                                                               float* __restrict__ part, int H, int W, int C, int dil,
                                                               long long pixels, int cpb) {
-    constexpr int V = Wide<T>::N;
+    constexpr int V = V16<T>::N;
     const int lanes = 256 / cpb, lane = (int)threadIdx.x / cpb;
     const int chunk = blockIdx.x * cpb + (int)threadIdx.x % cpb;
     if (lane >= lanes || chunk >= C / V) return;
@@ -206,16 +172,7 @@ __global__ __launch_bounds__(256) void dwconv3x3_wgrad_reduce_kernel(const float
 }
 
 // ------------------------------------------------------------------ bilinear x s, align_corners=True
-// src = dst * (n_in - 1) / (n_out - 1) in fp32, as ATen's area_pixel_compute_source_index does; a one-pixel
-// input has scale 0 (constant map).
-DEVI void ac_src(int d, int n_in, int n_out, int& i0, int& i1, float& w1) {
-    const float scale = n_out > 1 ? (float)(n_in - 1) / (float)(n_out - 1) : 0.f;
-    const float s = scale * (float)d;
-    i0 = (int)s;
-    i0 = i0 < n_in - 1 ? i0 : n_in - 1;
-    i1 = i0 + 1 < n_in ? i0 + 1 : n_in - 1;
-    w1 = s - (float)i0;
-}
+// the taps and weights of an output index: ac_src (map_chunk.h)
 template <typename T, int V>
 __global__ __launch_bounds__(256) void bilinear_up_ac_fwd_kernel(const T* __restrict__ x, T* __restrict__ y, int H,
                                                                  int W, int C, int s) {
@@ -318,11 +275,6 @@ __global__ __launch_bounds__(256) void chan_copy_kernel(const T* __restrict__ sr
     Chunk<T, V>::st(dst + (size_t)r * ldd + c, f);
 }
 
-bool dt_ok(int dt) { return dt == SSL4GIE_F32 || dt == SSL4GIE_BF16; }
-int vecn(int dt) { return dt == SSL4GIE_BF16 ? 8 : 4; }
-bool is16(const void* p) { return ((uintptr_t)p & 15) == 0; }
-unsigned blocks_of(long long total) { return (unsigned)((total + 255) / 256); }
-
 struct WgradGrid {
     unsigned gx, gy;
     int cpb;
@@ -352,13 +304,7 @@ extern "C" int ssl4gie_im2col3x3_dil(const void* x, void* cols, int dtype, int B
     const long long total = (long long)B * H * W * (ld / vecn(dtype));
     REQUIRE((total + 255) / 256 <= 0x7fffffffLL);
     hipStream_t st = (hipStream_t)stream;
-    if (dtype == SSL4GIE_BF16)
-        hipLaunchKernelGGL(im2col3x3_dil_kernel<bf16_t>, dim3(blocks_of(total)), dim3(256), 0, st, (const bf16_t*)x,
-                           (bf16_t*)cols, H, W, C, dilation, ld, total);
-    else
-        hipLaunchKernelGGL(im2col3x3_dil_kernel<float>, dim3(blocks_of(total)), dim3(256), 0, st, (const float*)x,
-                           (float*)cols, H, W, C, dilation, ld, total);
-    LAUNCH_CHECK();
+    MAP_LAUNCH(dtype, im2col3x3_dil_kernel, blocks_of(total), 256, (const T*)x, (T*)cols, H, W, C, dilation, ld, total);
     return 0;
 }
 
@@ -371,13 +317,7 @@ extern "C" int ssl4gie_dwconv3x3_fwd(const void* x, const float* w, void* y, int
     REQUIRE((long long)W * (C / vecn(dtype)) < (1LL << 31) && gy <= 65535 && B <= 65535);
     hipStream_t st = (hipStream_t)stream;
     const dim3 grid((per_row + 255) / 256, gy, B), block(256);
-    if (dtype == SSL4GIE_BF16)
-        hipLaunchKernelGGL(dwconv3x3_fwd_kernel<bf16_t>, grid, block, 0, st, (const bf16_t*)x, w, (bf16_t*)y, H, W, C,
-                           dilation, flip);
-    else
-        hipLaunchKernelGGL(dwconv3x3_fwd_kernel<float>, grid, block, 0, st, (const float*)x, w, (float*)y, H, W, C,
-                           dilation, flip);
-    LAUNCH_CHECK();
+    MAP_LAUNCH(dtype, dwconv3x3_fwd_kernel, grid, block, (const T*)x, w, (T*)y, H, W, C, dilation, flip);
     return 0;
 }
 
@@ -395,31 +335,13 @@ extern "C" int ssl4gie_dwconv3x3_wgrad(const void* dy, const void* x, float* dwe
     const WgradGrid g = wgrad_grid(dtype, pixels, C);
     hipStream_t st = (hipStream_t)stream;
     const dim3 grid(g.gx, g.gy), block(256);
-    if (dtype == SSL4GIE_BF16)
-        hipLaunchKernelGGL(dwconv3x3_wgrad_kernel<bf16_t>, grid, block, 0, st, (const bf16_t*)dy, (const bf16_t*)x,
-                           (float*)workspace, H, W, C, dilation, pixels, g.cpb);
-    else
-        hipLaunchKernelGGL(dwconv3x3_wgrad_kernel<float>, grid, block, 0, st, (const float*)dy, (const float*)x,
-                           (float*)workspace, H, W, C, dilation, pixels, g.cpb);
-    LAUNCH_CHECK();
+    MAP_LAUNCH(dtype, dwconv3x3_wgrad_kernel, grid, block, (const T*)dy, (const T*)x, (float*)workspace, H, W, C,
+               dilation, pixels, g.cpb);
     hipLaunchKernelGGL(dwconv3x3_wgrad_reduce_kernel, dim3((unsigned)((9LL * C + 15) / 16)), dim3(256), 0, st,
                        (const float*)workspace, dweight, C, (int)g.slices, accumulate ? 1 : 0);
     LAUNCH_CHECK();
     return 0;
 }
-
-#define UP_LAUNCH(KERNEL, grid, a, b)                                                                          \
-    do {                                                                                                       \
-        if (dtype == SSL4GIE_BF16 && wide)                                                                     \
-            hipLaunchKernelGGL((KERNEL<bf16_t, 8>), grid, dim3(256), 0, st, (const bf16_t*)a, (bf16_t*)b, H, W, C, scale); \
-        else if (dtype == SSL4GIE_BF16)                                                                        \
-            hipLaunchKernelGGL((KERNEL<bf16_t, 1>), grid, dim3(256), 0, st, (const bf16_t*)a, (bf16_t*)b, H, W, C, scale); \
-        else if (wide)                                                                                         \
-            hipLaunchKernelGGL((KERNEL<float, 4>), grid, dim3(256), 0, st, (const float*)a, (float*)b, H, W, C, scale);   \
-        else                                                                                                   \
-            hipLaunchKernelGGL((KERNEL<float, 1>), grid, dim3(256), 0, st, (const float*)a, (float*)b, H, W, C, scale);   \
-        LAUNCH_CHECK();                                                                                        \
-    } while (0)
 
 static bool up_args_ok(const void* a, const void* b, int dtype, int B, int H, int W, int C, int scale) {
     return a && b && a != b && dt_ok(dtype) && B > 0 && H > 0 && W > 0 && C > 0 && scale >= 2 && B <= 65535 &&
@@ -432,7 +354,7 @@ extern "C" int ssl4gie_bilinear_up_ac_fwd(const void* x, void* y, int dtype, int
     const unsigned per_row = (unsigned)(W * scale) * (unsigned)(wide ? C / vecn(dtype) : C);
     hipStream_t st = (hipStream_t)stream;
     const dim3 grid((per_row + 255) / 256, H * scale, B);
-    UP_LAUNCH(bilinear_up_ac_fwd_kernel, grid, x, y);
+    MAP_LAUNCH_V(dtype, wide, bilinear_up_ac_fwd_kernel, grid, 256, (const T*)x, (T*)y, H, W, C, scale);
     return 0;
 }
 extern "C" int ssl4gie_bilinear_up_ac_bwd(const void* dy, void* dx, int dtype, int B, int H, int W, int C, int scale,
@@ -442,7 +364,7 @@ extern "C" int ssl4gie_bilinear_up_ac_bwd(const void* dy, void* dx, int dtype, i
     const unsigned per_row = (unsigned)W * (unsigned)(wide ? C / vecn(dtype) : C);
     hipStream_t st = (hipStream_t)stream;
     const dim3 grid((per_row + 255) / 256, H, B);
-    UP_LAUNCH(bilinear_up_ac_bwd_kernel, grid, dy, dx);
+    MAP_LAUNCH_V(dtype, wide, bilinear_up_ac_bwd_kernel, grid, 256, (const T*)dy, (T*)dx, H, W, C, scale);
     return 0;
 }
 
@@ -455,14 +377,6 @@ extern "C" int ssl4gie_chan_copy(const void* src, long long lds, void* dst, long
     REQUIRE((total + 255) / 256 <= 0x7fffffffLL);
     hipStream_t st = (hipStream_t)stream;
     const dim3 grid(blocks_of(total)), block(256);
-    if (dtype == SSL4GIE_BF16 && wide)
-        hipLaunchKernelGGL((chan_copy_kernel<bf16_t, 8>), grid, block, 0, st, (const bf16_t*)src, lds, (bf16_t*)dst, ldd, C, rep, total);
-    else if (dtype == SSL4GIE_BF16)
-        hipLaunchKernelGGL((chan_copy_kernel<bf16_t, 1>), grid, block, 0, st, (const bf16_t*)src, lds, (bf16_t*)dst, ldd, C, rep, total);
-    else if (wide)
-        hipLaunchKernelGGL((chan_copy_kernel<float, 4>), grid, block, 0, st, (const float*)src, lds, (float*)dst, ldd, C, rep, total);
-    else
-        hipLaunchKernelGGL((chan_copy_kernel<float, 1>), grid, block, 0, st, (const float*)src, lds, (float*)dst, ldd, C, rep, total);
-    LAUNCH_CHECK();
+    MAP_LAUNCH_V(dtype, wide, chan_copy_kernel, grid, block, (const T*)src, lds, (T*)dst, ldd, C, rep, total);
     return 0;
 }

@@ -7,47 +7,7 @@
 #include "common.h"
 #include "internal.h"
 #include "ssl4gie_hip.h"
-
-namespace {
-template <typename T> struct V16;
-template <> struct V16<bf16_t> { static constexpr int N = 8; typedef u32x4 raw; };
-template <> struct V16<float> { static constexpr int N = 4; typedef f32x4 raw; };
-template <typename T> DEVI void un(const typename V16<T>::raw& r, float (&f)[V16<T>::N]);
-template <> DEVI void un<bf16_t>(const u32x4& r, float (&f)[8]) {
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        f[2 * j] = __uint_as_float(r[j] << 16);
-        f[2 * j + 1] = __uint_as_float(r[j] & 0xffff0000u);
-    }
-}
-template <> DEVI void un<float>(const f32x4& r, float (&f)[4]) {
-#pragma unroll
-    for (int j = 0; j < 4; ++j) f[j] = r[j];
-}
-template <typename T> DEVI typename V16<T>::raw pk(const float (&f)[V16<T>::N]);
-template <> DEVI u32x4 pk<bf16_t>(const float (&f)[8]) {
-    u32x4 r;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) r[j] = pack_bf2(f[2 * j], f[2 * j + 1]);
-    return r;
-}
-template <> DEVI f32x4 pk<float>(const float (&f)[4]) { return f32x4{f[0], f[1], f[2], f[3]}; }
-bool okdt(int dt) { return dt == SSL4GIE_F32 || dt == SSL4GIE_BF16; }
-int vn(int dt) { return dt == SSL4GIE_BF16 ? 8 : 4; }
-}  // namespace
-
-#define DET_LAUNCH(dtype, KERNEL, total, ...)                                                       \
-    do {                                                                                            \
-        const dim3 grid_((unsigned)(((total) + 255) / 256)), block_(256);                           \
-        if ((dtype) == SSL4GIE_BF16) {                                                              \
-            typedef bf16_t T;                                                                       \
-            hipLaunchKernelGGL(KERNEL<T>, grid_, block_, 0, st, __VA_ARGS__);                       \
-        } else {                                                                                    \
-            typedef float T;                                                                        \
-            hipLaunchKernelGGL(KERNEL<T>, grid_, block_, 0, st, __VA_ARGS__);                       \
-        }                                                                                           \
-        LAUNCH_CHECK();                                                                             \
-    } while (0)
+#include "map_chunk.h"
 
 // ------------------------------------------------------------------ MaxPool2d(kernel 2, stride 2)
 // x [B, H, W, C] -> y [B, H/2, W/2, C]; backward routes dy to the FIRST maximum of the window in
@@ -351,29 +311,29 @@ __global__ void mapln_bwd_apply_kernel(const T* __restrict__ x, const T* __restr
 // =====================================================================================
 extern "C" int ssl4gie_maxpool2x2_fwd(const void* x, void* y, int dtype, int B, int H, int W, int C,
                                       void* stream) {
-    REQUIRE(x && y && okdt(dtype) && B > 0 && H > 0 && W > 0 && H % 2 == 0 && W % 2 == 0 &&
-            C % vn(dtype) == 0);
+    REQUIRE(x && y && dt_ok(dtype) && B > 0 && H > 0 && W > 0 && H % 2 == 0 && W % 2 == 0 &&
+            C % vecn(dtype) == 0);
     hipStream_t st = (hipStream_t)stream;
-    const long long total = (long long)B * (H / 2) * (W / 2) * (C / vn(dtype));
-    DET_LAUNCH(dtype, maxpool2_fwd_kernel, total, (const T*)x, (T*)y, H, W, C, total);
+    const long long total = (long long)B * (H / 2) * (W / 2) * (C / vecn(dtype));
+    MAP_LAUNCH(dtype, maxpool2_fwd_kernel, blocks_of(total), 256, (const T*)x, (T*)y, H, W, C, total);
     return 0;
 }
 extern "C" int ssl4gie_maxpool2x2_bwd(const void* x, const void* dy, void* dx, int dtype, int B, int H,
                                       int W, int C, void* stream) {
-    REQUIRE(x && dy && dx && okdt(dtype) && B > 0 && H > 0 && W > 0 && H % 2 == 0 && W % 2 == 0 &&
-            C % vn(dtype) == 0);
+    REQUIRE(x && dy && dx && dt_ok(dtype) && B > 0 && H > 0 && W > 0 && H % 2 == 0 && W % 2 == 0 &&
+            C % vecn(dtype) == 0);
     hipStream_t st = (hipStream_t)stream;
-    const long long total = (long long)B * (H / 2) * (W / 2) * (C / vn(dtype));
-    DET_LAUNCH(dtype, maxpool2_bwd_kernel, total, (const T*)x, (const T*)dy, (T*)dx, H, W, C, total);
+    const long long total = (long long)B * (H / 2) * (W / 2) * (C / vecn(dtype));
+    MAP_LAUNCH(dtype, maxpool2_bwd_kernel, blocks_of(total), 256, (const T*)x, (const T*)dy, (T*)dx, H, W, C, total);
     return 0;
 }
 // dy == NULL: out = gelu(x) (exact erf form, nn.GELU);  dy != NULL: out = dy * gelu'(x)
 extern "C" int ssl4gie_gelu_map(const void* x, const void* dy, void* out, int dtype, long long n,
                                 void* stream) {
-    REQUIRE(x && out && okdt(dtype) && n >= 0 && n % vn(dtype) == 0);
+    REQUIRE(x && out && dt_ok(dtype) && n >= 0 && n % vecn(dtype) == 0);
     if (n == 0) return 0;
     hipStream_t st = (hipStream_t)stream;
-    DET_LAUNCH(dtype, gelu_map_kernel, n / vn(dtype), (const T*)x, (const T*)dy, (T*)out, n);
+    MAP_LAUNCH(dtype, gelu_map_kernel, blocks_of(n / vecn(dtype)), 256, (const T*)x, (const T*)dy, (T*)out, n);
     return 0;
 }
 extern "C" size_t ssl4gie_map_layernorm_workspace_bytes(int B) {
@@ -383,21 +343,17 @@ extern "C" size_t ssl4gie_map_layernorm_workspace_bytes(int B) {
 extern "C" int ssl4gie_map_layernorm_fwd(const void* x, const float* w, const float* bias, void* y,
                                          float* mean, float* rstd, float eps, float* workspace,
                                          int dtype, int B, long long M, void* stream) {
-    REQUIRE(x && w && bias && y && mean && rstd && workspace && okdt(dtype) && B > 0 && M > 0 &&
+    REQUIRE(x && w && bias && y && mean && rstd && workspace && dt_ok(dtype) && B > 0 && M > 0 &&
             M % 8 == 0 && B <= 65535);
     hipStream_t st = (hipStream_t)stream;
     dim3 grid(MLN_PARTS, B), block(256);
-    if (dtype == SSL4GIE_BF16)
-        hipLaunchKernelGGL(mapln_stats_kernel<bf16_t>, grid, block, 0, st, (const bf16_t*)x, workspace, M);
-    else
-        hipLaunchKernelGGL(mapln_stats_kernel<float>, grid, block, 0, st, (const float*)x, workspace, M);
-    LAUNCH_CHECK();
-    hipLaunchKernelGGL(mapln_stats_finalize_kernel, dim3(B), dim3(64), 0, st, workspace, mean, rstd, M, vn(dtype),
+    MAP_LAUNCH(dtype, mapln_stats_kernel, grid, block, (const T*)x, workspace, M);
+    hipLaunchKernelGGL(mapln_stats_finalize_kernel, dim3(B), dim3(64), 0, st, workspace, mean, rstd, M, vecn(dtype),
                        eps);
     LAUNCH_CHECK();
     const long long total = (long long)B * M;
-    DET_LAUNCH(dtype, mapln_apply_kernel, total / vn(dtype), (const T*)x, w, bias, mean, rstd, (T*)y, M,
-               total);
+    MAP_LAUNCH(dtype, mapln_apply_kernel, blocks_of(total / vecn(dtype)), 256, (const T*)x, w, bias, mean, rstd, (T*)y,
+               M, total);
     return 0;
 }
 // dx, and dw / db [M] overwritten (accumulate = 0) or accumulated (either may be NULL)
@@ -405,22 +361,16 @@ extern "C" int ssl4gie_map_layernorm_bwd(const void* x, const void* dy, const fl
                                          const float* mean, const float* rstd, void* dx, float* dw,
                                          float* db, int accumulate, float* workspace, int dtype, int B,
                                          long long M, void* stream) {
-    REQUIRE(x && dy && w && mean && rstd && dx && workspace && okdt(dtype) && B > 0 && M > 0 &&
+    REQUIRE(x && dy && w && mean && rstd && dx && workspace && dt_ok(dtype) && B > 0 && M > 0 &&
             M % 8 == 0 && B <= 65535);
     hipStream_t st = (hipStream_t)stream;
     dim3 grid(MLN_PARTS, B), block(256);
     float* mg = workspace + (size_t)B * MLN_PARTS * 2;
     float* mgx = mg + B;
-    if (dtype == SSL4GIE_BF16)
-        hipLaunchKernelGGL(mapln_reduce_kernel<bf16_t>, grid, block, 0, st, (const bf16_t*)x, (const bf16_t*)dy, w,
-                           mean, rstd, workspace, M);
-    else
-        hipLaunchKernelGGL(mapln_reduce_kernel<float>, grid, block, 0, st, (const float*)x, (const float*)dy, w,
-                           mean, rstd, workspace, M);
-    LAUNCH_CHECK();
+    MAP_LAUNCH(dtype, mapln_reduce_kernel, grid, block, (const T*)x, (const T*)dy, w, mean, rstd, workspace, M);
     hipLaunchKernelGGL(mapln_finalize_kernel, dim3(B), dim3(64), 0, st, workspace, mg, mgx, M);
     LAUNCH_CHECK();
-    DET_LAUNCH(dtype, mapln_bwd_apply_kernel, M / vn(dtype), (const T*)x, (const T*)dy, w, mean, rstd, mg,
-               mgx, (T*)dx, dw, db, accumulate, B, M);
+    MAP_LAUNCH(dtype, mapln_bwd_apply_kernel, blocks_of(M / vecn(dtype)), 256, (const T*)x, (const T*)dy, w, mean, rstd,
+               mg, mgx, (T*)dx, dw, db, accumulate, B, M);
     return 0;
 }

@@ -11,17 +11,9 @@
 #include "common.h"
 #include "ssl4gie_hip.h"
 #include "internal.h"
+#include "map_chunk.h"
 #include <stdlib.h>
 
-template <typename T> struct Vec;  // 16-byte vector of T
-template <> struct Vec<bf16_t> {
-    static constexpr int N = 8;
-    typedef u32x4 raw;
-};
-template <> struct Vec<float> {
-    static constexpr int N = 4;
-    typedef f32x4 raw;
-};
 DEVI u32x4 relu_raw(u32x4 v) {  // bf16 pairs: clear negative halves (sign bit set), -0 -> +0
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
@@ -36,28 +28,7 @@ DEVI f32x4 relu_raw(f32x4 v) {
     for (int j = 0; j < 4; ++j) v[j] = v[j] > 0.f ? v[j] : 0.f;
     return v;
 }
-template <typename T> DEVI void unpack(const typename Vec<T>::raw& r, float (&f)[Vec<T>::N]);
-template <> DEVI void unpack<bf16_t>(const u32x4& r, float (&f)[8]) {
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        f[2 * j] = __uint_as_float(r[j] << 16);
-        f[2 * j + 1] = __uint_as_float(r[j] & 0xffff0000u);
-    }
-}
-template <> DEVI void unpack<float>(const f32x4& r, float (&f)[4]) {
-#pragma unroll
-    for (int j = 0; j < 4; ++j) f[j] = r[j];
-}
-template <typename T> DEVI typename Vec<T>::raw pack(const float (&f)[Vec<T>::N]);
-template <> DEVI u32x4 pack<bf16_t>(const float (&f)[8]) {
-    u32x4 r;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) r[j] = pack_bf2(f[2 * j], f[2 * j + 1]);
-    return r;
-}
-template <> DEVI f32x4 pack<float>(const float (&f)[4]) { return f32x4{f[0], f[1], f[2], f[3]}; }
 
-#define DPT_GRID(total) dim3((unsigned)(((total) + 255) / 256)), dim3(256)
 // ------------------------------------------------------------------ 3x3 patch matrix (pad 1)
 // cols[(b, oy, ox), (dy*3 + dx)*C + c] = act(x[b, oy*s + dy - 1, ox*s + dx - 1, c]) (0 outside);
 // columns [9C, ld) are zero-filled (K padding for the MFMA GEMM)
@@ -65,25 +36,25 @@ template <typename T>
 __global__ void im2col3x3_kernel(const T* __restrict__ x, T* __restrict__ cols, int B, int H, int W,
                                  int C, int Ho, int Wo, int stride, int relu, long long ld,
                                  long long total) {
-    constexpr int V = Vec<T>::N;
+    constexpr int V = V16<T>::N;
     const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (idx >= total) return;
     const int cpr = (int)(ld / V);  // chunks per output row
     const long long m = idx / cpr;
     const int ch = (int)(idx % cpr);
     const int col = ch * V;
-    typename Vec<T>::raw v = {};
+    typename V16<T>::raw v = {};
     if (col < 9 * C) {
         const int tap = col / C, c = col % C;
         const int dy = tap / 3, dx = tap % 3;
         const int ox = (int)(m % Wo), oy = (int)((m / Wo) % Ho), b = (int)(m / ((long long)Wo * Ho));
         const int iy = oy * stride + dy - 1, ix = ox * stride + dx - 1;
         if (iy >= 0 && iy < H && ix >= 0 && ix < W) {
-            v = *(const typename Vec<T>::raw*)(x + (((size_t)b * H + iy) * W + ix) * C + c);
+            v = *(const typename V16<T>::raw*)(x + (((size_t)b * H + iy) * W + ix) * C + c);
             if (relu) v = relu_raw(v);
         }
     }
-    *(typename Vec<T>::raw*)(cols + (size_t)m * ld + col) = v;
+    *(typename V16<T>::raw*)(cols + (size_t)m * ld + col) = v;
 }
 
 // gather-form transpose of the above (data gradient of a strided conv):
@@ -92,7 +63,7 @@ template <typename T>
 __global__ void col2im3x3_kernel(const T* __restrict__ dcols, T* __restrict__ dx, int B, int H,
                                  int W, int C, int Ho, int Wo, int stride, long long ld,
                                  long long total) {
-    constexpr int V = Vec<T>::N;
+    constexpr int V = V16<T>::N;
     const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (idx >= total) return;
     const int cpr = C / V;
@@ -114,24 +85,16 @@ __global__ void col2im3x3_kernel(const T* __restrict__ dcols, T* __restrict__ dx
             if (ox >= Wo) continue;
             const size_t m = ((size_t)b * Ho + oy) * Wo + ox;
             float f[V];
-            unpack<T>(*(const typename Vec<T>::raw*)(dcols + m * ld + (dy * 3 + dxx) * C + c), f);
+            un<T>(*(const typename V16<T>::raw*)(dcols + m * ld + (dy * 3 + dxx) * C + c), f);
 #pragma unroll
             for (int j = 0; j < V; ++j) acc[j] += f[j];
         }
     }
-    *(typename Vec<T>::raw*)(dx + (size_t)p * C + c) = pack<T>(acc);
+    *(typename V16<T>::raw*)(dx + (size_t)p * C + c) = pk<T>(acc);
 }
 
 // ------------------------------------------------------------------ bilinear x2, align_corners=True
-// src = dst * (H - 1) / (2H - 1)   (torch.nn.functional.interpolate semantics)
-DEVI void bl_src(int d, int n_in, int n_out, int& i0, int& i1, float& w1) {
-    const float scale = n_out > 1 ? (float)(n_in - 1) / (float)(n_out - 1) : 0.f;
-    const float s = scale * (float)d;
-    i0 = (int)s;
-    i0 = i0 < n_in - 1 ? i0 : n_in - 1;
-    i1 = i0 + 1 < n_in ? i0 + 1 : n_in - 1;
-    w1 = s - (float)i0;
-}
+// src = dst * (H - 1) / (2H - 1)   (torch.nn.functional.interpolate semantics): ac_src of map_chunk.h
 // one output element from its four taps: rows first, then the vertical lerp (ATen's upsample_bilinear2d order), with
 // the multiply-adds written out — under -ffp-contract=fast the compiler is otherwise free to contract the two
 // forward kernels differently, and they must agree bit for bit
@@ -148,7 +111,7 @@ DEVI float bl_lerp(float f00, float f01, float f10, float f11, float wx, float w
 template <typename T>
 __global__ __launch_bounds__(256) void bilinear2x_fwd_kernel(const T* __restrict__ x, T* __restrict__ y, int H,
                                                              int W, int C) {
-    constexpr int V = Vec<T>::N;
+    constexpr int V = V16<T>::N;
     const unsigned cpr = (unsigned)(C / V), Ho = 2 * H, Wo = 2 * W;
     const unsigned t = blockIdx.x * 256u + threadIdx.x;
     const unsigned ox = t / cpr;
@@ -157,17 +120,17 @@ __global__ __launch_bounds__(256) void bilinear2x_fwd_kernel(const T* __restrict
     const int oy = blockIdx.y, b = blockIdx.z;
     int y0, y1, x0, x1;
     float wy, wx;
-    bl_src(oy, H, Ho, y0, y1, wy);
-    bl_src((int)ox, W, Wo, x0, x1, wx);
+    ac_src(oy, H, Ho, y0, y1, wy);
+    ac_src((int)ox, W, Wo, x0, x1, wx);
     const T* base = x + (size_t)b * H * W * C + c;
     float f00[V], f01[V], f10[V], f11[V], o[V];
-    unpack<T>(*(const typename Vec<T>::raw*)(base + ((size_t)y0 * W + x0) * C), f00);
-    unpack<T>(*(const typename Vec<T>::raw*)(base + ((size_t)y0 * W + x1) * C), f01);
-    unpack<T>(*(const typename Vec<T>::raw*)(base + ((size_t)y1 * W + x0) * C), f10);
-    unpack<T>(*(const typename Vec<T>::raw*)(base + ((size_t)y1 * W + x1) * C), f11);
+    un<T>(*(const typename V16<T>::raw*)(base + ((size_t)y0 * W + x0) * C), f00);
+    un<T>(*(const typename V16<T>::raw*)(base + ((size_t)y0 * W + x1) * C), f01);
+    un<T>(*(const typename V16<T>::raw*)(base + ((size_t)y1 * W + x0) * C), f10);
+    un<T>(*(const typename V16<T>::raw*)(base + ((size_t)y1 * W + x1) * C), f11);
 #pragma unroll
     for (int j = 0; j < V; ++j) o[j] = bl_lerp(f00[j], f01[j], f10[j], f11[j], wx, wy);
-    *(typename Vec<T>::raw*)(y + (((size_t)b * Ho + oy) * Wo + ox) * C + c) = pack<T>(o);
+    *(typename V16<T>::raw*)(y + (((size_t)b * Ho + oy) * Wo + ox) * C + c) = pk<T>(o);
 }
 // backward in gather form: an input pixel collects from every output pixel whose two taps include it, in the
 // order (output row, output column) of the candidates.  The column coefficients are computed once per thread (not
@@ -175,7 +138,7 @@ __global__ __launch_bounds__(256) void bilinear2x_fwd_kernel(const T* __restrict
 template <typename T>
 __global__ __launch_bounds__(256) void bilinear2x_bwd_kernel(const T* __restrict__ dy, T* __restrict__ dx, int H,
                                                              int W, int C) {
-    constexpr int V = Vec<T>::N;
+    constexpr int V = V16<T>::N;
     const unsigned cpr = (unsigned)(C / V);
     const int Ho = 2 * H, Wo = 2 * W;
     const unsigned t = blockIdx.x * 256u + threadIdx.x;
@@ -195,7 +158,7 @@ __global__ __launch_bounds__(256) void bilinear2x_bwd_kernel(const T* __restrict
         const int ox = ox_lo + k;
         int x0, x1;
         float wx;
-        bl_src(ox <= ox_hi ? ox : ox_hi, W, Wo, x0, x1, wx);
+        ac_src(ox <= ox_hi ? ox : ox_hi, W, Wo, x0, x1, wx);
         float cx = 0.f;
         if (x0 == ix) cx += 1.f - wx;
         if (x1 == ix) cx += wx;
@@ -204,7 +167,7 @@ __global__ __launch_bounds__(256) void bilinear2x_bwd_kernel(const T* __restrict
     for (int oy = oy_lo; oy <= oy_hi; ++oy) {
         int y0, y1;
         float wy;
-        bl_src(oy, H, Ho, y0, y1, wy);
+        ac_src(oy, H, Ho, y0, y1, wy);
         float cy = 0.f;
         if (y0 == iy) cy += 1.f - wy;
         if (y1 == iy) cy += wy;
@@ -215,13 +178,13 @@ __global__ __launch_bounds__(256) void bilinear2x_bwd_kernel(const T* __restrict
             const float cx = cxs[k];
             if (cx == 0.f) continue;
             float f[V];
-            unpack<T>(*(const typename Vec<T>::raw*)(row + (size_t)k * C), f);
+            un<T>(*(const typename V16<T>::raw*)(row + (size_t)k * C), f);
             const float w = cy * cx;
 #pragma unroll
             for (int j = 0; j < V; ++j) acc[j] += w * f[j];
         }
     }
-    *(typename Vec<T>::raw*)(dx + (((size_t)b * H + iy) * W + ix) * C + c) = pack<T>(acc);
+    *(typename V16<T>::raw*)(dx + (((size_t)b * H + iy) * W + ix) * C + c) = pk<T>(acc);
 }
 
 // ---- 2 x 2 outputs per thread (round 6).  The forward above issues four 16-byte tap loads per 16-byte store and runs
@@ -235,8 +198,8 @@ __global__ __launch_bounds__(256) void bilinear2x_bwd_kernel(const T* __restrict
 template <typename T>
 __global__ __launch_bounds__(256) void bilinear2x_fwd22_kernel(const T* __restrict__ x, T* __restrict__ y, int H,
                                                                int W, int C) {
-    constexpr int V = Vec<T>::N;
-    typedef typename Vec<T>::raw raw;
+    constexpr int V = V16<T>::N;
+    typedef typename V16<T>::raw raw;
     const unsigned cpr = (unsigned)(C / V), Wo = 2 * W;
     const int Ho = 2 * H;
     const unsigned t = blockIdx.x * 256u + threadIdx.x;
@@ -246,10 +209,10 @@ __global__ __launch_bounds__(256) void bilinear2x_fwd22_kernel(const T* __restri
     const int k = blockIdx.y, b = blockIdx.z;
     int y0a, y1a, y0b, y1b, x0a, x1a, x0b, x1b;
     float wya, wyb, wxa, wxb;
-    bl_src(2 * k, H, Ho, y0a, y1a, wya);
-    bl_src(2 * k + 1, H, Ho, y0b, y1b, wyb);
-    bl_src(2 * (int)j, W, (int)Wo, x0a, x1a, wxa);
-    bl_src(2 * (int)j + 1, W, (int)Wo, x0b, x1b, wxb);
+    ac_src(2 * k, H, Ho, y0a, y1a, wya);
+    ac_src(2 * k + 1, H, Ho, y0b, y1b, wyb);
+    ac_src(2 * (int)j, W, (int)Wo, x0a, x1a, wxa);
+    ac_src(2 * (int)j + 1, W, (int)Wo, x0b, x1b, wxb);
     const T* base = x + (size_t)b * H * W * C + c;
     const int rows[3] = {y0a, y1a, y1b}, cols[3] = {x0a, x1a, x1b};
     raw tp[3][3];
@@ -263,10 +226,10 @@ __global__ __launch_bounds__(256) void bilinear2x_fwd22_kernel(const T* __restri
     auto lerp_store = [&](const raw& r00, const raw& r01, const raw& r10, const raw& r11, float wx, float wy, int oy,
                           unsigned ox) {
         float f00[V], f01[V], f10[V], f11[V], o[V];
-        unpack<T>(r00, f00); unpack<T>(r01, f01); unpack<T>(r10, f10); unpack<T>(r11, f11);
+        un<T>(r00, f00); un<T>(r01, f01); un<T>(r10, f10); un<T>(r11, f11);
 #pragma unroll
         for (int i = 0; i < V; ++i) o[i] = bl_lerp(f00[i], f01[i], f10[i], f11[i], wx, wy);
-        *(raw*)(y + (((size_t)b * Ho + oy) * Wo + ox) * C + c) = pack<T>(o);
+        *(raw*)(y + (((size_t)b * Ho + oy) * Wo + ox) * C + c) = pk<T>(o);
     };
     auto sel = [](bool p, const raw& a, const raw& bb) -> raw {
         raw r;
@@ -307,7 +270,7 @@ template <typename T>
 __global__ void pixel_shuffle_kernel(const T* __restrict__ g, const float* __restrict__ bias,
                                      T* __restrict__ y, int B, int H, int W, int k, int C,
                                      long long total) {
-    constexpr int V = Vec<T>::N;
+    constexpr int V = V16<T>::N;
     const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (idx >= total) return;
     const int cpr = C / V, Ho = k * H, Wo = k * W;
@@ -317,17 +280,17 @@ __global__ void pixel_shuffle_kernel(const T* __restrict__ g, const float* __res
     const int yy = oy / k, i = oy % k, xx = ox / k, j = ox % k;
     const size_t m = ((size_t)b * H + yy) * W + xx;
     float f[V];
-    unpack<T>(*(const typename Vec<T>::raw*)(g + m * ((size_t)k * k * C) + (size_t)(i * k + j) * C + c), f);
+    un<T>(*(const typename V16<T>::raw*)(g + m * ((size_t)k * k * C) + (size_t)(i * k + j) * C + c), f);
     if (bias) {
 #pragma unroll
         for (int q = 0; q < V; ++q) f[q] += bias[c + q];
     }
-    *(typename Vec<T>::raw*)(y + (size_t)p * C + c) = pack<T>(f);
+    *(typename V16<T>::raw*)(y + (size_t)p * C + c) = pk<T>(f);
 }
 template <typename T>
 __global__ void pixel_unshuffle_kernel(const T* __restrict__ dy, T* __restrict__ dg, int B, int H,
                                        int W, int k, int C, long long total) {
-    constexpr int V = Vec<T>::N;
+    constexpr int V = V16<T>::N;
     const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (idx >= total) return;
     const int cpr = C / V, Ho = k * H, Wo = k * W;
@@ -336,8 +299,8 @@ __global__ void pixel_unshuffle_kernel(const T* __restrict__ dy, T* __restrict__
     const int ox = (int)(p % Wo), oy = (int)((p / Wo) % Ho), b = (int)(p / ((long long)Wo * Ho));
     const int yy = oy / k, i = oy % k, xx = ox / k, j = ox % k;
     const size_t m = ((size_t)b * H + yy) * W + xx;
-    *(typename Vec<T>::raw*)(dg + m * ((size_t)k * k * C) + (size_t)(i * k + j) * C + c) =
-        *(const typename Vec<T>::raw*)(dy + (size_t)p * C + c);
+    *(typename V16<T>::raw*)(dg + m * ((size_t)k * k * C) + (size_t)(i * k + j) * C + c) =
+        *(const typename V16<T>::raw*)(dy + (size_t)p * C + c);
 }
 
 // ------------------------------------------------------------------ tokens <-> map
@@ -371,12 +334,12 @@ __global__ void map_to_tokens_kernel(const T* __restrict__ dx, float* __restrict
 template <typename T>
 __global__ void eltwise_kernel(int op, const T* __restrict__ a, const T* __restrict__ b,
                                const T* __restrict__ c, T* __restrict__ out, long long total) {
-    constexpr int V = Vec<T>::N;
+    constexpr int V = V16<T>::N;
     const long long idx = ((long long)blockIdx.x * blockDim.x + threadIdx.x) * V;
     if (idx >= total) return;
     float fa[V], fb[V], fo[V];
-    unpack<T>(*(const typename Vec<T>::raw*)(a + idx), fa);
-    unpack<T>(*(const typename Vec<T>::raw*)(b + idx), fb);
+    un<T>(*(const typename V16<T>::raw*)(a + idx), fa);
+    un<T>(*(const typename V16<T>::raw*)(b + idx), fb);
     if (op == 0) {
 #pragma unroll
         for (int j = 0; j < V; ++j) fo[j] = fa[j] + fb[j];
@@ -385,12 +348,12 @@ __global__ void eltwise_kernel(int op, const T* __restrict__ a, const T* __restr
         for (int j = 0; j < V; ++j) fo[j] = fa[j] > 0.f ? fb[j] : 0.f;
         if (c) {
             float fc[V];
-            unpack<T>(*(const typename Vec<T>::raw*)(c + idx), fc);
+            un<T>(*(const typename V16<T>::raw*)(c + idx), fc);
 #pragma unroll
             for (int j = 0; j < V; ++j) fo[j] += fc[j];
         }
     }
-    *(typename Vec<T>::raw*)(out + idx) = pack<T>(fo);
+    *(typename V16<T>::raw*)(out + idx) = pk<T>(fo);
 }
 
 // ------------------------------------------------------------------ depth head
@@ -399,13 +362,13 @@ template <typename T>
 __global__ void depth_head_fwd_kernel(const T* __restrict__ x, const float* __restrict__ w,
                                       const float* __restrict__ bias, float* __restrict__ y,
                                       long long M, int C) {
-    constexpr int V = Vec<T>::N;
+    constexpr int V = V16<T>::N;
     const long long m = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (m >= M) return;
     float s = bias[0];
     for (int c = 0; c < C; c += V) {
         float f[V];
-        unpack<T>(*(const typename Vec<T>::raw*)(x + (size_t)m * C + c), f);
+        un<T>(*(const typename V16<T>::raw*)(x + (size_t)m * C + c), f);
 #pragma unroll
         for (int j = 0; j < V; ++j) s += (f[j] > 0.f ? f[j] : 0.f) * w[c + j];
     }
@@ -417,7 +380,7 @@ __global__ __launch_bounds__(256) void depth_head_bwd_kernel(
     const T* __restrict__ x, const float* __restrict__ w, const float* __restrict__ y,
     const float* __restrict__ dy, T* __restrict__ dx, float* __restrict__ partial, long long M,
     int C) {
-    constexpr int V = Vec<T>::N;
+    constexpr int V = V16<T>::N;
     __shared__ float red[4][65];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     float aw[64];  // C <= 64
@@ -433,14 +396,14 @@ __global__ __launch_bounds__(256) void depth_head_bwd_kernel(
         for (int c0 = 0; c0 < 64; c0 += V) {
             if (c0 < C) {
                 float f[V], o[V];
-                unpack<T>(*(const typename Vec<T>::raw*)(x + (size_t)m * C + c0), f);
+                un<T>(*(const typename V16<T>::raw*)(x + (size_t)m * C + c0), f);
 #pragma unroll
                 for (int j = 0; j < V; ++j) {
                     const bool on = f[j] > 0.f;
                     o[j] = on ? ds * w[c0 + j] : 0.f;
                     aw[c0 + j] += on ? ds * f[j] : 0.f;
                 }
-                *(typename Vec<T>::raw*)(dx + (size_t)m * C + c0) = pack<T>(o);
+                *(typename V16<T>::raw*)(dx + (size_t)m * C + c0) = pk<T>(o);
             }
         }
     }
@@ -466,20 +429,6 @@ __global__ __launch_bounds__(256) void depth_head_bwd_kernel(
 // =====================================================================================
 // C ABI
 // =====================================================================================
-static bool dt_ok(int dt) { return dt == SSL4GIE_F32 || dt == SSL4GIE_BF16; }
-static int vecn(int dt) { return dt == SSL4GIE_BF16 ? 8 : 4; }
-#define DPT_LAUNCH(dtype, KERNEL, total, ...)                                                      \
-    do {                                                                                           \
-        if ((dtype) == SSL4GIE_BF16) {                                                             \
-            typedef bf16_t T;                                                                      \
-            hipLaunchKernelGGL(KERNEL<T>, DPT_GRID(total), 0, st, __VA_ARGS__);                    \
-        } else {                                                                                   \
-            typedef float T;                                                                       \
-            hipLaunchKernelGGL(KERNEL<T>, DPT_GRID(total), 0, st, __VA_ARGS__);                    \
-        }                                                                                          \
-        LAUNCH_CHECK();                                                                            \
-    } while (0)
-
 extern "C" int ssl4gie_im2col3x3(const void* x, void* cols, int dtype, int B, int H, int W, int C,
                                  int stride, int relu, long long ld, void* stream) {
     REQUIRE(x && cols && dt_ok(dtype) && B > 0 && H > 0 && W > 0 && C > 0);
@@ -488,8 +437,8 @@ extern "C" int ssl4gie_im2col3x3(const void* x, void* cols, int dtype, int B, in
     hipStream_t st = (hipStream_t)stream;
     const int Ho = (H - 1) / stride + 1, Wo = (W - 1) / stride + 1;
     const long long total = (long long)B * Ho * Wo * (ld / vecn(dtype));
-    DPT_LAUNCH(dtype, im2col3x3_kernel, total, (const T*)x, (T*)cols, B, H, W, C, Ho, Wo, stride,
-               relu, ld, total);
+    MAP_LAUNCH(dtype, im2col3x3_kernel, blocks_of(total), 256, (const T*)x, (T*)cols, B, H, W, C, Ho, Wo, stride, relu,
+               ld, total);
     return 0;
 }
 extern "C" int ssl4gie_col2im3x3(const void* dcols, void* dx, int dtype, int B, int H, int W, int C,
@@ -499,8 +448,8 @@ extern "C" int ssl4gie_col2im3x3(const void* dcols, void* dx, int dtype, int B, 
     hipStream_t st = (hipStream_t)stream;
     const int Ho = (H - 1) / stride + 1, Wo = (W - 1) / stride + 1;
     const long long total = (long long)B * H * W * (C / vecn(dtype));
-    DPT_LAUNCH(dtype, col2im3x3_kernel, total, (const T*)dcols, (T*)dx, B, H, W, C, Ho, Wo, stride,
-               ld, total);
+    MAP_LAUNCH(dtype, col2im3x3_kernel, blocks_of(total), 256, (const T*)dcols, (T*)dx, B, H, W, C, Ho, Wo, stride, ld,
+               total);
     return 0;
 }
 extern "C" int ssl4gie_bilinear2x_fwd(const void* x, void* y, int dtype, int B, int H, int W, int C,
@@ -511,20 +460,12 @@ extern "C" int ssl4gie_bilinear2x_fwd(const void* x, void* y, int dtype, int B, 
     if (bilinear22()) {
         const unsigned per = (unsigned)W * (unsigned)(C / vecn(dtype));
         const dim3 grid((per + 255) / 256, H, B), block(256);
-        if (dtype == SSL4GIE_BF16)
-            hipLaunchKernelGGL(bilinear2x_fwd22_kernel<bf16_t>, grid, block, 0, st, (const bf16_t*)x, (bf16_t*)y, H, W, C);
-        else
-            hipLaunchKernelGGL(bilinear2x_fwd22_kernel<float>, grid, block, 0, st, (const float*)x, (float*)y, H, W, C);
-        LAUNCH_CHECK();
+        MAP_LAUNCH(dtype, bilinear2x_fwd22_kernel, grid, block, (const T*)x, (T*)y, H, W, C);
         return 0;
     }
     const unsigned per_row = (unsigned)(2 * W) * (unsigned)(C / vecn(dtype));
     const dim3 grid((per_row + 255) / 256, 2 * H, B), block(256);
-    if (dtype == SSL4GIE_BF16)
-        hipLaunchKernelGGL(bilinear2x_fwd_kernel<bf16_t>, grid, block, 0, st, (const bf16_t*)x, (bf16_t*)y, H, W, C);
-    else
-        hipLaunchKernelGGL(bilinear2x_fwd_kernel<float>, grid, block, 0, st, (const float*)x, (float*)y, H, W, C);
-    LAUNCH_CHECK();
+    MAP_LAUNCH(dtype, bilinear2x_fwd_kernel, grid, block, (const T*)x, (T*)y, H, W, C);
     return 0;
 }
 extern "C" int ssl4gie_bilinear2x_bwd(const void* dy, void* dx, int dtype, int B, int H, int W,
@@ -534,11 +475,7 @@ extern "C" int ssl4gie_bilinear2x_bwd(const void* dy, void* dx, int dtype, int B
     REQUIRE(H <= 65535 && B <= 65535);
     const unsigned per_row = (unsigned)W * (unsigned)(C / vecn(dtype));
     const dim3 grid((per_row + 255) / 256, H, B), block(256);
-    if (dtype == SSL4GIE_BF16)
-        hipLaunchKernelGGL(bilinear2x_bwd_kernel<bf16_t>, grid, block, 0, st, (const bf16_t*)dy, (bf16_t*)dx, H, W, C);
-    else
-        hipLaunchKernelGGL(bilinear2x_bwd_kernel<float>, grid, block, 0, st, (const float*)dy, (float*)dx, H, W, C);
-    LAUNCH_CHECK();
+    MAP_LAUNCH(dtype, bilinear2x_bwd_kernel, grid, block, (const T*)dy, (T*)dx, H, W, C);
     return 0;
 }
 extern "C" int ssl4gie_pixel_shuffle(const void* g, const float* bias, void* y, int dtype, int B,
@@ -547,7 +484,7 @@ extern "C" int ssl4gie_pixel_shuffle(const void* g, const float* bias, void* y, 
             C % vecn(dtype) == 0);
     hipStream_t st = (hipStream_t)stream;
     const long long total = (long long)B * k * H * k * W * (C / vecn(dtype));
-    DPT_LAUNCH(dtype, pixel_shuffle_kernel, total, (const T*)g, bias, (T*)y, B, H, W, k, C, total);
+    MAP_LAUNCH(dtype, pixel_shuffle_kernel, blocks_of(total), 256, (const T*)g, bias, (T*)y, B, H, W, k, C, total);
     return 0;
 }
 extern "C" int ssl4gie_pixel_unshuffle(const void* dy, void* dg, int dtype, int B, int H, int W,
@@ -556,7 +493,7 @@ extern "C" int ssl4gie_pixel_unshuffle(const void* dy, void* dg, int dtype, int 
             C % vecn(dtype) == 0);
     hipStream_t st = (hipStream_t)stream;
     const long long total = (long long)B * k * H * k * W * (C / vecn(dtype));
-    DPT_LAUNCH(dtype, pixel_unshuffle_kernel, total, (const T*)dy, (T*)dg, B, H, W, k, C, total);
+    MAP_LAUNCH(dtype, pixel_unshuffle_kernel, blocks_of(total), 256, (const T*)dy, (T*)dg, B, H, W, k, C, total);
     return 0;
 }
 extern "C" int ssl4gie_tokens_to_map(const float* z, void* x, int dtype, int B, int L, int D,
@@ -564,7 +501,7 @@ extern "C" int ssl4gie_tokens_to_map(const float* z, void* x, int dtype, int B, 
     REQUIRE(z && x && dt_ok(dtype) && B > 0 && L > 0 && D > 0 && D % 4 == 0);
     hipStream_t st = (hipStream_t)stream;
     const long long total = (long long)B * L * D;
-    DPT_LAUNCH(dtype, tokens_to_map_kernel, total / 4, z, (T*)x, L, D, total);
+    MAP_LAUNCH(dtype, tokens_to_map_kernel, blocks_of(total / 4), 256, z, (T*)x, L, D, total);
     return 0;
 }
 extern "C" int ssl4gie_map_to_tokens(const void* dx, float* dz, int dtype, int B, int L, int D,
@@ -572,7 +509,7 @@ extern "C" int ssl4gie_map_to_tokens(const void* dx, float* dz, int dtype, int B
     REQUIRE(dx && dz && dt_ok(dtype) && B > 0 && L > 0 && D > 0 && D % 4 == 0);
     hipStream_t st = (hipStream_t)stream;
     const long long total = (long long)B * (L + 1) * D;
-    DPT_LAUNCH(dtype, map_to_tokens_kernel, total / 4, (const T*)dx, dz, L, D, total);
+    MAP_LAUNCH(dtype, map_to_tokens_kernel, blocks_of(total / 4), 256, (const T*)dx, dz, L, D, total);
     return 0;
 }
 extern "C" int ssl4gie_eltwise(int op, const void* a, const void* b, const void* c, void* out,
@@ -580,7 +517,7 @@ extern "C" int ssl4gie_eltwise(int op, const void* a, const void* b, const void*
     REQUIRE(a && b && out && dt_ok(dtype) && n >= 0 && n % vecn(dtype) == 0 && (op == 0 || op == 1));
     if (n == 0) return 0;
     hipStream_t st = (hipStream_t)stream;
-    DPT_LAUNCH(dtype, eltwise_kernel, n / vecn(dtype), op, (const T*)a, (const T*)b, (const T*)c,
+    MAP_LAUNCH(dtype, eltwise_kernel, blocks_of(n / vecn(dtype)), 256, op, (const T*)a, (const T*)b, (const T*)c,
                (T*)out, n);
     return 0;
 }
@@ -588,7 +525,7 @@ extern "C" int ssl4gie_depth_head_fwd(const void* x, const float* w, const float
                                       int dtype, long long M, int C, void* stream) {
     REQUIRE(x && w && bias && y && dt_ok(dtype) && M > 0 && C > 0 && C <= 64 && C % vecn(dtype) == 0);
     hipStream_t st = (hipStream_t)stream;
-    DPT_LAUNCH(dtype, depth_head_fwd_kernel, M, (const T*)x, w, bias, y, M, C);
+    MAP_LAUNCH(dtype, depth_head_fwd_kernel, blocks_of(M), 256, (const T*)x, w, bias, y, M, C);
     return 0;
 }
 static int head_blocks(long long M) {
@@ -607,13 +544,7 @@ extern "C" int ssl4gie_depth_head_bwd(const void* x, const float* w, const float
             C <= 64 && C % vecn(dtype) == 0);
     hipStream_t st = (hipStream_t)stream;
     const int nb = head_blocks(M);
-    if (dtype == SSL4GIE_BF16)
-        hipLaunchKernelGGL(depth_head_bwd_kernel<bf16_t>, dim3(nb), dim3(256), 0, st,
-                           (const bf16_t*)x, w, y, dy, (bf16_t*)dx, workspace, M, C);
-    else
-        hipLaunchKernelGGL(depth_head_bwd_kernel<float>, dim3(nb), dim3(256), 0, st,
-                           (const float*)x, w, y, dy, (float*)dx, workspace, M, C);
-    LAUNCH_CHECK();
+    MAP_LAUNCH(dtype, depth_head_bwd_kernel, nb, 256, (const T*)x, w, y, dy, (T*)dx, workspace, M, C);
     int rc = ssl4gie_internal_reduce_partials(workspace, dw, nb, C, (size_t)(C + 1), accumulate, st);
     if (rc) return rc;
     return ssl4gie_internal_reduce_partials(workspace + C, db, nb, 1, (size_t)(C + 1), accumulate, st);

@@ -16,45 +16,7 @@
 #include "prof.h"
 #include "ssl4gie_hip.h"
 #include "internal.h"
-
-namespace {
-template <typename T> struct V16;
-template <> struct V16<bf16_t> { static constexpr int N = 8; typedef u32x4 raw; };
-template <> struct V16<float> { static constexpr int N = 4; typedef f32x4 raw; };
-template <typename T> DEVI void un(const typename V16<T>::raw& r, float (&f)[V16<T>::N]);
-template <> DEVI void un<bf16_t>(const u32x4& r, float (&f)[8]) {
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        f[2 * j] = __uint_as_float(r[j] << 16);
-        f[2 * j + 1] = __uint_as_float(r[j] & 0xffff0000u);
-    }
-}
-template <> DEVI void un<float>(const f32x4& r, float (&f)[4]) {
-#pragma unroll
-    for (int j = 0; j < 4; ++j) f[j] = r[j];
-}
-template <typename T> DEVI typename V16<T>::raw pk(const float (&f)[V16<T>::N]);
-template <> DEVI u32x4 pk<bf16_t>(const float (&f)[8]) {
-    u32x4 r;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) r[j] = pack_bf2(f[2 * j], f[2 * j + 1]);
-    return r;
-}
-template <> DEVI f32x4 pk<float>(const float (&f)[4]) { return f32x4{f[0], f[1], f[2], f[3]}; }
-}  // namespace
-
-#define RN_GRID(total) dim3((unsigned)(((total) + 255) / 256)), dim3(256)
-#define RN_LAUNCH(dtype, KERNEL, total, ...)                                                       \
-    do {                                                                                           \
-        if ((dtype) == SSL4GIE_BF16) {                                                             \
-            typedef bf16_t T;                                                                      \
-            hipLaunchKernelGGL(KERNEL<T>, RN_GRID(total), 0, st, __VA_ARGS__);                     \
-        } else {                                                                                   \
-            typedef float T;                                                                       \
-            hipLaunchKernelGGL(KERNEL<T>, RN_GRID(total), 0, st, __VA_ARGS__);                     \
-        }                                                                                          \
-        LAUNCH_CHECK();                                                                            \
-    } while (0)
+#include "map_chunk.h"
 
 // ------------------------------------------------------------------ stem patch matrix
 // cols[(b, oy, ox), (dy*7 + dx)*3 + c] = img[b, c, 2 oy + dy - 3, 2 ox + dx - 3]; [147, ld) zero
@@ -695,12 +657,10 @@ __global__ void avgpool_bwd_kernel(const float* __restrict__ dy, T* __restrict__
 // =====================================================================================
 // C ABI
 // =====================================================================================
-static bool rdt(int dt) { return dt == SSL4GIE_F32 || dt == SSL4GIE_BF16; }
-static int rvn(int dt) { return dt == SSL4GIE_BF16 ? 8 : 4; }
 // grid of the two BatchNorm reductions: strips of 64 lanes x V channels over C (y: row partitions).
 // ~64K elements per workgroup, at most 1024 partitions (the partials are parts x 2C floats)
 static int bn_strips(int C, int dtype) {
-    const int v = rvn(dtype);
+    const int v = vecn(dtype);
     return (C / v + 63) / 64;
 }
 static int bn_parts(long long rows, int C) {
@@ -710,24 +670,24 @@ static int bn_parts(long long rows, int C) {
 
 extern "C" int ssl4gie_stem_im2col7x7(const float* img, void* cols, int dtype, int B, int H, int W,
                                       long long ld, void* stream) {
-    REQUIRE(img && cols && rdt(dtype) && B > 0 && H > 0 && W > 0 && ld >= 147 && ld % 8 == 0);
+    REQUIRE(img && cols && dt_ok(dtype) && B > 0 && H > 0 && W > 0 && ld >= 147 && ld % 8 == 0);
     hipStream_t st = (hipStream_t)stream;
     const int Ho = (H - 1) / 2 + 1, Wo = (W - 1) / 2 + 1;
     const long long total = (long long)B * Ho * Wo * (ld / 8);
-    RN_LAUNCH(dtype, stem_im2col_kernel, total, img, (T*)cols, B, H, W, Ho, Wo, ld, total);
+    MAP_LAUNCH(dtype, stem_im2col_kernel, blocks_of(total), 256, img, (T*)cols, B, H, W, Ho, Wo, ld, total);
     return 0;
 }
 extern "C" int ssl4gie_subsample2(const void* x, void* y, int dtype, int B, int H, int W, int C,
                                   int backward, void* stream) {
-    REQUIRE(x && y && rdt(dtype) && B > 0 && H > 0 && W > 0 && C > 0 && C % rvn(dtype) == 0);
+    REQUIRE(x && y && dt_ok(dtype) && B > 0 && H > 0 && W > 0 && C > 0 && C % vecn(dtype) == 0);
     hipStream_t st = (hipStream_t)stream;
     const int Ho = (H - 1) / 2 + 1, Wo = (W - 1) / 2 + 1;
     if (!backward) {
-        const long long total = (long long)B * Ho * Wo * (C / rvn(dtype));
-        RN_LAUNCH(dtype, subsample2_kernel, total, (const T*)x, (T*)y, H, W, C, Ho, Wo, total);
+        const long long total = (long long)B * Ho * Wo * (C / vecn(dtype));
+        MAP_LAUNCH(dtype, subsample2_kernel, blocks_of(total), 256, (const T*)x, (T*)y, H, W, C, Ho, Wo, total);
     } else {  // x = dy [B, Ho, Wo, C], y = dx [B, H, W, C]
-        const long long total = (long long)B * H * W * (C / rvn(dtype));
-        RN_LAUNCH(dtype, subsample2_bwd_kernel, total, (const T*)x, (T*)y, H, W, C, Ho, Wo, total);
+        const long long total = (long long)B * H * W * (C / vecn(dtype));
+        MAP_LAUNCH(dtype, subsample2_bwd_kernel, blocks_of(total), 256, (const T*)x, (T*)y, H, W, C, Ho, Wo, total);
     }
     return 0;
 }
@@ -782,17 +742,17 @@ static int bn_fold(const float* partial, int parts, float* scratch, int C, hipSt
 }
 extern "C" int ssl4gie_maxpool3x3s2_fwd(const void* x, void* y, unsigned char* arg, int dtype, int B,
                                         int H, int W, int C, void* stream) {
-    REQUIRE(x && y && arg && rdt(dtype) && B > 0 && H > 0 && W > 0 && C > 0);
+    REQUIRE(x && y && arg && dt_ok(dtype) && B > 0 && H > 0 && W > 0 && C > 0);
     hipStream_t st = (hipStream_t)stream;
     const int Ho = (H - 1) / 2 + 1, Wo = (W - 1) / 2 + 1;
-    if (C % rvn(dtype) == 0) {
-        const long long total = (long long)B * Ho * Wo * (C / rvn(dtype));
-        RN_LAUNCH(dtype, maxpool_fwd_vec_kernel, total, (const T*)x, (T*)y, arg, H, W, C, Ho, Wo, total,
-                  (const float*)nullptr, 0);
+    if (C % vecn(dtype) == 0) {
+        const long long total = (long long)B * Ho * Wo * (C / vecn(dtype));
+        MAP_LAUNCH(dtype, maxpool_fwd_vec_kernel, blocks_of(total), 256, (const T*)x, (T*)y, arg, H, W, C, Ho, Wo,
+                   total, (const float*)nullptr, 0);
         return 0;
     }
     const long long total = (long long)B * Ho * Wo * C;
-    RN_LAUNCH(dtype, maxpool_fwd_kernel, total, (const T*)x, (T*)y, arg, H, W, C, Ho, Wo, total);
+    MAP_LAUNCH(dtype, maxpool_fwd_kernel, blocks_of(total), 256, (const T*)x, (T*)y, arg, H, W, C, Ho, Wo, total);
     return 0;
 }
 // MaxPool2d(3, 2, 1) over act(x coef[0][c] + coef[1][c]) (coef [2][C] from the coefficients-only ssl4gie_bn_fwd): BatchNorm
@@ -800,45 +760,43 @@ extern "C" int ssl4gie_maxpool3x3s2_fwd(const void* x, void* y, unsigned char* a
 extern "C" int ssl4gie_bn_maxpool3x3s2_fwd(const void* x, const float* coef, int relu, void* y,
                                            unsigned char* arg, int dtype, int B, int H, int W, int C,
                                            void* stream) {
-    REQUIRE(x && coef && y && arg && rdt(dtype) && B > 0 && H > 0 && W > 0 && C > 0 && C % rvn(dtype) == 0);
+    REQUIRE(x && coef && y && arg && dt_ok(dtype) && B > 0 && H > 0 && W > 0 && C > 0 && C % vecn(dtype) == 0);
     hipStream_t st = (hipStream_t)stream;
     const int Ho = (H - 1) / 2 + 1, Wo = (W - 1) / 2 + 1;
-    const long long total = (long long)B * Ho * Wo * (C / rvn(dtype));
-    RN_LAUNCH(dtype, maxpool_fwd_vec_kernel, total, (const T*)x, (T*)y, arg, H, W, C, Ho, Wo, total, coef, relu);
+    const long long total = (long long)B * Ho * Wo * (C / vecn(dtype));
+    MAP_LAUNCH(dtype, maxpool_fwd_vec_kernel, blocks_of(total), 256, (const T*)x, (T*)y, arg, H, W, C, Ho, Wo, total,
+               coef, relu);
     return 0;
 }
 extern "C" int ssl4gie_maxpool3x3s2_bwd(const void* dy, const unsigned char* arg, void* dx, int dtype,
                                         int B, int H, int W, int C, void* stream) {
-    REQUIRE(dy && dx && arg && rdt(dtype) && B > 0 && H > 0 && W > 0 && C > 0);
+    REQUIRE(dy && dx && arg && dt_ok(dtype) && B > 0 && H > 0 && W > 0 && C > 0);
     hipStream_t st = (hipStream_t)stream;
     const int Ho = (H - 1) / 2 + 1, Wo = (W - 1) / 2 + 1;
-    if (C % rvn(dtype) == 0) {
-        const long long total = (long long)B * H * W * (C / rvn(dtype));
-        RN_LAUNCH(dtype, maxpool_bwd_vec_kernel, total, (const T*)dy, arg, (T*)dx, H, W, C, Ho, Wo, total);
+    if (C % vecn(dtype) == 0) {
+        const long long total = (long long)B * H * W * (C / vecn(dtype));
+        MAP_LAUNCH(dtype, maxpool_bwd_vec_kernel, blocks_of(total), 256, (const T*)dy, arg, (T*)dx, H, W, C, Ho, Wo,
+                   total);
         return 0;
     }
     const long long total = (long long)B * H * W * C;
-    RN_LAUNCH(dtype, maxpool_bwd_kernel, total, (const T*)dy, arg, (T*)dx, H, W, C, Ho, Wo, total);
+    MAP_LAUNCH(dtype, maxpool_bwd_kernel, blocks_of(total), 256, (const T*)dy, arg, (T*)dx, H, W, C, Ho, Wo, total);
     return 0;
 }
 extern "C" int ssl4gie_avgpool_fwd(const void* x, float* y, int dtype, int B, int HW, int C,
                                    void* stream) {
-    REQUIRE(x && y && rdt(dtype) && B > 0 && HW > 0 && C > 0);
+    REQUIRE(x && y && dt_ok(dtype) && B > 0 && HW > 0 && C > 0);
     hipStream_t st = (hipStream_t)stream;
     dim3 grid((C + 255) / 256, B), block(256);
-    if (dtype == SSL4GIE_BF16)
-        hipLaunchKernelGGL(avgpool_fwd_kernel<bf16_t>, grid, block, 0, st, (const bf16_t*)x, y, HW, C);
-    else
-        hipLaunchKernelGGL(avgpool_fwd_kernel<float>, grid, block, 0, st, (const float*)x, y, HW, C);
-    LAUNCH_CHECK();
+    MAP_LAUNCH(dtype, avgpool_fwd_kernel, grid, block, (const T*)x, y, HW, C);
     return 0;
 }
 extern "C" int ssl4gie_avgpool_bwd(const float* dy, void* dx, int dtype, int B, int HW, int C,
                                    void* stream) {
-    REQUIRE(dy && dx && rdt(dtype) && B > 0 && HW > 0 && C > 0);
+    REQUIRE(dy && dx && dt_ok(dtype) && B > 0 && HW > 0 && C > 0);
     hipStream_t st = (hipStream_t)stream;
     const long long total = (long long)B * HW * C;
-    RN_LAUNCH(dtype, avgpool_bwd_kernel, total, dy, (T*)dx, HW, C, total);
+    MAP_LAUNCH(dtype, avgpool_bwd_kernel, blocks_of(total), 256, dy, (T*)dx, HW, C, total);
     return 0;
 }
 
@@ -892,7 +850,7 @@ extern "C" size_t ssl4gie_bn_workspace_bytes(long long rows, int C) {
 }
 
 // ---- argument validation: a combination no kernel serves is SSL4GIE_EARG
-static bool bn_map_ok(int dtype, long long rows, int C) { return rdt(dtype) && rows > 0 && C > 0 && C % 8 == 0; }
+static bool bn_map_ok(int dtype, long long rows, int C) { return dt_ok(dtype) && rows > 0 && C > 0 && C % 8 == 0; }
 static bool bn_fwd_ok(int source, const void* x, const float* partial, int parts, const float* gamma,
                       const float* beta, const void* res, const void* y, const unsigned char* relu_bits,
                       const float* coef, const float* mean, const float* rstd, const float* running_mean,
@@ -909,7 +867,7 @@ static bool bn_fwd_ok(int source, const void* x, const float* partial, int parts
     if (!mean || !rstd || !workspace) return false;
     if (!y)  // coefficients only, into the caller's [2][C]: from partials (a statistics pass over x always writes y)
         return source == SSL4GIE_BN_FROM_PARTIALS && coef && !x && !res && !relu_bits;
-    if (!x || coef || !rdt(dtype)) return false;
+    if (!x || coef || !dt_ok(dtype)) return false;
     return !relu_bits || (source == SSL4GIE_BN_FROM_PARTIALS && relu && dtype == SSL4GIE_BF16);
 }
 // what the three backward functions share; `dres` is NULL in the apply half
@@ -930,20 +888,14 @@ static bool bn_bwd_ok(const void* dy, int mask_kind, const void* mask, const voi
 static int bn_launch_stats(const void* x, const BnWs& ws, int parts, int dtype, long long rows, int C,
                            hipStream_t st) {
     dim3 grid(bn_strips(C, dtype), parts), block(256);
-    if (dtype == SSL4GIE_BF16)
-        hipLaunchKernelGGL(bn_stats_kernel<bf16_t>, grid, block, 0, st, (const bf16_t*)x, ws.partial, ws.pivot,
-                           rows, C);
-    else
-        hipLaunchKernelGGL(bn_stats_kernel<float>, grid, block, 0, st, (const float*)x, ws.partial, ws.pivot,
-                           rows, C);
-    LAUNCH_CHECK();
+    MAP_LAUNCH(dtype, bn_stats_kernel, grid, block, (const T*)x, ws.partial, ws.pivot, rows, C);
     return 0;
 }
 static int bn_launch_apply(const void* x, const float* coef, const void* res, void* y, int relu,
                            unsigned char* relu_bits, int dtype, long long rows, int C, hipStream_t st) {
     const long long total = rows * C;
-    RN_LAUNCH(dtype, bn_apply_kernel, total / rvn(dtype), (const T*)x, coef, (const T*)res, (T*)y, relu, C, total,
-              relu_bits);
+    MAP_LAUNCH(dtype, bn_apply_kernel, blocks_of(total / vecn(dtype)), 256, (const T*)x, coef, (const T*)res, (T*)y,
+               relu, C, total, relu_bits);
     return 0;
 }
 template <typename T>
@@ -978,8 +930,8 @@ static int bn_launch_bwd_apply(const void* g, const void* y, const void* x, cons
                                const float* mcoef, const float* mu, int dtype, long long rows, int C,
                                hipStream_t st) {
     const long long total = rows * C;
-    RN_LAUNCH(dtype, bn_bwd_apply_kernel, total / rvn(dtype), (const T*)g, (const T*)y, (const T*)x, coef, (T*)dx,
-              relu, C, total, mcoef, mu);
+    MAP_LAUNCH(dtype, bn_bwd_apply_kernel, blocks_of(total / vecn(dtype)), 256, (const T*)g, (const T*)y, (const T*)x,
+               coef, (T*)dx, relu, C, total, mcoef, mu);
     return 0;
 }
 
@@ -1041,7 +993,7 @@ extern "C" int ssl4gie_bn_fwd(int source, const void* x, const float* partial, i
 extern "C" int ssl4gie_bn_stats(const void* x, const float* partial, int parts, float* mean, float* var,
                                 float* workspace, int dtype, long long rows, int C, void* stream) {
     REQUIRE(mean && var && workspace && rows > 0 && C > 0 && C % 8 == 0);
-    REQUIRE(partial ? (parts > 0 && !x) : (x && rdt(dtype)));
+    REQUIRE(partial ? (parts > 0 && !x) : (x && dt_ok(dtype)));
     hipStream_t st = (hipStream_t)stream;
     const int parts_x = partial ? BN_FOLD : bn_parts(rows, C);
     const BnWs ws(workspace, parts_x, C);
