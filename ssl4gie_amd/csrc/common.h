@@ -84,7 +84,7 @@ DEVI void st4(bf16_t* p, f32x4 v) {
 }
 
 // ---- wave reductions (64 lanes) -------------------------------------------------------
-DEVI float wave_sum(float v) {
+template <typename T> DEVI T wave_sum(T v) {  // float, double, int; the sums over a workgroup are in reduce.h
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
     return v;
@@ -160,7 +160,9 @@ DEVI int xcd_remap(int bid, int nwg) {
     return base + (bid >> 3);
 }
 
-#define HIP_RET(expr)                                  \
+__host__ __device__ inline size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }  // workspace granule
+
+#define HIP_RET(expr)                                 \
     do {                                               \
         hipError_t e__ = (expr);                       \
         if (e__ != hipSuccess) return (int)e__;        \

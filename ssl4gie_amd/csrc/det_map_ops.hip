@@ -328,23 +328,22 @@ __global__ __launch_bounds__(SORT_TILE) void dm_sort_scatter_kernel(const SortIn
     }
 }
 
-__host__ __device__ inline size_t al256(size_t b) { return (b + 255) & ~(size_t)255; }
 inline int sort_blocks(long long n) { return (int)((n + SORT_CHUNK - 1) / SORT_CHUNK); }
 // workspace: keys A | keys B | idx A | idx B | table int [256][blocks] | kept count
 struct SortWs { u64 *ka, *kb; unsigned *ia, *ib; int *table, *n_kept; };
 inline SortWs sort_ws(void* ws, long long n) {
     SortWs w;
     char* p = (char*)ws;
-    w.ka = (u64*)p; p += al256((size_t)n * 8);
-    w.kb = (u64*)p; p += al256((size_t)n * 8);
-    w.ia = (unsigned*)p; p += al256((size_t)n * 4);
-    w.ib = (unsigned*)p; p += al256((size_t)n * 4);
-    w.table = (int*)p; p += al256((size_t)256 * sort_blocks(n) * 4);
+    w.ka = (u64*)p; p += align256((size_t)n * 8);
+    w.kb = (u64*)p; p += align256((size_t)n * 8);
+    w.ia = (unsigned*)p; p += align256((size_t)n * 4);
+    w.ib = (unsigned*)p; p += align256((size_t)n * 4);
+    w.table = (int*)p; p += align256((size_t)256 * sort_blocks(n) * 4);
     w.n_kept = (int*)p;
     return w;
 }
 inline size_t sort_ws_bytes(long long n) {
-    return 2 * al256((size_t)n * 8) + 2 * al256((size_t)n * 4) + al256((size_t)256 * sort_blocks(n) * 4) + 256;
+    return 2 * align256((size_t)n * 8) + 2 * align256((size_t)n * 4) + align256((size_t)256 * sort_blocks(n) * 4) + 256;
 }
 
 // ------------------------------------------------------------------ accumulate

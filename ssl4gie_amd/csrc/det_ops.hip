@@ -4,7 +4,7 @@
 // convolutions and ConvTranspose2d(2, 2) of the pyramid are the GEMM paths of gemm*.hip.
 //
 // All of it is HBM-bound streaming: 16-byte accesses, two-stage deterministic reductions.
-#include "common.h"
+#include "reduce.h"
 #include "internal.h"
 #include "ssl4gie_hip.h"
 #include "map_chunk.h"
@@ -110,12 +110,6 @@ __host__ __device__ inline long long mapln_part_vectors(long long nvec, int p) {
     const long long rem = nvec % (MLN_PARTS * 256) - (long long)p * 256;
     return nvec / (MLN_PARTS * 256) * 256 + (rem < 0 ? 0 : rem > 256 ? 256 : rem);
 }
-DEVI float mapln_block_sum(float v, float* red /*[4]*/) {  // 256 threads; red is not reused by the caller
-    v = wave_sum(v);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return (red[0] + red[1]) + (red[2] + red[3]);
-}
 template <typename T>
 __global__ __launch_bounds__(256) void mapln_stats_kernel(const T* __restrict__ x, float* __restrict__ partial,
                                                           long long M) {
@@ -133,7 +127,7 @@ __global__ __launch_bounds__(256) void mapln_stats_kernel(const T* __restrict__ 
 #pragma unroll
         for (int j = 0; j < V; ++j) s += f[j];
     }
-    const float m0 = n > 0.f ? mapln_block_sum(s, red[0]) / n : 0.f;  // n is the same for the whole block
+    const float m0 = n > 0.f ? block_sum_all<SumOrder::Pairwise>(s, red[0]) / n : 0.f;  // n is the same for the whole block
     s = 0.f;
     float q = 0.f;
     for (long long i = first; i < M; i += step) {
@@ -146,8 +140,8 @@ __global__ __launch_bounds__(256) void mapln_stats_kernel(const T* __restrict__ 
             q += d * d;
         }
     }
-    s = mapln_block_sum(s, red[1]);
-    q = mapln_block_sum(q, red[2]);
+    s = block_sum_all<SumOrder::Pairwise>(s, red[1]);
+    q = block_sum_all<SumOrder::Pairwise>(q, red[2]);
     if (threadIdx.x == 0) {
         float* o = partial + ((size_t)b * MLN_PARTS + p) * 2;
         const float d = n > 0.f ? s / n : 0.f;
@@ -218,13 +212,12 @@ __global__ __launch_bounds__(256) void mapln_reduce_kernel(
     }
     s = wave_sum(s);
     q = wave_sum(q);
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    if (lane == 0) { red[0][wave] = s; red[1][wave] = q; }
+    block_put(s, red[0]); block_put(q, red[1]);
     __syncthreads();
     if (threadIdx.x == 0) {
         float* o = partial + ((size_t)b * MLN_PARTS + p) * 2;
-        o[0] = red[0][0] + red[0][1] + red[0][2] + red[0][3];
-        o[1] = red[1][0] + red[1][1] + red[1][2] + red[1][3];
+        o[0] = block_get<SumOrder::Sequential>(red[0]);
+        o[1] = block_get<SumOrder::Sequential>(red[1]);
     }
 }
 // one wave per image: fold the partials into the two means of dx

@@ -117,7 +117,6 @@ SideStream* side_stream() {
     return ss;
 }
 
-size_t align_up(size_t v) { return (v + 255) & ~(size_t)255; }
 size_t esize(int dt) { return dt == SSL4GIE_BF16 ? 2 : 4; }
 
 struct BwdLayout {
@@ -148,14 +147,14 @@ BwdLayout bwd_layout(const ssl4gie_block_dims* d) {
     const size_t T = (size_t)d->B * d->N, D = d->D, F = d->F, es = esize(d->dtype);
     BwdLayout L;
     size_t o = 0;
-    L.du = o; o += align_up(T * F * es);
-    L.dh = o; o += align_up(T * D * es);
-    L.dxmid = o; o += align_up(T * D * 4);
-    L.dxmid_lp = o; o += (d->dtype == SSL4GIE_F32) ? 0 : align_up(T * D * es);
-    L.dattn = o; o += align_up(T * D * es);
-    L.dqkv = o; o += align_up(T * 3 * D * es);
-    L.ln_ws = o; o += align_up(ssl4gie_layernorm_bwd_workspace_bytes((int)T, (int)D));
-    L.ln_ws1 = o; o += align_up(ssl4gie_layernorm_bwd_workspace_bytes((int)T, (int)D));  // LN1's own partials: LN2's are still being summed on the side stream
+    L.du = o; o += align256(T * F * es);
+    L.dh = o; o += align256(T * D * es);
+    L.dxmid = o; o += align256(T * D * 4);
+    L.dxmid_lp = o; o += (d->dtype == SSL4GIE_F32) ? 0 : align256(T * D * es);
+    L.dattn = o; o += align256(T * D * es);
+    L.dqkv = o; o += align256(T * 3 * D * es);
+    L.ln_ws = o; o += align256(ssl4gie_layernorm_bwd_workspace_bytes((int)T, (int)D));
+    L.ln_ws1 = o; o += align256(ssl4gie_layernorm_bwd_workspace_bytes((int)T, (int)D));  // LN1's own partials: LN2's are still being summed on the side stream
     size_t g = 0;
     // the weight gradients run as two pairs: (fc2, fc1) and (proj, qkv)
     const int dims[4][2] = {{(int)D, (int)F}, {(int)F, (int)D}, {(int)D, (int)D}, {(int)(3 * D), (int)D}};
@@ -169,8 +168,8 @@ BwdLayout bwd_layout(const ssl4gie_block_dims* d) {
         if (b > g) g = b;
     }
     L.gemm_ws_bytes = g;
-    L.gemm_ws = o; o += align_up(g);  // one weight-gradient stream: the two pairs run in order and share the slabs
-    L.attn_ws = o; o += align_up(ssl4gie_attn_workspace_bytes(d->dtype, d->B, d->N, d->H, d->D / d->H));
+    L.gemm_ws = o; o += align256(g);  // one weight-gradient stream: the two pairs run in order and share the slabs
+    L.attn_ws = o; o += align256(ssl4gie_attn_workspace_bytes(d->dtype, d->B, d->N, d->H, d->D / d->H));
     L.total = o;
     return L;
 }
@@ -190,9 +189,9 @@ DpLayout dp_layout(const ssl4gie_block_dims* d, const BwdLayout& L) {
     const size_t T = (size_t)d->B * d->N, D = d->D, es = esize(d->dtype);
     DpLayout P;
     size_t o = L.total;
-    P.t = o; o += align_up(T * D * 4);
-    P.dys_out = o; o += align_up(T * D * es);
-    P.dys_mid = o; o += align_up(T * D * es);
+    P.t = o; o += align256(T * D * 4);
+    P.dys_out = o; o += align256(T * D * es);
+    P.dys_mid = o; o += align256(T * D * es);
     P.total = o;
     return P;
 }

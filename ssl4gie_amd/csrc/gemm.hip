@@ -877,7 +877,6 @@ int ssl4gie_internal_conv_k(const ssl4gie_conv3x3_geom* g, ConvK* k) {
     return rc;
 }
 
-static size_t al256(size_t v) { return (v + 255) & ~(size_t)255; }
 // workspace layout of the TN paths: [slabs (splits > 1)] [column-sum scratch (colsum_a)]
 struct TnPlan {
     bool big;
@@ -889,7 +888,7 @@ static TnPlan tn_plan(const ssl4gie_gemm_desc* d) {
     p.big = ssl4gie_internal_tn256_ok(d);
     p.splits = p.big ? ssl4gie_internal_tn256_splits(d, 1, TN_SPLIT_LONE) : tn_splits(d);
     p.slab_bytes = p.splits > 1 ? (size_t)p.splits * d->M * d->N * sizeof(float) : 0;
-    p.cs_off = al256(p.slab_bytes);
+    p.cs_off = align256(p.slab_bytes);
     p.cs_bytes = 0;
     if (d->colsum_a)
         p.cs_bytes = p.big ? (p.splits > 1 ? (size_t)p.splits * d->M * sizeof(float) : 0)
@@ -1041,11 +1040,11 @@ static TnManyPlan tn_many_plan(const ssl4gie_gemm_desc* ds, int n, int splits) {
     size_t o = 0;
     for (int i = 0; i < n; ++i) {
         p.slab_off[i] = o;
-        if (splits > 1) o += al256((size_t)splits * ds[i].M * ds[i].N * sizeof(float));
+        if (splits > 1) o += align256((size_t)splits * ds[i].M * ds[i].N * sizeof(float));
     }
     for (int i = 0; i < n; ++i) {
         p.cs_off[i] = o;
-        if (splits > 1 && ds[i].colsum_a) o += al256((size_t)splits * ds[i].M * sizeof(float));
+        if (splits > 1 && ds[i].colsum_a) o += align256((size_t)splits * ds[i].M * sizeof(float));
     }
     p.total = o;
     return p;

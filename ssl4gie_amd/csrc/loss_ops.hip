@@ -14,7 +14,7 @@
 //    Two-stage deterministic reductions (block partials, then one block per image / per batch).
 //  * SoftDiceLoss (Binary_segmentation/Metrics/losses.py:5-24): per image sums of sigmoid(l) t,
 //    sigmoid(l)^2, t^2; loss = 1 - mean score; gradient in a second pass.
-#include "common.h"
+#include "reduce.h"
 #include "internal.h"
 #include "ssl4gie_hip.h"
 
@@ -23,20 +23,6 @@ namespace {
 constexpr int NB = 32;      // blocks per image
 constexpr int NSUM_A = 8;   // a00 a01 a11 b0 b1 M1 M2 M3
 constexpr int NSUM_B = 7;   // mse reg0 reg1 reg2 reg3 G0 G1
-
-template <int K>
-DEVI void block_reduce(float (&v)[K], float* sh /* [4][K] */) {
-#pragma unroll
-    for (int k = 0; k < K; ++k) v[k] = wave_sum(v[k]);
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    if (lane == 0)
-#pragma unroll
-        for (int k = 0; k < K; ++k) sh[wave * K + k] = v[k];
-    __syncthreads();
-    if (threadIdx.x == 0)
-#pragma unroll
-        for (int k = 0; k < K; ++k) v[k] = sh[k] + sh[K + k] + sh[2 * K + k] + sh[3 * K + k];
-}
 
 // layout of the fp32 workspace (floats): partA [B][NB][8] | img [B][12] | tot [8] | partB [B][NB][7] | g [B*H*W]
 struct SsiWs {
@@ -71,7 +57,7 @@ __global__ __launch_bounds__(256) void ssi_sums_kernel(const float* __restrict__
         }
     }
     __shared__ float sh[4 * NSUM_A];
-    block_reduce<NSUM_A>(v, sh);
+    block_sum<SumOrder::Sequential>(v, sh);
     if (threadIdx.x == 0) {
         float* o = ssi_ws(ws, B, HW).partA + ((size_t)b * NB + blockIdx.x) * NSUM_A;
 #pragma unroll
@@ -152,7 +138,7 @@ __global__ __launch_bounds__(256) void ssi_grad_kernel(const float* __restrict__
         v[6] += g * p[i];
     }
     __shared__ float sh[4 * NSUM_B];
-    block_reduce<NSUM_B>(v, sh);
+    block_sum<SumOrder::Sequential>(v, sh);
     if (threadIdx.x == 0) {
         float* o = w.partB + ((size_t)b * NB + blockIdx.x) * NSUM_B;
 #pragma unroll
@@ -219,7 +205,7 @@ __global__ __launch_bounds__(256) void dice_sums_kernel(const float* __restrict_
         v[0] += m1 * m2; v[1] += m1 * m1; v[2] += m2 * m2;
     }
     __shared__ float sh[4 * 3];
-    block_reduce<3>(v, sh);
+    block_sum<SumOrder::Sequential>(v, sh);
     if (threadIdx.x == 0)
         for (int k = 0; k < 3; ++k) ws[((size_t)b * NB + blockIdx.x) * 3 + k] = v[k];
 }
@@ -465,7 +451,7 @@ __global__ __launch_bounds__(256) void nce_finalize_kernel(float* __restrict__ w
     dot = wave_sum(dot);
     if ((t & 63) == 0) shd[t >> 6] = dot;
     __syncthreads();
-    dot = (shd[0] + shd[1]) + (shd[2] + shd[3]);
+    dot = block_get<SumOrder::Pairwise>(shd);
     const float nrm = w.qnorm[i];
 #pragma unroll
     for (int u = 0; u < 4; ++u) {
@@ -502,8 +488,8 @@ __global__ __launch_bounds__(256) void ce_rows_kernel(const float* __restrict__ 
     if (lane == 0) { sh[wave * 2] = v[0]; sh[wave * 2 + 1] = v[1]; }
     __syncthreads();
     if (threadIdx.x == 0) {
-        ws[blockIdx.x * 2] = (sh[0] + sh[2]) + (sh[4] + sh[6]);
-        ws[blockIdx.x * 2 + 1] = (sh[1] + sh[3]) + (sh[5] + sh[7]);
+        ws[blockIdx.x * 2] = block_get<SumOrder::Pairwise, 2>(sh, 0);
+        ws[blockIdx.x * 2 + 1] = block_get<SumOrder::Pairwise, 2>(sh, 1);
     }
 }
 __global__ __launch_bounds__(256) void ce_apply_kernel(const float* __restrict__ logits,
@@ -516,11 +502,7 @@ __global__ __launch_bounds__(256) void ce_apply_kernel(const float* __restrict__
     double a = 0.0, b = 0.0;
     for (int p = t; p < nblk; p += 256) { a += (double)ws[p * 2]; b += (double)ws[p * 2 + 1]; }
     sh[0][t] = a; sh[1][t] = b;
-    __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) {
-        if (t < o) { sh[0][t] += sh[0][t + o]; sh[1][t] += sh[1][t + o]; }
-        __syncthreads();
-    }
+    block_tree_sum(sh, t);
     if (blockIdx.x == 0 && t == 0) *loss = (float)(sh[0][0] / sh[1][0]);  // sum w = 0: NaN, as torch
     if (!dlogits) return;
     const float wsum = (float)sh[1][0];
@@ -586,7 +568,7 @@ __global__ __launch_bounds__(256) void soft_ce_rows_kernel(const float* __restri
     __shared__ float sh[4];
     if (lane == 0) sh[wave] = total;
     __syncthreads();
-    if (threadIdx.x == 0) ws[blockIdx.x] = (sh[0] + sh[1]) + (sh[2] + sh[3]);
+    if (threadIdx.x == 0) ws[blockIdx.x] = block_get<SumOrder::Pairwise>(sh);
 }
 __global__ __launch_bounds__(256) void soft_ce_finalize_kernel(const float* __restrict__ ws, float* __restrict__ loss,
                                                                int B, int nblk) {
@@ -627,7 +609,7 @@ __global__ __launch_bounds__(256) void bt_loss_partial_kernel(const float* __res
         }
     }
     __shared__ float sh[4 * 2];
-    block_reduce<2>(v, sh);
+    block_sum<SumOrder::Sequential>(v, sh);
     if (threadIdx.x == 0) { ws[blockIdx.x * 2] = v[0]; ws[blockIdx.x * 2 + 1] = v[1]; }
 }
 __global__ __launch_bounds__(256) void bt_loss_final_kernel(const float* __restrict__ ws, float* __restrict__ loss,
@@ -637,11 +619,7 @@ __global__ __launch_bounds__(256) void bt_loss_final_kernel(const float* __restr
     double a = 0.0, b = 0.0;
     for (int p = t; p < nblk; p += 256) { a += (double)ws[p * 2]; b += (double)ws[p * 2 + 1]; }
     sh[0][t] = a; sh[1][t] = b;
-    __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) {
-        if (t < o) { sh[0][t] += sh[0][t + o]; sh[1][t] += sh[1][t + o]; }
-        __syncthreads();
-    }
+    block_tree_sum(sh, t);
     if (t == 0) *loss = (float)(sh[0][0] + (double)lambd * sh[1][0]);
 }
 // one read of c, both GEMM operands of the backward: w = round(dc s), wt = w^T through an LDS tile so that both

@@ -19,7 +19,7 @@
 // the separate torch ops give.
 #include <type_traits>
 
-#include "common.h"
+#include "reduce.h"
 #include "ssl4gie_hip.h"
 
 #pragma clang fp contract(off)
@@ -41,30 +41,6 @@ constexpr int SEL_BINS = 2048; // radix of the select: 11 + 11 + 10 bits
 constexpr uint32_t SEL_SKIP = 0xFFFFFFFFu;  // bit pattern of a masked-out entry (a negative NaN: never a valid |d / t|)
 
 typedef unsigned long long u64;
-
-DEVI int wave_sum_i(int v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-DEVI double wave_sum_d(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-template <int K>
-DEVI void block_sum_d(double (&v)[K], double* sh /* [4][K] */) {
-#pragma unroll
-    for (int k = 0; k < K; ++k) v[k] = wave_sum_d(v[k]);
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    if (lane == 0)
-#pragma unroll
-        for (int k = 0; k < K; ++k) sh[wave * K + k] = v[k];
-    __syncthreads();
-    if (threadIdx.x == 0)
-#pragma unroll
-        for (int k = 0; k < K; ++k) v[k] = (sh[k] + sh[K + k]) + (sh[2 * K + k] + sh[3 * K + k]);
-}
 
 // F.interpolate(mode = "bilinear", align_corners = False): source taps and weight of output index `dst`
 struct Tap { int i0, i1; float l1; };
@@ -124,17 +100,14 @@ __global__ __launch_bounds__(256) void seg_counts_kernel(const LT* __restrict__ 
             c[0] += m1; c[1] += m2; c[2] += m1 && m2;
         }
     }
-    __shared__ int sh[4][3];
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    __shared__ int sh[4 * 3];
 #pragma unroll
-    for (int k = 0; k < 3; ++k) c[k] = wave_sum_i(c[k]);
-    if (lane == 0)
-#pragma unroll
-        for (int k = 0; k < 3; ++k) sh[wave][k] = c[k];
+    for (int k = 0; k < 3; ++k) c[k] = wave_sum(c[k]);
+    block_put(c, sh);
     __syncthreads();
-    if (threadIdx.x < 3) {
+    if (threadIdx.x < 3) {  // thread k closes count k
         const int k = threadIdx.x;
-        const int s = sh[0][k] + sh[1][k] + sh[2][k] + sh[3][k];
+        const int s = block_get<SumOrder::Sequential, 3>(sh, k);
         if (s) atomicAdd(counts + (size_t)b * 3 + k, (u64)s);  // integer: the order of arrival does not matter
     }
 }
@@ -234,14 +207,7 @@ __global__ __launch_bounds__(256) void confusion_scores_kernel(const long long* 
     }
     shi[0][threadIdx.x] = diag;
     shi[1][threadIdx.x] = total;
-    __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) {
-        if ((int)threadIdx.x < o) {
-            shi[0][threadIdx.x] += shi[0][threadIdx.x + o];
-            shi[1][threadIdx.x] += shi[1][threadIdx.x + o];
-        }
-        __syncthreads();
-    }
+    block_tree_sum(shi, threadIdx.x);
     if (threadIdx.x == 0) {
         scores[0] = run[0] / (float)C;
         scores[1] = run[1] / (float)C;
@@ -387,7 +353,7 @@ __global__ __launch_bounds__(256) void depth_sums_kernel(const float* __restrict
         }
     }
     __shared__ double sh[4 * 5];
-    block_sum_d<5>(v, sh);
+    block_sum<SumOrder::Pairwise>(v, sh);
     if (threadIdx.x == 0)
 #pragma unroll
         for (int k = 0; k < 5; ++k) partA[((size_t)b * DEPTH_NB + blockIdx.x) * 5 + k] = v[k];
@@ -451,9 +417,8 @@ __global__ __launch_bounds__(256) void depth_err_kernel(const float* __restrict_
     }
     __shared__ double sh[4 * 2];
     __shared__ int shc[4];
-    block_sum_d<2>(v, sh);
-    cnt = wave_sum_i(cnt);
-    if ((threadIdx.x & 63) == 0) shc[threadIdx.x >> 6] = cnt;
+    block_sum<SumOrder::Pairwise>(v, sh);
+    block_put(wave_sum(cnt), shc);
     __syncthreads();
     if (threadIdx.x == 0) {
         const size_t o = (size_t)b * MAXBLK + blockIdx.x;

@@ -19,7 +19,7 @@
 //   ctl[2] found_inf: 1 when any ACTIVE element of g is inf or NaN (decided per element), else 0
 //   ctl[3] reserved (0)
 // which the scale kernel and the _ctl AdamW read on the device: nothing comes back to the host.
-#include "common.h"
+#include "reduce.h"
 #include "ssl4gie_hip.h"
 
 namespace {
@@ -152,13 +152,13 @@ __global__ __launch_bounds__(256) void grad_norm_partial_kernel(
         }
     }
     double a = ((double)acc[0] + (double)acc[1]) + ((double)acc[2] + (double)acc[3]);
-#pragma unroll
+#pragma unroll  // written out here and below: see reduce.h
     for (int o = 32; o > 0; o >>= 1) a += __shfl_xor(a, o, 64);
     const int wbad = __any((int)bad);
     if ((threadIdx.x & 63) == 0) { red[threadIdx.x >> 6] = a; redb[threadIdx.x >> 6] = wbad; }
     __syncthreads();
     if (threadIdx.x == 0) {
-        part_sum[blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
+        part_sum[blockIdx.x] = block_get<SumOrder::Pairwise>(red);
         part_bad[blockIdx.x] = (redb[0] | redb[1] | redb[2] | redb[3]) != 0;
     }
 }
@@ -180,7 +180,7 @@ __global__ __launch_bounds__(256) void grad_norm_final_kernel(
     if ((threadIdx.x & 63) == 0) { red[threadIdx.x >> 6] = a; redb[threadIdx.x >> 6] = bad; }
     __syncthreads();
     if (threadIdx.x == 0) {
-        const float norm = (float)sqrt((red[0] + red[1]) + (red[2] + red[3]));
+        const float norm = (float)sqrt(block_get<SumOrder::Pairwise>(red));
         float coef = 1.f;
         if (max_norm > 0.f) {  // torch.nn.utils.clip_grad_norm_: clamp(max_norm / (norm + 1e-6), max=1)
             coef = max_norm / (norm + 1e-6f);
@@ -230,11 +230,11 @@ __global__ __launch_bounds__(256) void lars_norm_partial_kernel(
     }
     a = wave_sum(a);
     b = wave_sum(b);
-    if ((threadIdx.x & 63) == 0) { red[0][threadIdx.x >> 6] = a; red[1][threadIdx.x >> 6] = b; }
+    block_put(a, red[0]); block_put(b, red[1]);
     __syncthreads();
     if (threadIdx.x == 0) {
-        partial[((size_t)s * LARS_PARTS + part) * 2] = red[0][0] + red[0][1] + red[0][2] + red[0][3];
-        partial[((size_t)s * LARS_PARTS + part) * 2 + 1] = red[1][0] + red[1][1] + red[1][2] + red[1][3];
+        partial[((size_t)s * LARS_PARTS + part) * 2] = block_get<SumOrder::Sequential>(red[0]);
+        partial[((size_t)s * LARS_PARTS + part) * 2 + 1] = block_get<SumOrder::Sequential>(red[1]);
     }
 }
 // stage 2: q[s] = trust |p| / |dp| where both norms are > 0, else 1 (matrices); 1 for vectors
