@@ -20,7 +20,8 @@
  *     joined it the same way, and so did the detection input entry points ssl4gie_det_color{_workspace_bytes,} / ssl4gie_det_geometry / ssl4gie_det_boxes and the
  *     detection metric ssl4gie_det_map_{workspace_bytes,match,order,accumulate}, and the Faster R-CNN head entry points ssl4gie_nms_{workspace_bytes,segments} /
  *     ssl4gie_rpn_decode / ssl4gie_roi_decode / ssl4gie_roi_align_{fwd,bwd}, and the fine-tuning recipe's ssl4gie_block_{dp_workspace_bytes,fwd_dp,bwd_dp} /
- *     ssl4gie_drop_path_{add,scale_cast} / ssl4gie_mixup{,_target} / ssl4gie_soft_cross_entropy{_workspace_bytes,}; revision 12 later LOST ssl4gie_conv3x3_direct_{fwd,wgrad}_affine,
+ *     ssl4gie_drop_path_{add,scale_cast} / ssl4gie_mixup{,_target} / ssl4gie_soft_cross_entropy{_workspace_bytes,}, and its loader's ssl4gie_quantize_u8 / ssl4gie_randaug_layer{_workspace_bytes,} /
+ *     ssl4gie_normalize_erase_u8; revision 12 later LOST ssl4gie_conv3x3_direct_{fwd,wgrad}_affine,
  *     ssl4gie_block_wgrad_descs, ssl4gie_wgrad_group and the SSL4GIE_BWD_DEFER_WGRAD flag of ssl4gie_block_bwd with the two opt-in paths of the Python
  *     package that were their only callers (measured null or slower, profiles/HISTORY.md appendix 4) — the number is kept because the suite asserts 12
  *     in nine places; a caller of those four entry points fails at symbol resolution instead; 11: before the sixteen BatchNorm entry points that had grown one per fusion (ssl4gie_bn_fwd / _fwd_partials / _fwd_partials_bits /
@@ -840,6 +841,75 @@ int ssl4gie_det_boxes(const float* boxes, const long long* labels, const long lo
                       const int* sizes, long long n, const long long* index, const unsigned char* geom,
                       const long long* out_start, float* out_boxes, long long* out_labels, long long m_out, int B, int F,
                       int max_boxes, void* stream);
+
+/* ---------------------------------------------------------------- RandAugment and RandomErasing (joined ABI 12)
+ * The input of the MAE fine-tuning recipe (Models/mae/util/datasets.py:37-48: timm.data.create_transform with
+ * auto_augment='rand-m9-mstd0.5-inc1', interpolation='bicubic', re_prob=0.25, re_mode='pixel', re_count=1) after the
+ * crop and flip of ssl4gie_view_sample_u8, with the op ids, arguments, matrices and boxes already drawn
+ * (ssl4gie_amd.data.RandAugment / RandomErasing).  timm is not vendored by the reference and is absent from the build
+ * machine: the op list and level maps restate timm 0.3.2's published source (that boundary is unpinned); every PIXEL
+ * rule is PIL's, and tests/test_randaug_checks_cpu.py holds the numpy restatement of each rule below to PIL bit for bit.
+ * The intermediate image is uint8 NHWC [B, S, S, 3] (the bank's layout), S % 4 == 0.
+ *
+ * ssl4gie_quantize_u8: x fp32 NCHW [B, 3, S, S] in 0..255 units (ssl4gie_view_sample_u8 with mean 0 and std 1 / 255)
+ *   -> out uint8 NHWC: q = (int)(min(max(x, 0), 255) + 0.5f), the sum in fp32; a NaN gives 0.  One launch.  PIL rounds
+ *   to 8 bits after EACH resize pass and uses fixed-point weights; here one rounding follows the fp32 resample.
+ *
+ * ssl4gie_randaug_layer: ONE RandAugment layer, out = op[b] applied to in, per sample; in and out must not overlap.
+ *   op uint8 [B], arg fp32 [B], matrix fp64 [B, 6] (read by the geometric ops only), fill: HOST array of 3 bytes.
+ *   workspace: ssl4gie_randaug_layer_workspace_bytes(B) bytes (int32 [B, 4, 256]: the R, G, B and L histograms), zeroed
+ *   by a memset node, then two launches: the histograms of the samples whose op reads them (ids 0, 1, 8; counts private to
+ *   a workgroup in LDS, merged with integer atomics, so the result does not depend on arrival order), and the op.
+ *   L = (19595 R + 38470 G + 7471 B + 0x8000) >> 16.
+ *   clip8(t) = 0 if t <= 0, 255 if t >= 255, else t truncated.  blend(d, v, f) = clip8(d + f (v - d)) in fp32, the
+ *   product and the sum rounded one by one (Image.blend).  n = (int)arg.
+ *     0 AutoContrast   per channel, lo / hi the lowest / highest level present: identity if hi <= lo, else
+ *                      lut[i] = min(255, max(0, (int)(i s + o))), s = 255.0 / (hi - lo), o = -lo s, fp64
+ *     1 Equalize       per channel: identity if at most one level is present; step = (S S - h[hi]) / 255 (integers);
+ *                      identity if step == 0; else lut[i] = min(255, (step / 2 + h[0] + .. + h[i - 1]) / step)
+ *     2 Invert         255 - v
+ *     3 Rotate         the gather below; arg (degrees) is not read
+ *     4 Posterize      n >= 8: v;  n <= 0: 0;  else v & ~(2^(8 - n) - 1)
+ *     5 Solarize       v if v < n else 255 - v
+ *     6 SolarizeAdd    min(255, v + n) if v < 128 else v
+ *     7 Color          blend(L of the pixel, v, arg)
+ *     8 Contrast       blend(m, v, arg), m = (int)(sum_i i hL[i] / (S S) + 0.5) in fp64, hL the L histogram
+ *     9 Brightness     blend(0, v, arg)
+ *    10 Sharpness      blend(SMOOTH(v), v, arg).  SMOOTH (ImageFilter.SMOOTH) on pixels not on the one-pixel border:
+ *                      fp32, k1 = 1.f / 13.f, k5 = 5.f / 13.f, ss = 0.5f; ss += (a k1 + b k1) + c k1 over the row BELOW
+ *                      (left, centre, right), then (a k1 + b k5) + c k1 over the pixel's row, then the row above as the
+ *                      first; clip8(ss).  A border pixel is its own SMOOTH.
+ *    11 ShearX, 12 ShearY, 13 TranslateX, 14 TranslateY, and 3: Image.transform(AFFINE, matrix, BICUBIC, fillcolor), fp64,
+ *                      every operation rounded on its own:  xin = m0 (x + 0.5) + m1 (y + 0.5) + m2, yin likewise from
+ *                      m3, m4, m5; unless 0 <= xin < S and 0 <= yin < S (so a NaN too) the pixel is `fill`; else
+ *                      xin -= 0.5, x0 = floor(xin), dx = xin - x0 (y alike); taps x0 - 1 .. x0 + 2 and rows y0 - 1 .. y0 + 2,
+ *                      indices clamped to [0, S - 1]; cubic(v1..v4, d): p1 = v2, p2 = -v1 + v3, p3 = 2 (v1 - v2) + v3 - v4,
+ *                      p4 = -v1 + v2 - v3 + v4, r = p1 + d (p2 + d (p3 + d p4)); the four rows first (d = dx), then the
+ *                      column (d = dy); clip8(r) — truncated, no + 0.5.  A coordinate is compared before it is clamped
+ *                      and never addresses memory otherwise.
+ *    any other id (255 = skip) copies the sample.
+ *
+ * ssl4gie_normalize_erase_u8: ToTensor + Normalize + timm's RandomErasing in one launch: img uint8 NHWC -> out fp32
+ *   NCHW.  box int32 [B, 4] = (top, left, h, w).  Outside the box: fma(float(v), 1 / (255 std[c]), -mean[c] / std[c]),
+ *   the bits of ssl4gie_normalize_u8.  h == 0 or w == 0: no erase.  Inside: mode SSL4GIE_ERASE_CONST 0.0;
+ *   SSL4GIE_ERASE_PIXEL z(seed, b, c, y, x); SSL4GIE_ERASE_RAND z(seed, b, c, 0, 0).  A box that does not lie inside the
+ *   image (a negative entry, top + h > S, left + w > S) makes its sample all NaN; the box is compared with coordinates
+ *   and used for nothing else.  mean / std: HOST arrays of 3 floats.
+ *   z: Philox4x32-10 (Salmon et al., SC'11; multipliers 0xD2511F53 on word 0 and 0xCD9E8D57 on word 2, key increments
+ *   0x9E3779B9 and 0xBB67AE85) with counter (x, y, c, b) and key (seed & 0xffffffff, seed >> 32); k1, k2 = output words 0
+ *   and 1 shifted right by 8; u = (k + 1) 2^-24 (exact in fp32, in (0, 1]); z = sqrtf(-2.f logf(u1)) cosf(6.2831855f u2).
+ *   A pure function of (seed, b, c, y, x): the result does not depend on B or on the launch geometry.
+ * SSL4GIE_EARG: a null pointer, S % 4 != 0, S < 4, S > 2048 (layer) or 16384, B < 0, B > 65535 (layer), in == out, a
+ * pointer not 16-byte aligned, a std entry <= 0, an unknown mode.  B == 0 launches nothing. */
+#define SSL4GIE_ERASE_CONST 0
+#define SSL4GIE_ERASE_RAND 1
+#define SSL4GIE_ERASE_PIXEL 2
+int ssl4gie_quantize_u8(const float* x, unsigned char* out, int B, int S, void* stream);
+size_t ssl4gie_randaug_layer_workspace_bytes(int B);
+int ssl4gie_randaug_layer(const unsigned char* in, unsigned char* out, const unsigned char* op, const float* arg,
+                          const double* matrix, const unsigned char* fill, void* workspace, int B, int S, void* stream);
+int ssl4gie_normalize_erase_u8(const unsigned char* img, float* out, const float* mean, const float* std,
+                               const int* box, int mode, unsigned long long seed, int B, int S, void* stream);
 
 /* ---------------------------------------------------------------- detection pyramid glue (channels-last)
  * ViTDet_FPN (Models/models.py:213-259) around its GEMM-shaped convolutions:

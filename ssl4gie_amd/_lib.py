@@ -26,6 +26,7 @@ TGT_U8, TGT_U16, TGT_F32 = range(3)                                   # ssl4gie_
 DET_MAP_MAX_PER_IMAGE, DET_MAP_CLASSES, DET_MAP_CHUNK = 1024, 256, 256   # ssl4gie_det_map_*: the caps and the scan step
 NMS_MAX_PER_SEGMENT = 4096                                            # ssl4gie_nms_segments: 64 lanes x 64 bits
 PRED_I64 = 2                                                          # ssl4gie_confusion_update: int64 predictions instead of logits
+ERASE_CONST, ERASE_RAND, ERASE_PIXEL = range(3)                       # ssl4gie_normalize_erase_u8: what fills the box
 BN_MASK_NONE, BN_MASK_Y, BN_MASK_X, BN_MASK_BITS = range(4)           # backward: source of the ReLU mask
 
 vp, i32, i64, f32, sz = C.c_void_p, C.c_int, C.c_longlong, C.c_float, C.c_size_t
@@ -161,6 +162,11 @@ PROTOTYPES = {
     "ssl4gie_normalize_u8": (i32, [vp, vp, C.POINTER(C.c_float), C.POINTER(C.c_float), i32, i32, i32, vp]),
     "ssl4gie_view_sample_u8": (i32, [vp, i64, i32, i32, vp, vp, vp, vp, i32, i32, i32, C.POINTER(C.c_float),
                                      C.POINTER(C.c_float), vp]),
+    "ssl4gie_quantize_u8": (i32, [vp, vp, i32, i32, vp]),
+    "ssl4gie_randaug_layer_workspace_bytes": (sz, [i32]),
+    "ssl4gie_randaug_layer": (i32, [vp, vp, vp, vp, vp, C.POINTER(C.c_ubyte), vp, i32, i32, vp]),
+    "ssl4gie_normalize_erase_u8": (i32, [vp, vp, C.POINTER(C.c_float), C.POINTER(C.c_float), vp, i32, C.c_ulonglong, i32,
+                                         i32, vp]),
     "ssl4gie_color_augment_workspace_bytes": (sz, [i32, i32]),
     "ssl4gie_color_augment": (i32, [vp, vp, i32, i32, vp, vp, vp, vp, C.POINTER(C.c_float), C.POINTER(C.c_float), vp, sz,
                                     vp]),

@@ -54,6 +54,23 @@ batch in place with one launch of ops.mixup; ops.mixup_target builds the soft ta
 
     mixup_fn = Mixup(mixup_alpha=0.8, cutmix_alpha=1.0, label_smoothing=0.1, num_classes=1000)
     samples, targets = mixup_fn(samples, targets)                       # engine_finetune.py:53, as written
+
+The input of that recipe (Models/mae/util/datasets.py:25-66: timm's create_transform with auto_augment=
+'rand-m9-mstd0.5-inc1', bicubic, re_prob=0.25, re_mode='pixel', re_count=1) is `MAEFinetuneTransform`: the crop and
+flip of `RandomResizedCropFlip` in 0..255 units, ops.quantize_u8 to the bank's uint8 layout, one ops.randaug_layer per
+RandAugment layer on op ids, arguments and AFFINE matrices drawn on the device (`RandAugment`), and
+ops.normalize_erase_u8, which is ToTensor + Normalize + `RandomErasing` in one pass.  The pixel rules are PIL's, bit
+for bit; timm's op list and level maps are restated from its published source.
+
+    bank = DeviceImageBank.from_npy("train_256.npy", "cuda", labels="train_labels.npy")
+    loader = DeviceLoader(bank, 256, sampler=sampler_train, transform=MAEFinetuneTransform(224))
+    val = DeviceLoader(DeviceImageBank.from_npy("val_256.npy", "cuda", labels="val_labels.npy"), 256,
+                       sampler=sampler_val, drop_last=False, transform=MAEFinetuneTransform.eval(224))
+    for data_iter_step, (samples, targets) in enumerate(loader):        # engine_finetune.py:42-53, as written
+        samples = samples.to(device, non_blocking=True)                 # already there
+        targets = targets.to(device, non_blocking=True)
+        if mixup_fn is not None:
+            samples, targets = mixup_fn(samples, targets)
 """
 from __future__ import annotations
 
@@ -689,6 +706,237 @@ class DeviceLoader:
                 idx = []
         if idx and not self.drop_last:
             yield self._batch(idx)
+
+
+# ------------------------------------------------------------------------------------------------
+# The train and eval transforms of the MAE fine-tuning recipe (Models/mae/util/datasets.py:25-66: timm's
+# create_transform with auto_augment='rand-m9-mstd0.5-inc1', bicubic, re_prob=0.25, re_mode='pixel', re_count=1).
+# timm is not vendored by the reference: the op list, level maps and RandomErasing restate timm 0.3.2's published
+# source; the pixel rules are PIL's (include/ssl4gie_hip.h, tests/randaug_checks.py).
+# ------------------------------------------------------------------------------------------------
+RANDAUG_OPS = ("AutoContrast", "Equalize", "Invert", "Rotate", "Posterize", "Solarize", "SolarizeAdd", "Color", "Contrast",
+               "Brightness", "Sharpness", "ShearX", "ShearY", "TranslateXRel", "TranslateYRel")   # id = position
+RANDAUG_SKIP = 255
+
+
+def randaug_level_args(op, magnitude, negate, inc, size):
+    """timm's level functions (auto_augment.py, _MAX_LEVEL = 10) as a pure function of the draws: op int64 [N] (ids of
+    RANDAUG_OPS), magnitude float64 [N] in [0, 10], negate bool [N] (_randomly_negate's `random() > 0.5`), inc: the
+    'Increasing' variants of Posterize / Solarize / Color / Contrast / Brightness / Sharpness.  Returns arg fp32 [N] — what
+    the kernel reads: bits, threshold, addend, blend factor; for the geometric ops degrees, shear or pixels, for the
+    record — and matrix float64 [N, 6], PIL's AFFINE coefficients (the identity for the other ops).  float64 in timm's
+    order of operations on op's device, no host read-back.  Image.rotate rounds cos and sin to 15 decimals; this does not."""
+    lv = magnitude.to(torch.float64) / 10
+    neg = lambda v: torch.where(negate, -v, v)
+    zero = torch.zeros_like(lv)
+    rot = neg(lv * 30.)
+    post = torch.trunc(lv * 4)
+    sol = torch.trunc(lv * 256)
+    if inc:
+        post, sol = 4 - post, 256 - sol
+    sadd = torch.trunc(lv * 110)
+    enh = 1.0 + neg(lv * .9) if inc else lv * 1.8 + 0.1
+    shear = neg(lv * 0.3)
+    trans = neg(lv * 0.45) * size
+    table = torch.stack([zero, zero, zero, rot, post, sol, sadd, enh, enh, enh, enh, shear, shear, trans, trans], dim=1)
+    known = (op >= 0) & (op < len(RANDAUG_OPS))
+    arg = torch.where(known, table.gather(1, op.clamp(0, len(RANDAUG_OPS) - 1).view(-1, 1)).squeeze(1), zero)
+    a = -torch.deg2rad(rot)
+    c, s = torch.cos(a), torch.sin(a)
+    half = size / 2.0
+    is_rot = op == 3
+    one = torch.ones_like(lv)
+    m2 = (c * -half + s * -half + 0.0) + half     # Image.rotate: the centre through the matrix, then the centre added
+    m5 = (-s * -half + c * -half + 0.0) + half
+    matrix = torch.stack([torch.where(is_rot, c, one),
+                          torch.where(is_rot, s, torch.where(op == 11, shear, zero)),
+                          torch.where(is_rot, m2, torch.where(op == 13, trans, zero)),
+                          torch.where(is_rot, -s, torch.where(op == 12, shear, zero)),
+                          torch.where(is_rot, c, one),
+                          torch.where(is_rot, m5, torch.where(op == 14, trans, zero))], dim=1)
+    return arg.to(torch.float32), matrix.contiguous()
+
+
+class RandAugment:
+    """timm's rand_augment_transform(config_str, hparams) over the 15 ops of RANDAUG_OPS, drawn on the device:
+    config_str 'rand-m9-mstd0.5-inc1' with the keys m (magnitude), n (layers, default 2), mstd (default 0), inc (0 / 1);
+    w (weighted choice) raises NotImplementedError.  `size` is the image side (TranslateXRel moves 0.45 level size
+    pixels), `mean` gives the fill colour of the geometric ops, min(255, round(255 m)).  Per image and layer: an op
+    uniformly from the 15 (with replacement), skipped with probability 0.5, magnitude clip(gauss(m, mstd), 0, 10)."""
+
+    def __init__(self, config_str, size, mean=IMAGENET_MEAN, generator=None):
+        parts = str(config_str).split("-")
+        if parts[0] != "rand":
+            raise ValueError(f"RandAugment takes a 'rand-...' config string, got {config_str!r}")
+        self.magnitude, self.layers, self.mstd, self.inc = 10.0, 2, 0.0, 0
+        for part in parts[1:]:
+            key = part.rstrip("0123456789.")
+            val = part[len(key):]
+            if not key or not val:
+                raise ValueError(f"RandAugment config section {part!r} of {config_str!r} is not a key and a number")
+            if key == "w":
+                raise NotImplementedError("RandAugment: the weighted op choice ('w') is not built")
+            if key == "m":
+                self.magnitude = float(int(val))
+            elif key == "n":
+                self.layers = int(val)
+            elif key == "mstd":
+                self.mstd = float(val)
+            elif key == "inc":
+                self.inc = int(bool(int(val)))
+            else:
+                raise ValueError(f"unknown RandAugment config section {part!r} in {config_str!r}")
+        if self.layers < 1 or not 0.0 <= self.magnitude <= 10.0:
+            raise ValueError(f"RandAugment needs n >= 1 and 0 <= m <= 10, got {config_str!r}")
+        self.size, self.generator = int(size), generator
+        self.fill = tuple(min(255, int(round(255 * m))) for m in mean)
+
+    def draw(self, B, device):
+        """op uint8 [B, n] (255 = skipped), arg fp32 [B, n], matrix float64 [B, n, 6]; advances the generator.
+        Vectorised on the device, no host read-back; timm's random SEQUENCE is not reproduced, its distribution is."""
+        n = self.layers
+        u = torch.rand(B, n, 3, dtype=torch.float64, device=device, generator=self.generator)
+        z = torch.randn(B, n, dtype=torch.float64, device=device, generator=self.generator)
+        op = torch.floor(u[..., 0] * len(RANDAUG_OPS)).clamp(max=len(RANDAUG_OPS) - 1).to(torch.int64)
+        skip = u[..., 1] > 0.5
+        mag = torch.full_like(z, self.magnitude)
+        if self.mstd > 0:
+            mag = mag + z * self.mstd
+        mag = mag.clamp(0.0, 10.0)
+        op = torch.where(skip, RANDAUG_SKIP, op)
+        arg, matrix = randaug_level_args(op.view(-1), mag.view(-1), (u[..., 2] > 0.5).view(-1), self.inc, self.size)
+        return op.to(torch.uint8), arg.view(B, n), matrix.view(B, n, 6)
+
+
+def erase_boxes(u, H, W, probability=0.5, min_area=0.02, max_area=1 / 3, min_aspect=0.3, max_aspect=None):
+    """timm's RandomErasing box choice (max_count = 1) as a pure function of uniforms u [B, 41] in [0, 1): u[:, 0] the
+    apply draw (no erase when it exceeds `probability`), then ten tries of (area fraction, log-aspect, top, left); the
+    first try with h < H and w < W wins, none: no erase.  float64 on u's device, vectorised, no host read-back.
+    Returns int32 [B, 4] = (top, left, h, w), all 0 for no erase."""
+    assert u.dim() == 2 and u.shape[1] == 41
+    u = u.to(torch.float64)
+    B = u.shape[0]
+    t = u[:, 1:].view(B, 10, 4)
+    l0, l1 = math.log(min_aspect), math.log(max_aspect or 1 / min_aspect)
+    target = (min_area + (max_area - min_area) * t[..., 0]) * (H * W)
+    aspect = torch.exp(l0 + (l1 - l0) * t[..., 1])
+    h = torch.round(torch.sqrt(target * aspect))          # round half to even, as Python's round()
+    w = torch.round(torch.sqrt(target / aspect))
+    ok = (w < W) & (h < H)
+    top = torch.minimum(torch.floor(t[..., 2] * (H - h + 1)), H - h)     # random.randint(0, H - h)
+    left = torch.minimum(torch.floor(t[..., 3] * (W - w + 1)), W - w)
+    first = torch.argmax(ok.to(torch.uint8), dim=1)
+    won = torch.stack([top, left, h, w], dim=2).gather(1, first.view(-1, 1, 1).expand(-1, 1, 4)).squeeze(1)
+    apply = ~(u[:, 0] > probability) & ok.any(dim=1)
+    return torch.where(apply.unsqueeze(1), won, torch.zeros_like(won)).to(torch.int32)
+
+
+class RandomErasing:
+    """timm.data.RandomErasing(probability, mode, min_area, max_area, min_aspect, max_aspect, max_count=1) on the
+    uint8 image that Normalize would read: __call__(img_u8 [B, S, S, 3], seed, mean, std) -> fp32 [B, 3, S, S], the
+    normalised batch with one box per erased sample filled with per-element N(0, 1) noise ('pixel'), one N(0, 1) value
+    per channel ('rand') or zeros ('const') — one launch of ops.normalize_erase_u8.  max_count > 1 is not built."""
+
+    def __init__(self, probability=0.5, mode="const", min_area=0.02, max_area=1 / 3, min_aspect=0.3, max_aspect=None,
+                 max_count=1, generator=None):
+        if max_count != 1:
+            raise NotImplementedError("RandomErasing: max_count > 1 is not built")
+        if mode not in ("const", "rand", "pixel"):
+            raise ValueError(f"mode must be 'const', 'rand' or 'pixel', got {mode!r}")
+        self.probability, self.mode = float(probability), mode
+        self.min_area, self.max_area, self.min_aspect, self.max_aspect = min_area, max_area, min_aspect, max_aspect
+        self.generator = generator
+
+    def draw(self, B, H, W, device):
+        """box int32 [B, 4] (advances the generator)"""
+        u = torch.rand(B, 41, dtype=torch.float64, device=device, generator=self.generator)
+        return erase_boxes(u, H, W, self.probability, self.min_area, self.max_area, self.min_aspect, self.max_aspect)
+
+    def __call__(self, img_u8, seed, mean=IMAGENET_MEAN, std=IMAGENET_STD):
+        box = self.draw(img_u8.shape[0], img_u8.shape[1], img_u8.shape[2], img_u8.device)
+        return ops.normalize_erase_u8(img_u8, box, self.mode, seed, mean, std)
+
+
+class MAEFinetuneTransform:
+    """build_transform(is_train=True) of Models/mae/util/datasets.py:25-48 for DeviceLoader, drawn and computed on the
+    bank's device: RandomResizedCropAndInterpolation(input_size, scale, bicubic) + RandomHorizontalFlip
+    (RandomResizedCropFlip into 0..255 units) -> ops.quantize_u8 -> the n layers of RandAugment(auto_augment)
+    (ops.randaug_layer between two uint8 buffers kept across calls; None: no layers) -> ToTensor + Normalize +
+    RandomErasing(re_prob, re_mode) (ops.normalize_erase_u8).  __call__(bank, index) -> fp32 [B, 3, S, S].
+    One generator is drawn from in the order crop, RandAugment, erase; the noise seed of call k is
+    noise_seed + k 0x9E3779B97F4A7C15 mod 2^64, noise_seed defaulting to the generator's (or torch's) initial seed, which
+    the host knows: nothing is read back.  MAEFinetuneTransform.eval(input_size) is the eval transform."""
+
+    _GOLDEN = 0x9E3779B97F4A7C15
+
+    def __init__(self, input_size=224, auto_augment="rand-m9-mstd0.5-inc1", re_prob=0.25, re_mode="pixel", re_count=1,
+                 scale=(0.08, 1.0), mean=IMAGENET_MEAN, std=IMAGENET_STD, generator=None, noise_seed=None):
+        self.size, self.mean, self.std, self.generator = int(input_size), tuple(mean), tuple(std), generator
+        # the crop in 0..255 units: (v / 255 - 0) / (1 / 255)
+        self.crop = RandomResizedCropFlip(self.size, scale=scale, interpolation="bicubic", mean=(0.0, 0.0, 0.0),
+                                          std=(1.0 / 255.0,) * 3, generator=generator)
+        self.randaug = None if auto_augment is None else RandAugment(auto_augment, self.size, mean, generator)
+        self.erase = RandomErasing(re_prob, re_mode, max_count=re_count, generator=generator)
+        if noise_seed is None:
+            noise_seed = generator.initial_seed() if generator is not None else torch.initial_seed()
+        self.noise_seed, self.calls = int(noise_seed) & 0xffffffffffffffff, 0
+        self.stored = self.offset = None   # set by eval()
+        self._bufs = self._workspace = self._eval_box = None
+
+    @classmethod
+    def eval(cls, input_size=224, mean=IMAGENET_MEAN, std=IMAGENET_STD):
+        """build_transform(is_train=False), datasets.py:50-66: Resize(int(input_size / crop_pct), bicubic) + CenterCrop
+        (input_size) + ToTensor + Normalize, crop_pct = 224 / 256 up to input_size 224 and 1 above, for a bank stored
+        square at int(input_size / crop_pct), where the Resize is the identity: the centre box at
+        int(round((M - S) / 2.)), bit-equal to ops.normalize_u8 of that slice.  Any other stored size raises."""
+        t = cls(input_size, auto_augment=None, re_prob=0.0, mean=mean, std=std, noise_seed=0)
+        crop_pct = 224 / 256 if t.size <= 224 else 1.0
+        t.stored = int(t.size / crop_pct)
+        t.offset = int(round((t.stored - t.size) / 2.))
+        return t
+
+    def draw(self, B, Hs, Ws, device):
+        """(box int32 [B, 4], flip uint8 [B], layers: None or (op uint8 [n, B], arg fp32 [n, B], matrix float64
+        [n, B, 6]), erase box int32 [B, 4], noise seed); advances the generator and the call counter"""
+        box, flip = self.crop.draw(B, Hs, Ws, device)
+        layers = None
+        if self.randaug is not None:
+            op, arg, matrix = self.randaug.draw(B, device)
+            layers = (op.t().contiguous(), arg.t().contiguous(), matrix.transpose(0, 1).contiguous())
+        ebox = self.erase.draw(B, self.size, self.size, device)
+        seed = (self.noise_seed + self.calls * self._GOLDEN) & 0xffffffffffffffff
+        self.calls += 1
+        return box, flip, layers, ebox, seed
+
+    def apply(self, bank, index, box, flip, layers, ebox, seed):
+        """the launches, on draws that are given"""
+        B, S = index.shape[0], self.size
+        x = ops.view_sample_u8(bank.images, index, box, flip, S, "bicubic", self.crop.mean, self.crop.std)
+        if self._bufs is None or self._bufs[0].shape[0] < B or self._bufs[0].device != x.device:
+            self._bufs = [torch.empty(B, S, S, 3, dtype=torch.uint8, device=x.device) for _ in range(2)]
+            self._workspace = ops.randaug_layer_workspace(B, x.device)
+        cur, nxt = self._bufs[0][:B], self._bufs[1][:B]
+        ops.quantize_u8(x, cur)
+        if layers is not None:
+            for op, arg, matrix in zip(*layers):
+                ops.randaug_layer(cur, op, arg, matrix, self.randaug.fill, nxt, self._workspace)
+                cur, nxt = nxt, cur
+        return ops.normalize_erase_u8(cur, ebox, self.erase.mode, seed, self.mean, self.std)
+
+    def __call__(self, bank, index):
+        Hs, Ws = bank.stored_size
+        if self.stored is not None:
+            if (Hs, Ws) != (self.stored, self.stored):
+                raise ValueError(f"MAEFinetuneTransform.eval({self.size}) needs a bank stored at {self.stored} x "
+                                 f"{self.stored} (Resize({self.stored}) is then the identity), got {Hs} x {Ws}: pack it "
+                                 f"at {self.stored} (tools/pack_images.py --size {self.stored})")
+            B = index.shape[0]
+            if self._eval_box is None or self._eval_box.device != index.device:
+                self._eval_box = torch.tensor([[self.offset, self.offset, self.size, self.size]], dtype=torch.int32,
+                                              device=index.device)
+            return ops.view_sample_u8(bank.images, index, self._eval_box.expand(B, 4).contiguous(), None, self.size,
+                                      "bicubic", self.mean, self.std)
+        return self.apply(bank, index, *self.draw(index.shape[0], Hs, Ws, index.device))
 
 
 # ------------------------------------------------------------------------------------------------

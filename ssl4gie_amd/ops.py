@@ -1428,6 +1428,93 @@ def view_sample_u8(bank, index, box, flip, S, filter="bicubic", mean=IMAGENET_ME
     return out
 
 
+def _u8_images(name, img):
+    if not (img.dtype == torch.uint8 and img.dim() == 4 and img.shape[3] == 3 and img.shape[1] == img.shape[2]
+            and img.is_contiguous()):
+        raise ValueError(f"{name} needs contiguous uint8 images [B, S, S, 3], got {img.dtype} {tuple(img.shape)}")
+    if img.shape[1] < 4 or img.shape[1] % 4:
+        raise ValueError(f"{name} needs S >= 4 and a multiple of 4, got {img.shape[1]}")
+
+
+def quantize_u8(x, out=None):
+    """fp32 NCHW [B, 3, S, S] in 0..255 units (view_sample_u8 with mean 0, std 1 / 255) -> uint8 NHWC [B, S, S, 3]:
+    clamp to [0, 255], add 0.5 in fp32, truncate; a NaN gives 0.  The one rounding between the engine's fp32 resample and
+    the uint8 ops of RandAugment (PIL rounds after each resize pass)."""
+    _dev(x, out)
+    _f32(x)
+    if x.dim() != 4 or x.shape[1] != 3 or x.shape[2] != x.shape[3] or x.shape[2] % 4 or not x.is_contiguous():
+        raise ValueError(f"quantize_u8 needs contiguous x [B, 3, S, S] with S a multiple of 4, got {tuple(x.shape)}")
+    B, _, S, _ = x.shape
+    if out is None:
+        out = torch.empty(B, S, S, 3, dtype=torch.uint8, device=x.device)
+    _u8_images("quantize_u8 (out)", out)
+    assert tuple(out.shape) == (B, S, S, 3)
+    _lib.check(_lib.load().ssl4gie_quantize_u8(ptr(x), ptr(out), B, S, stream()), "quantize_u8")
+    return out
+
+
+def randaug_layer_workspace(B, device):
+    """the histogram workspace of randaug_layer for up to B samples"""
+    return torch.empty(_lib.load().ssl4gie_randaug_layer_workspace_bytes(B), dtype=torch.uint8, device=device)
+
+
+def randaug_layer(img, op, arg, matrix, fill, out=None, workspace=None):
+    """One RandAugment layer on uint8 NHWC images [B, S, S, 3]: out[b] = op[b] applied to img[b].  op uint8 [B] holds
+    timm's op ids (0 AutoContrast, 1 Equalize, 2 Invert, 3 Rotate, 4 Posterize, 5 Solarize, 6 SolarizeAdd, 7 Color,
+    8 Contrast, 9 Brightness, 10 Sharpness, 11 ShearX, 12 ShearY, 13 TranslateX, 14 TranslateY; any other id, 255 by
+    convention, copies), arg fp32 [B] the bits / threshold / addend / factor, matrix fp64 [B, 6] PIL's AFFINE
+    coefficients of the geometric ops (bicubic, `fill` = three byte values where the source lies outside).  PIL's rules,
+    bit for bit (include/ssl4gie_hip.h spells them out).  `out` must not share memory with img; `workspace`: a uint8
+    buffer from randaug_layer_workspace, allocated when None."""
+    _dev(img, op, arg, matrix, out, workspace)
+    _u8_images("randaug_layer", img)
+    B, S = img.shape[0], img.shape[1]
+    if op.dtype != torch.uint8 or tuple(op.shape) != (B,) or not op.is_contiguous():
+        raise ValueError(f"op must be contiguous uint8 [{B}], got {op.dtype} {tuple(op.shape)}")
+    if arg.dtype != torch.float32 or tuple(arg.shape) != (B,) or not arg.is_contiguous():
+        raise ValueError(f"arg must be contiguous float32 [{B}], got {arg.dtype} {tuple(arg.shape)}")
+    if matrix.dtype != torch.float64 or tuple(matrix.shape) != (B, 6) or not matrix.is_contiguous():
+        raise ValueError(f"matrix must be contiguous float64 [{B}, 6], got {matrix.dtype} {tuple(matrix.shape)}")
+    if out is None:
+        out = torch.empty_like(img)
+    _u8_images("randaug_layer (out)", out)
+    if tuple(out.shape) != tuple(img.shape) or out.data_ptr() == img.data_ptr():
+        raise ValueError("out must have img's shape and must not be img")
+    L = _lib.load()
+    if workspace is None:
+        workspace = randaug_layer_workspace(B, img.device)
+    assert workspace.dtype == torch.uint8 and workspace.numel() >= L.ssl4gie_randaug_layer_workspace_bytes(B)
+    f = (C.c_ubyte * 3)(*(int(v) for v in fill))
+    _lib.check(L.ssl4gie_randaug_layer(ptr(img), ptr(out), ptr(op), ptr(arg), ptr(matrix), f, ptr(workspace), B, S,
+                                       stream()), "randaug_layer")
+    return out
+
+
+_ERASE_MODES = {"const": _lib.ERASE_CONST, "rand": _lib.ERASE_RAND, "pixel": _lib.ERASE_PIXEL}
+
+
+def normalize_erase_u8(img_u8, box, mode="pixel", seed=0, mean=IMAGENET_MEAN, std=IMAGENET_STD):
+    """ToTensor + Normalize + timm's RandomErasing in one pass: uint8 NHWC [B, S, S, 3] -> fp32 NCHW.  box int32 [B, 4] =
+    (top, left, h, w); h == 0 or w == 0 erases nothing; outside the box the result has normalize_u8's bits.  Inside:
+    `pixel` N(0, 1) noise per element, `rand` one N(0, 1) value per channel, `const` zeros.  The noise is a pure
+    function of (seed, b, c, y, x) — Philox4x32-10 and a fp32 Box-Muller, include/ssl4gie_hip.h — so the same seed gives
+    the same bits whatever B is.  A box that does not lie inside the image gives an all-NaN sample."""
+    _dev(img_u8, box)
+    _u8_images("normalize_erase_u8", img_u8)
+    B, S = img_u8.shape[0], img_u8.shape[1]
+    if box.dtype != torch.int32 or tuple(box.shape) != (B, 4) or not box.is_contiguous():
+        raise ValueError(f"box must be contiguous int32 [{B}, 4], got {box.dtype} {tuple(box.shape)}")
+    if mode not in _ERASE_MODES:
+        raise ValueError(f"mode must be 'const', 'rand' or 'pixel', got {mode!r}")
+    out = torch.empty(B, 3, S, S, dtype=torch.float32, device=img_u8.device)
+    m = (C.c_float * 3)(*mean)
+    s = (C.c_float * 3)(*std)
+    _lib.check(_lib.load().ssl4gie_normalize_erase_u8(ptr(img_u8), ptr(out), m, s, ptr(box), _ERASE_MODES[mode],
+                                                      int(seed) & 0xffffffffffffffff, B, S, stream()),
+               "normalize_erase_u8")
+    return out
+
+
 def color_augment(x, factors, order, flags, sigma, mean=IMAGENET_MEAN, std=IMAGENET_STD, out=None):
     """The colour half of MoCo-v3's augmentation on fp32 [B, 3, S, S] images in [0, 1] (view_sample_u8 with
     mean 0, std 1), per-sample parameters given as device arrays (data.ColorAugment draws them): colour jitter —
