@@ -21,7 +21,7 @@
  *     detection metric ssl4gie_det_map_{workspace_bytes,match,order,accumulate}, and the Faster R-CNN head entry points ssl4gie_nms_{workspace_bytes,segments} /
  *     ssl4gie_rpn_decode / ssl4gie_roi_decode / ssl4gie_roi_align_{fwd,bwd}, and the fine-tuning recipe's ssl4gie_block_{dp_workspace_bytes,fwd_dp,bwd_dp} /
  *     ssl4gie_drop_path_{add,scale_cast} / ssl4gie_mixup{,_target} / ssl4gie_soft_cross_entropy{_workspace_bytes,}, and its loader's ssl4gie_quantize_u8 / ssl4gie_randaug_layer{_workspace_bytes,} /
- *     ssl4gie_normalize_erase_u8; revision 12 later LOST ssl4gie_conv3x3_direct_{fwd,wgrad}_affine,
+ *     ssl4gie_normalize_erase_u8, and the linear probe's ssl4gie_topk_{workspace_bytes,update} / ssl4gie_sgd_arena; revision 12 later LOST ssl4gie_conv3x3_direct_{fwd,wgrad}_affine,
  *     ssl4gie_block_wgrad_descs, ssl4gie_wgrad_group and the SSL4GIE_BWD_DEFER_WGRAD flag of ssl4gie_block_bwd with the two opt-in paths of the Python
  *     package that were their only callers (measured null or slower, profiles/HISTORY.md appendix 4) — the number is kept because the suite asserts 12
  *     in nine places; a caller of those four entry points fails at symbol resolution instead; 11: before the sixteen BatchNorm entry points that had grown one per fusion (ssl4gie_bn_fwd / _fwd_partials / _fwd_partials_bits /
@@ -690,6 +690,42 @@ size_t ssl4gie_lars_workspace_bytes(int S);
 int ssl4gie_lars_arena(float* p, const float* g, float* mu, const long long* seg_start,
                        const float* seg_lr, const float* seg_wd, const float* seg_mat, int S,
                        float momentum, float trust, float* workspace, long long n, void* stream);
+
+/* ---------------------------------------------------------------- linear probe: scoring and the head's SGD step
+ * (csrc/probe_ops.hip; joined ABI 12 as additions).  The frozen trunk's forward is the bulk of a probe step
+ * (Models/mae/main_linprobe.py, Models/moco_v3/main_lincls.py) and is not touched; these are the device code around it.
+ *
+ * topk_update  accuracy(output, target, topk) (main_lincls.py:506-520; timm's accuracy at Models/mae/engine_finetune.py:
+ *              19,119-124) and the criterion's value for one batch, added into caller-owned device accumulators so
+ *              that a loader is scored with ONE read-back instead of one .item() per meter per batch.
+ *              logits [B, C] of `dtype` (SSL4GIE_F32 / SSL4GIE_BF16) with row stride ld >= C ELEMENTS; target int64 [B];
+ *              ks: HOST array of nk (1..8) strictly ascending values in [1, C].
+ *              acc int64 [nk + 2] += (hits at ks[0], ..., hits at ks[nk - 1], rows counted, rows rejected);
+ *              loss_sum fp64 [1] += the sum of the counted rows' cross-entropy; rank (int32 [B]) / row_loss (fp32 [B]),
+ *              each may be NULL, are overwritten: the row's rank and loss, -1 and 0 for a rejected row.
+ *              Rank of a row = the number of columns ordered above the target's logit; equal values are ordered by
+ *              lower index first (the rule of ssl4gie_confusion_update's argmax; torch.topk leaves ties open), a NaN
+ *              above every number as torch orders it, NaNs among themselves by lower index first.  Hit at k: rank < k.
+ *              A target outside [0, C) is never used as an index: the row is counted as rejected and adds to nothing
+ *              else.  Loss = logsumexp - target logit in fp32 with the row maximum subtracted (logits of magnitude 1e4
+ *              give a finite loss); a row holding a NaN has a NaN loss, which reaches loss_sum.
+ *              One wave per row; a row is walked in 16-byte chunks, a chunk inside the row at a 16-byte aligned address
+ *              by one load and any other column by column, on the same lane either way: any C, ld and base are
+ *              accepted and a row's loss does not depend on its alignment.  The row losses are added in fp64 in a fixed
+ *              order (rows in index order over 256 threads, then a tree), no floating-point atomics: the same inputs
+ *              give the same bits from run to run and for any grid.  The counts are integer atomics.
+ *              workspace: ssl4gie_topk_workspace_bytes(B) bytes (0 for B <= 0), 4-byte aligned.  C <= 2^30.
+ * sgd_arena    torch.optim.SGD(momentum, weight_decay) with dampening 0 and no Nesterov (main_lincls.py:236-238) over the
+ *              segment tables above: d = g + wd p; buf = momentum buf + d; p -= lr buf.  A zero buf reproduces torch's
+ *              first step (buf = d).  A skipped segment's p and buf (its padding included) stay bit-unchanged; an
+ *              active segment's zero padding stays zero (g, p and buf are all zero there).  It takes the n elements (n % 4 == 0) behind the pointers it is
+ *              given (16-byte aligned): a caller may hand it a sub-range of the arena with seg_start rebased to it. */
+size_t ssl4gie_topk_workspace_bytes(int B);
+int ssl4gie_topk_update(const void* logits, int dtype, long long ld, const long long* target, const int* ks, int nk,
+                        long long* acc, double* loss_sum, int* rank, float* row_loss, int B, int C, void* workspace,
+                        void* stream);
+int ssl4gie_sgd_arena(float* p, const float* g, float* buf, const long long* seg_start, const float* seg_lr,
+                      const float* seg_wd, int S, float momentum, long long n, void* stream);
 
 /* ---------------------------------------------------------------- input pipeline
  * transforms.ToTensor() + transforms.Normalize(mean, std) (Depth_estimation/Data/dataloaders.py:

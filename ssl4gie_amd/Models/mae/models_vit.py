@@ -10,6 +10,11 @@ Forward (reference :34-53): patch embedding + [cls | tokens] + pos_embed, the bl
 (engine.run_blocks draws timm's per-sample factors for the whole stack at once), then either the mean over the patch
 tokens followed by `fc_norm`, or `norm` and the cls row; `head` gives fp32 logits.  `pos_drop` is the identity
 (drop_rate is 0 in the recipe).
+
+`head` is an nn.Linear, an nn.Identity, or the linear probe's `Sequential(BatchNorm1d(affine=False), Linear)`
+(reference `main_linprobe.py:222`; state keys `head.0.running_mean`, `head.0.running_var`,
+`head.0.num_batches_tracked`, `head.1.weight`, `head.1.bias`): the BatchNorm runs in the engine's BatchNorm kernels,
+then the product.  Anything else raises TypeError.  `forward_head(feats)` drives the head on given features.
 """
 from __future__ import annotations
 
@@ -79,11 +84,30 @@ class VisionTransformer(EngineModule):
             return self._ln(pooled, self.fc_norm)
         return self._ln(tok[:, 0].contiguous(), self.norm)  # LayerNorm is per token: the cls row alone
 
-    def forward(self, x, drop_scales=None):
-        x = self.forward_features(x, drop_scales=drop_scales)
-        if isinstance(self.head, nn.Identity):
+    _HEADS = ("nn.Linear", "nn.Identity", "nn.Sequential(nn.BatchNorm1d(affine=False), nn.Linear)")
+
+    def _head(self, x):
+        head = self.head
+        if isinstance(head, nn.Identity):
             return x.float()
-        return self._linear(x, self.head, out_dtype=torch.float32)
+        if isinstance(head, nn.Linear):
+            return self._linear(x, head, out_dtype=torch.float32)
+        if isinstance(head, nn.Sequential) and len(head) == 2 and type(head[0]) is nn.BatchNorm1d \
+                and not head[0].affine and isinstance(head[1], nn.Linear):
+            # the linear probe's head (reference main_linprobe.py:222): training mode normalises with the batch
+            # statistics and updates the running ones, eval() uses the running ones
+            from ...resnet_engine import BatchNormFn
+            x = BatchNormFn.apply(x.contiguous(), None, None, None, head[0], False, self.sink())
+            return self._linear(x, head[1], out_dtype=torch.float32)
+        raise TypeError(f"VisionTransformer.head must be one of {', '.join(self._HEADS)}; got {head!r}")
+
+    def forward_head(self, feats):
+        """`head` on given [B, D] features (what forward_features returns) -> fp32 logits"""
+        self._prepare()
+        return self._head(feats if feats.dtype == self.dtype_ else feats.to(self.dtype_))
+
+    def forward(self, x, drop_scales=None):
+        return self._head(self.forward_features(x, drop_scales=drop_scales))
 
 
 def _vit(embed_dim, depth, num_heads, patch_size=16, **kwargs):

@@ -37,7 +37,8 @@ class Bottleneck(nn.Module):
 
 
 class ResNet50(EngineModule):
-    """trunk only: `forward_features` -> channels-last layer4 map (or the 4 stage maps)"""
+    """the trunk (`forward_maps` -> channels-last layer4 map, or the 4 stage maps; `pooled`) and, when built with
+    num_classes, torchvision's `forward` through `fc`"""
 
     def __init__(self, zero_init_residual=False, num_classes=None):
         super().__init__()
@@ -189,6 +190,15 @@ class ResNet50(EngineModule):
     def pooled(self, imgs):
         """[B, 2048] fp32: avgpool + flatten of the layer4 map"""
         return AvgPoolFn.apply(self.forward_maps(imgs))
+
+    def forward(self, imgs):
+        """torchvision's `ResNet.forward`: pooled features -> `fc` -> fp32 logits [B, num_classes] (the 'fc' arm of the
+        linear probe, reference Models/moco_v3/main_lincls.py:157-161)"""
+        if not isinstance(getattr(self, "fc", None), nn.Linear):
+            raise RuntimeError("ResNet50.forward needs the classifier `fc`: build it with num_classes "
+                               "(resnet50(num_classes=...)); a trunk built without one has pooled() / forward_maps()")
+        x = self.pooled(imgs).to(self.dtype_)
+        return LinearFn.apply(x, self.fc.weight, self.fc.bias, self.dtype_, torch.float32, self.sink(), self.lp_cache)
 
 
 def resnet50(num_classes=1000, zero_init_residual=False, **kwargs):

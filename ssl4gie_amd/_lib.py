@@ -159,6 +159,9 @@ PROTOTYPES = {
     "ssl4gie_grad_scale_arena": (i32, [vp, vp, vp, i32, vp, i64, vp]),
     "ssl4gie_lars_workspace_bytes": (sz, [i32]),
     "ssl4gie_lars_arena": (i32, [vp, vp, vp, vp, vp, vp, vp, i32, f32, f32, vp, i64, vp]),
+    "ssl4gie_topk_workspace_bytes": (sz, [i32]),
+    "ssl4gie_topk_update": (i32, [vp, i32, i64, vp, C.POINTER(i32), i32, vp, vp, vp, vp, i32, i32, vp, vp]),
+    "ssl4gie_sgd_arena": (i32, [vp, vp, vp, vp, vp, vp, i32, f32, i64, vp]),
     "ssl4gie_normalize_u8": (i32, [vp, vp, C.POINTER(C.c_float), C.POINTER(C.c_float), i32, i32, i32, vp]),
     "ssl4gie_view_sample_u8": (i32, [vp, i64, i32, i32, vp, vp, vp, vp, i32, i32, i32, C.POINTER(C.c_float),
                                      C.POINTER(C.c_float), vp]),

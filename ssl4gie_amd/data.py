@@ -71,6 +71,11 @@ for bit; timm's op list and level maps are restated from its published source.
         targets = targets.to(device, non_blocking=True)
         if mixup_fn is not None:
             samples, targets = mixup_fn(samples, targets)
+
+The MAE linear probe's input (Models/mae/main_linprobe.py:132-141) is `MAELinprobeTransform`: the same crop kernel on
+boxes drawn by util/crop.py's one-draw rule (`tf_rrc_boxes`, `RandomResizedCropFlip(sampler="tf")`), flip, Normalize.
+MoCo-v3's lincls train input (main_lincls.py:270-277) is `RandomResizedCropFlip(224, scale=(0.08, 1.0),
+interpolation="bilinear")` as it stands.
 """
 from __future__ import annotations
 
@@ -324,22 +329,58 @@ def rrc_boxes(u, Hs, Ws, scale=(0.2, 1.0), ratio=(3.0 / 4.0, 4.0 / 3.0)):
     return torch.where(ok.any(dim=1, keepdim=True), won, fallback).to(torch.int32)
 
 
+@functools.lru_cache(maxsize=64)
+def _log_ratio_f32(ratio):
+    """torch.log(torch.tensor(ratio)) of util/crop.py:28 — fp32 — as two Python floats (a host constant of `ratio`)"""
+    lr = torch.log(torch.tensor(ratio, dtype=torch.float32))
+    return float(lr[0]), float(lr[1])
+
+
+def tf_rrc_boxes(u, Hs, Ws, scale=(0.08, 1.0), ratio=(3.0 / 4.0, 4.0 / 3.0)):
+    """The MAE linear probe's RandomResizedCrop.get_params (reference Models/mae/util/crop.py:23-42, "for matching
+    TF/TPU implementation: no for-loop is used"): ONE draw, clamped to the image, where torchvision's rule (rrc_boxes)
+    retries up to ten times and falls back to a centred box.  A pure function of uniforms u [B, 4] in [0, 1): area
+    fraction, log-aspect, top, left.  The log-ratio bounds and the exp are fp32, as the reference's are; everything
+    else is float64 on u's device, vectorised, no host read-back.  round() is half-to-even, as Python's.  Returns int32
+    [B, 4] = (top, left, height, width).  The reference draws its scalars one at a time from torch's global generator,
+    so its random SEQUENCE is not reproduced; its distribution is.  (A side that rounds to 0 — an image of a few
+    pixels, where the reference's crop fails — is raised to 1.)"""
+    assert u.dim() == 2 and u.shape[1] == 4
+    u = u.to(torch.float64)
+    l0, l1 = _log_ratio_f32((float(ratio[0]), float(ratio[1])))
+    target = float(Hs * Ws) * (scale[0] + u[:, 0] * (scale[1] - scale[0]))
+    aspect = torch.exp((l0 + u[:, 1] * (l1 - l0)).to(torch.float32)).to(torch.float64)
+    w = torch.round(torch.sqrt(target * aspect)).clamp(1, Ws)
+    h = torch.round(torch.sqrt(target / aspect)).clamp(1, Hs)
+    top = torch.minimum(torch.floor(u[:, 2] * (Hs - h + 1)), Hs - h)     # torch.randint(0, height - h + 1)
+    left = torch.minimum(torch.floor(u[:, 3] * (Ws - w + 1)), Ws - w)
+    return torch.stack([top, left, h, w], dim=1).to(torch.int32)
+
+
 class RandomResizedCropFlip:
     """RandomResizedCrop(size, scale, ratio, interpolation) + RandomHorizontalFlip(flip_p) + ToTensor +
     Normalize(mean, std), drawn and computed on the bank's device.  __call__(bank, index) -> [B, 3, size, size]
-    fp32, or a list of `views` independently drawn such batches when views > 1."""
+    fp32, or a list of `views` independently drawn such batches when views > 1.  sampler: the box rule —
+    "torchvision" (rrc_boxes: ten tries and a fallback) or "tf" (tf_rrc_boxes: the MAE linear probe's one draw)."""
 
     def __init__(self, size=224, scale=(0.2, 1.0), ratio=(3.0 / 4.0, 4.0 / 3.0), interpolation="bicubic", flip_p=0.5,
-                 views=1, mean=IMAGENET_MEAN, std=IMAGENET_STD, generator=None):
+                 views=1, mean=IMAGENET_MEAN, std=IMAGENET_STD, generator=None, sampler="torchvision"):
         if interpolation not in ("bicubic", "bilinear"):
             raise ValueError(f"interpolation must be 'bicubic' or 'bilinear', got {interpolation!r}")
+        if sampler not in ("torchvision", "tf"):
+            raise ValueError(f"sampler must be 'torchvision' or 'tf', got {sampler!r}")
         if size % 4 or views < 1:
             raise ValueError("size must be a multiple of 4 and views >= 1")
         self.size, self.scale, self.ratio, self.interpolation = int(size), tuple(scale), tuple(ratio), interpolation
         self.flip_p, self.views, self.mean, self.std, self.generator = float(flip_p), int(views), tuple(mean), tuple(std), generator
+        self.sampler = sampler
 
     def draw(self, B, Hs, Ws, device):
         """one view's boxes int32 [B, 4] and flips uint8 [B] (advances the generator)"""
+        if self.sampler == "tf":
+            u = torch.rand(B, 4, dtype=torch.float64, device=device, generator=self.generator)
+            v = torch.rand(B, dtype=torch.float64, device=device, generator=self.generator)
+            return tf_rrc_boxes(u, Hs, Ws, self.scale, self.ratio), (v < self.flip_p).to(torch.uint8)
         u = torch.rand(B, 10, 4, dtype=torch.float64, device=device, generator=self.generator)
         v = torch.rand(B, dtype=torch.float64, device=device, generator=self.generator)
         return rrc_boxes(u, Hs, Ws, self.scale, self.ratio), (v < self.flip_p).to(torch.uint8)
@@ -937,6 +978,21 @@ class MAEFinetuneTransform:
             return ops.view_sample_u8(bank.images, index, self._eval_box.expand(B, 4).contiguous(), None, self.size,
                                       "bicubic", self.mean, self.std)
         return self.apply(bank, index, *self.draw(index.shape[0], Hs, Ws, index.device))
+
+
+class MAELinprobeTransform(RandomResizedCropFlip):
+    """transform_train of Models/mae/main_linprobe.py:132-136 for DeviceLoader: util/crop.py's RandomResizedCrop
+    (input_size, scale (0.08, 1), bicubic; the one-draw box rule, sampler="tf") + RandomHorizontalFlip + ToTensor +
+    Normalize — a weak augmentation, no RandAugment, no erasing.  `MAELinprobeTransform.eval(input_size)` is
+    transform_val (:137-141: Resize(256, bicubic) + CenterCrop(224)), which is MAEFinetuneTransform.eval."""
+
+    def __init__(self, input_size=224, scale=(0.08, 1.0), mean=IMAGENET_MEAN, std=IMAGENET_STD, generator=None):
+        super().__init__(input_size, scale=scale, interpolation="bicubic", mean=mean, std=std, generator=generator,
+                         sampler="tf")
+
+    @staticmethod
+    def eval(input_size=224, mean=IMAGENET_MEAN, std=IMAGENET_STD):
+        return MAEFinetuneTransform.eval(input_size, mean=mean, std=std)
 
 
 # ------------------------------------------------------------------------------------------------

@@ -12,6 +12,12 @@ by an exact radix select.  The accumulators `SegmentationScores`, `Classificatio
 state on the device and synchronise only in `.compute()`.  CPU tensors, or SSL4GIE_FUSED_METRICS=0, take the torch
 formulation below, which restates the reference line by line and is the parity reference of the kernels.
 
+The linear-probe drivers score with `accuracy(output, target, topk=(1, 5))` and one `.item()` per meter per batch
+(`Models/moco_v3/main_lincls.py:365-373,506-520`, `Models/mae/engine_finetune.py:119-124`): `accuracy` here has that
+signature and returns device tensors, and `TopKAccuracy` adds hits per k, rows and the cross-entropy sum up on the
+device over a loader (csrc/probe_ops.hip) with one read-back.  Equal logits are ordered by lower index first — the rule
+of the argmax above — where `torch.topk` leaves ties open.
+
 The detection drivers (`Object_detection/train_detection.py:113-151`, `eval_detection.py:21-44`) score with torchmetrics'
 `MeanAveragePrecision()`; the class of that name here takes the same `update(preds, target)` / `compute()` calls, keeps
 the detections of a loader on the device and runs COCO's evaluation in the kernels of csrc/det_map_ops.hip.
@@ -266,6 +272,109 @@ class ClassificationScores:
             return {**{k: float("nan") for k in self.names}, "rejected": 0}
         s = self.scores().cpu()
         return {**{k: float(s[i]) for i, k in enumerate(self.names)}, "rejected": int(self.conf[-1])}
+
+
+# ------------------------------------------------------------------ top-k accuracy (the linear-probe drivers)
+def _check_topk(topk, C):
+    ks = [int(k) for k in topk]
+    if not 1 <= len(set(ks)) <= 8 or min(ks) < 1:
+        raise ValueError(f"topk must hold 1 to 8 distinct values >= 1, got {tuple(topk)}")
+    if max(ks) > C:
+        raise ValueError(f"topk={tuple(topk)} asks for more than the C = {C} classes of the logits")
+    return ks
+
+
+def topk_ranks_torch(logits, target):
+    """the rank rule of ssl4gie_topk_update in torch ops: (rank int64 [B], ok bool [B], loss fp32 [B]).  rank = the
+    number of columns ordered above the target's logit — equal values by lower index first, a NaN above every number,
+    NaNs among themselves by lower index first (`torch.topk` leaves the order of ties open); ok = target in [0, C);
+    loss = the row's cross-entropy in fp32.  Rows that are not ok hold rank -1 and loss 0."""
+    x = logits.float()
+    B, C = x.shape
+    ok = (target >= 0) & (target < C)
+    t = target.clamp(0, C - 1).view(B, 1)
+    xt = x.gather(1, t)
+    xnan, tnan = x.isnan(), xt.isnan()
+    over = ~tnan & (xnan | (x > xt))
+    tie = torch.where(tnan, xnan, x == xt)
+    col = torch.arange(C, device=x.device).view(1, C)
+    rank = (over | (tie & (col < t))).sum(1)
+    loss = F.cross_entropy(x, t.view(B), reduction="none")
+    return torch.where(ok, rank, torch.full_like(rank, -1)), ok, torch.where(ok, loss, torch.zeros_like(loss))
+
+
+def _topk_state(nk, device):
+    """int64 [nk + 3] in ONE buffer: hits per k, rows counted, rows rejected, and the fp64 loss sum's bits"""
+    state = torch.zeros(nk + 3, dtype=torch.int64, device=device)
+    return state, state[:nk + 2], state[nk + 2:].view(torch.float64)
+
+
+def _topk_update(acc, loss_sum, logits, target, ks, workspace=None):
+    if logits.dim() != 2 or target.dim() != 1 or logits.shape[0] != target.shape[0]:
+        raise ValueError(f"logits [B, C] and target [B] expected, got {tuple(logits.shape)}, {tuple(target.shape)}")
+    if _fused_ok(logits, target) and logits.shape[0]:
+        from . import ops
+        if logits.dtype not in (torch.float32, torch.bfloat16):
+            logits = logits.float()
+        ops.topk_update(acc, loss_sum, logits, target.long().contiguous(), ks, workspace=workspace)
+        return
+    rank, ok, loss = topk_ranks_torch(logits, target.long())
+    hits = [(ok & (rank < k)).sum() for k in ks]
+    acc += torch.stack(hits + [ok.sum(), (~ok).sum()])
+    loss_sum += loss.double().sum()
+
+
+@torch.no_grad()
+def accuracy(output, target, topk=(1,)):
+    """the drivers' `accuracy(output, target, topk=(1, 5))` (Models/moco_v3/main_lincls.py:506-520; timm's, imported at
+    Models/mae/engine_finetune.py:19): the precision@k of one batch in percent, a list of fp32 [1] tensors on the
+    logits' device — nothing is read back.  Ties are ordered by lower index first where `topk` leaves them open."""
+    ks = _check_topk(topk, output.shape[1])
+    order = sorted(set(ks))
+    _, acc, loss_sum = _topk_state(len(order), output.device)
+    _topk_update(acc, loss_sum, output, target, order)
+    scale = 100.0 / max(1, target.shape[0])
+    return [acc[order.index(k):order.index(k) + 1].float() * scale for k in ks]
+
+
+class TopKAccuracy:
+    """acc@k and the mean cross-entropy over a whole loader from device accumulators, instead of the drivers'
+    `accuracy(...)` + one `.item()` per meter per batch (main_lincls.py:365-368, engine_finetune.py:119-124).
+    `update(logits [B, C], target [B])` adds a batch (fp32 or bf16 logits, any row stride); `compute()` is the ONE
+    read-back: {"acc1": .., "acc5": .., "loss": .., "n": .., "rejected": ..}, accuracies in percent of the n rows
+    counted; a target outside [0, C) is counted as rejected and adds to nothing else."""
+
+    def __init__(self, topk=(1, 5)):
+        ks = [int(k) for k in topk]
+        if not 1 <= len(ks) <= 8 or ks[0] < 1 or any(b <= a for a, b in zip(ks, ks[1:])):
+            raise ValueError(f"topk must hold 1 to 8 strictly ascending values >= 1, got {tuple(topk)}")
+        self.topk = tuple(ks)
+        self.state = self._acc = self._loss = self._ws = None
+
+    def reset(self):
+        self.state = self._acc = self._loss = None
+
+    def update(self, logits, target):
+        _check_topk(self.topk, logits.shape[1])
+        if self.state is None:
+            self.state, self._acc, self._loss = _topk_state(len(self.topk), logits.device)
+        if _fused_ok(logits, target):  # the row-loss workspace is kept across batches
+            need = _lib.load().ssl4gie_topk_workspace_bytes(logits.shape[0])
+            if self._ws is None or self._ws.device != logits.device or self._ws.numel() < need:
+                from . import ops
+                self._ws = ops.topk_workspace(logits.shape[0], logits.device)
+        _topk_update(self._acc, self._loss, logits, target, list(self.topk), self._ws)
+
+    def compute(self):
+        names = [f"acc{k}" for k in self.topk]
+        if self.state is None:
+            return {**{k: float("nan") for k in names}, "loss": float("nan"), "n": 0, "rejected": 0}
+        host = self.state.cpu()
+        nk = len(self.topk)
+        n, rejected = int(host[nk]), int(host[nk + 1])
+        loss_sum = float(host[nk + 2:].view(torch.float64)[0])
+        out = {k: (100.0 * int(host[i]) / n if n else float("nan")) for i, k in enumerate(names)}
+        return {**out, "loss": loss_sum / n if n else float("nan"), "n": n, "rejected": rejected}
 
 
 # ------------------------------------------------------------------ depth

@@ -1820,6 +1820,48 @@ def confusion_scores(conf, smooth):
     return scores
 
 
+def topk_workspace(B, device):
+    return torch.empty(max(1, _lib.load().ssl4gie_topk_workspace_bytes(int(B))), dtype=torch.uint8, device=device)
+
+
+def topk_update(acc, loss_sum, logits, target, topk, rank=None, row_loss=None, workspace=None):
+    """acc (int64 [len(topk) + 2]: hits per k, rows counted, rows rejected) and loss_sum (fp64 [1]: summed cross-entropy)
+    += one batch.  logits fp32 / bf16 [B, C], unit stride along C, any row stride >= C; target int64 [B]; topk strictly
+    ascending, each in [1, C].  rank (int32 [B]) / row_loss (fp32 [B]) are overwritten when given.  The rank of a row is
+    the number of columns ordered above the target's logit, equal values by lower index first, a NaN above every number."""
+    _dev(acc, loss_sum, target, rank, row_loss)
+    _same_device(acc, loss_sum, logits, target, rank, row_loss)
+    if not logits.is_cuda:
+        raise RuntimeError("ssl4gie_amd ops need tensors on the HIP device (no CPU fallback)")
+    if logits.dim() != 2 or target.dim() != 1 or target.dtype != torch.int64 or logits.shape[0] != target.shape[0]:
+        raise ValueError(f"topk_update needs logits [B, C] and int64 target [B], got {tuple(logits.shape)}, "
+                         f"{tuple(target.shape)} {target.dtype}")
+    B, Cn = logits.shape
+    ks = [int(k) for k in topk]
+    if not 1 <= len(ks) <= 8 or any(b <= a for a, b in zip(ks, ks[1:])):
+        raise ValueError(f"topk must hold 1 to 8 strictly ascending values, got {tuple(topk)}")
+    if ks[0] < 1 or ks[-1] > Cn:
+        raise ValueError(f"topk={tuple(topk)} needs every k in [1, C = {Cn}]")
+    if acc.dtype != torch.int64 or acc.numel() != len(ks) + 2 or loss_sum.dtype != torch.float64 or loss_sum.numel() != 1:
+        raise ValueError("acc must be int64 [len(topk) + 2] and loss_sum fp64 [1]")
+    if (rank is not None and (rank.dtype != torch.int32 or rank.numel() != B)) or \
+            (row_loss is not None and (row_loss.dtype != torch.float32 or row_loss.numel() != B)):
+        raise ValueError(f"rank must be int32 [{B}] and row_loss fp32 [{B}]")
+    if B == 0:
+        return acc
+    if logits.stride(1) != 1 or (B > 1 and logits.stride(0) < Cn):
+        logits = logits.contiguous()
+    ld = logits.stride(0) if B > 1 else Cn
+    L = _lib.load()
+    nbytes = L.ssl4gie_topk_workspace_bytes(B)
+    if workspace is None or workspace.numel() < nbytes or workspace.device != logits.device:
+        workspace = torch.empty(nbytes, dtype=torch.uint8, device=logits.device)
+    _lib.check(L.ssl4gie_topk_update(ptr(logits), code(logits.dtype), ld, ptr(target), (C.c_int * len(ks))(*ks), len(ks),
+                                     ptr(acc), ptr(loss_sum), ptr(rank), ptr(row_loss), B, Cn, ptr(workspace), stream()),
+               "topk_update")
+    return acc
+
+
 def lower_median(x):
     """0-dim fp32: the element of rank (n - 1) // 2 of the non-negative fp32 values x (torch.median's lower median),
     by an exact radix select; NaN for an empty x.  x is not modified."""

@@ -449,3 +449,139 @@ class ArenaLARS(_ArenaOptimizer):
                                         ptr(mat), S, self.momentum, self.trust, ptr(self._ws), a.numel,
                                         stream()), "lars_arena")
         bump_weights_epoch(touched=[p for g in self.param_groups for p in g["params"]])
+
+
+class _RangedArenaOptimizer(_ArenaOptimizer):
+    """An arena optimizer whose parameters are a small part of the arena (a linear probe's head: 0.77 M of ViT-B's
+    86 M elements): state and launches cover only the HULL [lo, hi) of its parameters' segments — the kernels get
+    pointers offset by `lo`, `hi - lo` elements and a segment table rebased to the hull; any other parameter inside
+    the hull is inactive through seg_lr < 0, as a frozen one is.  `model` may be None: the arena is then found from the
+    parameters (engine.arena_of) at step(), because a model builds its arena lazily."""
+
+    _state_names = ()
+
+    def __init__(self, model, params, defaults):
+        super().__init__(model, params, defaults)
+        self._range_key = self._range = None
+
+    def _arena(self):
+        from .engine import arena_of
+        from .parallel import before_optimizer_step
+        before_optimizer_step()
+        own = [p for g in self.param_groups for p in g["params"]]
+        a = arena_of(own)   # pointer checks on the own parameters only: no walk over the model's parameters per step
+        if a is None and self.model is not None:
+            return super()._arena()   # not built yet, or the parameters moved: the model validates / rebuilds it
+        if a is None:
+            raise RuntimeError(f"{type(self).__name__}: its parameters do not live in one live engine arena (run a "
+                               "forward on the device first: the arena is built lazily)")
+        _adopt_grads(a, own)
+        return a
+
+    def _ranged_tables(self, a):
+        """-> (start - lo [S + 1], lr [S], wd [S], mat [S], S, lo, hi) over the hull's S segments: slices of the
+        whole-arena tables (a learning-rate schedule still only rewrites those), the rebased starts built once per
+        layout on the device"""
+        start, lr, wd, mat, _ = self._build_tables(a)
+        if self._range_key != self._tables_key:
+            own = {id(p) for g in self.param_groups for p in g["params"]}
+            idx = [i for i, p in enumerate(a.params) if id(p) in own]
+            i0, i1 = min(idx), max(idx) + 1
+            lo = a.offsets[i0]
+            hi = a.offsets[i1] if i1 < len(a.params) else a.numel
+            self._range = (i0, i1, lo, hi, (start[i0:i1 + 1] - lo).contiguous())
+            self._range_key = self._tables_key
+        i0, i1, lo, hi, rstart = self._range
+        return rstart, lr[i0:i1], wd[i0:i1], mat[i0:i1], i1 - i0, lo, hi
+
+    def _state(self, name, a, lo, hi):
+        """the hull-sized fp32 state buffer `name` on the arena's device (zeros when fresh)"""
+        v = getattr(self, name)
+        if v is None:
+            v = torch.zeros(hi - lo, dtype=torch.float32, device=a.data.device)
+        elif v.numel() != hi - lo:
+            raise ValueError(f"{type(self).__name__}.{name} holds {v.numel()} elements, the hull of its parameters "
+                             f"{hi - lo}: the state was saved for a different arena layout")
+        elif v.device != a.data.device:
+            v = v.to(a.data.device)
+        setattr(self, name, v)
+        return v
+
+    def _state_buffers(self):
+        return {k: getattr(self, k) for k in self._state_names}
+
+    def load_state_dict(self, sd):
+        """_ArenaOptimizer's format with hull-sized buffers; their size is checked against the hull at the next
+        step() (the arena may not exist yet)"""
+        assert sd["kind"] == type(self).__name__, (sd["kind"], type(self).__name__)
+        assert len(sd["param_groups"]) == len(self.param_groups)
+        for g, saved in zip(self.param_groups, sd["param_groups"]):
+            assert saved["n_params"] == len(g["params"]), "parameter groups differ from the saved ones"
+            g.update({k: v for k, v in saved.items() if k != "n_params"})
+        for k in self._state_names:
+            v = sd["state"].get(k)
+            setattr(self, k, None if v is None else v.detach().to(torch.float32).clone())
+        self.step_count = int(sd["step_count"])
+        self._hyper = None
+
+
+class ArenaSGD(_RangedArenaOptimizer):
+    """`ArenaSGD(model, params_or_groups, lr, momentum=0, weight_decay=0)`: torch.optim.SGD as the linear-probe driver
+    builds it (`Models/moco_v3/main_lincls.py:236-238`: momentum 0.9, weight decay 0 over fc's two parameters) in ONE
+    launch of ssl4gie_sgd_arena over the hull of its parameters: d = g + wd p; buf = momentum buf + d; p -= lr buf.
+    The momentum buffer starts at zero, which reproduces torch's first step (buf = d).  Nesterov momentum and
+    dampening are not built."""
+
+    _state_names = ("buf",)
+
+    def __init__(self, model, params, lr, momentum=0.0, weight_decay=0.0, dampening=0.0, nesterov=False):
+        if dampening != 0 or nesterov:
+            raise NotImplementedError("ArenaSGD: dampening != 0 and nesterov=True are not built (DESIGN.md §8)")
+        if lr < 0 or momentum < 0 or weight_decay < 0:
+            raise ValueError("ArenaSGD: lr, momentum and weight_decay must be >= 0")
+        super().__init__(model, params, dict(lr=lr, weight_decay=weight_decay))
+        self.momentum = float(momentum)
+        self.buf = None
+
+    @torch.no_grad()
+    def step(self):
+        a = self._arena()
+        start, lr, wd, _, S, lo, hi = self._ranged_tables(a)
+        buf = self._state("buf", a, lo, hi)
+        self.step_count += 1
+        _lib.check(_lib.load().ssl4gie_sgd_arena(ptr(a.data[lo:hi]), ptr(a.grad[lo:hi]), ptr(buf), ptr(start), ptr(lr),
+                                                 ptr(wd), S, self.momentum, hi - lo, stream()), "sgd_arena")
+        bump_weights_epoch(touched=[p for g in self.param_groups for p in g["params"]])
+
+
+class RangedLARS(_RangedArenaOptimizer):
+    """ArenaLARS's update (the same three launches of ssl4gie_lars_arena) over the hull of its parameters only: a
+    hull-sized momentum buffer and workspace instead of arena-sized ones.  `Models/mae/util/lars.py` gives it the
+    reference's signature."""
+
+    _state_names = ("mu",)
+
+    def __init__(self, model, params, lr=0.0, weight_decay=0.0, momentum=0.9, trust_coefficient=0.001):
+        super().__init__(model, params, dict(lr=lr, weight_decay=weight_decay, momentum=momentum,
+                                             trust_coefficient=trust_coefficient))
+        if any(g["momentum"] != self.param_groups[0]["momentum"] or
+               g["trust_coefficient"] != self.param_groups[0]["trust_coefficient"] for g in self.param_groups):
+            raise NotImplementedError("LARS: momentum and trust_coefficient must be the same in every group")
+        self.mu = None
+        self._ws = None
+
+    @torch.no_grad()
+    def step(self):
+        a = self._arena()
+        start, lr, wd, mat, S, lo, hi = self._ranged_tables(a)
+        mu = self._state("mu", a, lo, hi)
+        L = _lib.load()
+        nbytes = L.ssl4gie_lars_workspace_bytes(S)
+        if self._ws is None or self._ws.numel() < nbytes or self._ws.device != a.data.device:
+            self._ws = torch.empty(nbytes, dtype=torch.uint8, device=a.data.device)
+        self.step_count += 1
+        g0 = self.param_groups[0]
+        _lib.check(L.ssl4gie_lars_arena(ptr(a.data[lo:hi]), ptr(a.grad[lo:hi]), ptr(mu), ptr(start), ptr(lr), ptr(wd),
+                                        ptr(mat), S, float(g0["momentum"]), float(g0["trust_coefficient"]),
+                                        ptr(self._ws), hi - lo, stream()), "lars_arena")
+        bump_weights_epoch(touched=[p for g in self.param_groups for p in g["params"]])
