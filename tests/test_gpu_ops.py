@@ -346,6 +346,7 @@ def test_attention_bf16_one_hot_exact():
 
 # ------------------------------------------------------------------ casts
 def test_casts():
+    """every shape, dtype and edge of this kernel family, per element: tests/test_gpu_mae_kernels.py"""
     from ssl4gie_amd import ops
     x = torch.randn(768, 3072, generator=G(1))
     assert torch.equal(ops.cast(x.to(DEV), BF).cpu(), x.to(BF))
@@ -360,6 +361,7 @@ def test_casts():
 
 # ------------------------------------------------------------------ MAE glue (integer paths exact)
 def test_mask_argsort_bit_exact_vs_reference_fixture():
+    """every shape, dtype and edge of this kernel family, per element: tests/test_gpu_mae_kernels.py"""
     from ssl4gie_amd import ops
     g = load_golden("g1_masking.npz")
     s, r, m = ops.mask_argsort(torch.from_numpy(g["noise"]).to(DEV), 49)
@@ -376,6 +378,7 @@ def test_mask_argsort_bit_exact_vs_reference_fixture():
 
 
 def test_patch_gather_exact():
+    """every shape, dtype and edge of this kernel family, per element: tests/test_gpu_mae_kernels.py"""
     from ssl4gie_amd import ops
     g = load_golden("g2_patchify.npz")
     imgs = torch.from_numpy(g["imgs"])
@@ -391,6 +394,7 @@ def test_patch_gather_exact():
 
 
 def test_token_assembly_roundtrip():
+    """every shape, dtype and edge of this kernel family, per element: tests/test_gpu_mae_kernels.py"""
     from ssl4gie_amd import ops
     B, L, keep, D = 3, 16, 4, 128
     noise = torch.rand(B, L, generator=G(1))
@@ -436,6 +440,7 @@ def test_token_assembly_roundtrip():
 
 @pytest.mark.parametrize("norm_pix", [False, True])
 def test_mae_loss_and_gradient(norm_pix):
+    """every shape, dtype and edge of this kernel family, per element: tests/test_gpu_mae_kernels.py"""
     from oracle import mae_ref
     from ssl4gie_amd import ops
     B, p = 3, 16
@@ -496,6 +501,7 @@ def test_block_stack_fwd_bwd(dt, N, D, H):
 
 
 def test_normalize_u8_matches_totensor_normalize():
+    """every shape, dtype and edge of this kernel family, per element: tests/test_gpu_mae_kernels.py"""
     from ssl4gie_amd import ops
     img = torch.randint(0, 256, (3, 30, 28, 3), generator=G(11), dtype=torch.uint8)
     out = ops.normalize_u8(img.to(DEV)).cpu()
