@@ -265,6 +265,9 @@ def test_cross_entropy_target_out_of_range_is_nan_and_stays_in_bounds():
 LAMBD = 0.0051
 BT_DIMS = [1, 200, 256, 1000, 129]   # 129: odd and several tiles, the element-wise path of the operand kernel
 BT_SCALES = [1.0 / 512, 3.0 / 1024, 1.0, 1.0 / 512, 3.0 / 1024]
+# the operand check also beyond 1024 (the width of the projector the method is used with): odd, and a multiple of 4
+BT_GRAD_DIMS = BT_DIMS + [1025, 1028]
+BT_GRAD_SCALES = BT_SCALES + [1.0 / 512, 3.0 / 1024]
 
 
 @functools.lru_cache(maxsize=None)
@@ -292,7 +295,7 @@ def test_bt_loss_vs_fp64(D):
 
 
 @pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
-@pytest.mark.parametrize("D,scale", list(zip(BT_DIMS, BT_SCALES)))
+@pytest.mark.parametrize("D,scale", list(zip(BT_GRAD_DIMS, BT_GRAD_SCALES)))
 def test_bt_grad_operands_equal_the_torch_ops_bit_for_bit(D, scale, dtype):
     from ssl4gie_amd import ops
     from ssl4gie_amd.Models.barlow_twins import cross_corr_loss_terms
