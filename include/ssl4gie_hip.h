@@ -14,7 +14,10 @@
  *   - returns 0 on success, SSL4GIE_EARG (1000) for an invalid argument, otherwise a hipError_t;
  *   - callable from any host thread; the only mutable process-wide settings are the execution
  *     options ssl4gie_set_wgrad_stream / ssl4gie_set_compute_cus and the profiler;
- *   - ssl4gie_abi_version() = 12 (ssl4gie_view_sample_u8, after it ssl4gie_color_augment{_workspace_bytes,}, and after those ssl4gie_color_augment_ft / ssl4gie_paired_warp, joined revision 12
+ *   - ssl4gie_abi_version() = 13 (revision 13 LOST ssl4gie_adamw_arena_lp, ssl4gie_adamw_arena_range and ssl4gie_adamw_arena_range_ctl and CHANGED the
+ *     signature of ssl4gie_adamw_arena, which now is the one AdamW step: a range of the arena, the optional bf16 copy, and the step count either from the
+ *     host (ctl == NULL) or from a device counter behind the control block (ctl != NULL) — the same two kernels and launches as before; ssl4gie_sgd_arena
+ *     is unchanged (its source moved from probe_ops.hip to optim_ops.hip); 12: ssl4gie_view_sample_u8, after it ssl4gie_color_augment{_workspace_bytes,}, and after those ssl4gie_color_augment_ft / ssl4gie_paired_warp, joined revision 12
  *     without a new number: added symbols, nothing existing changed, so a caller built against the earlier 12 runs unchanged; the evaluation
  *     metrics ssl4gie_seg_{counts,scores} / ssl4gie_confusion_{update,scores} / ssl4gie_lower_median_{workspace_bytes,f32} / ssl4gie_depth_eval{_workspace_bytes,}
  *     joined it the same way, and so did the detection input entry points ssl4gie_det_color{_workspace_bytes,} / ssl4gie_det_geometry / ssl4gie_det_boxes and the
@@ -630,27 +633,20 @@ int ssl4gie_avgpool_bwd(const float* dy, void* dx, int dtype, int B, int HW, int
  * One parameter arena = S segments (one per parameter, 64-element aligned; padding stays zero).
  * Device tables: seg_start [S+1] int64 element offsets, seg_lr [S] (< 0: skip the segment: frozen or
  * without a gradient this step), seg_wd [S], seg_mat [S] (LARS: 1 for p.ndim > 1).
- * adamw_arena: torch.optim.AdamW's update (main_pretrain.py:179-180, train_depth.py:280), `step` =
- *   1-based step count for the bias corrections; m / v are the flat moment buffers.
  * lars_arena: Models/moco_v3/moco/optimizer.py:18-43: matrices dp = (g + wd p) trust |p|/|dp|
- *   (1 where a norm is 0), vectors dp = g; mu = momentum mu + dp; p -= lr mu. */
-int ssl4gie_adamw_arena(float* p, const float* g, float* m, float* v, const long long* seg_start,
-                        const float* seg_lr, const float* seg_wd, int S, float beta1, float beta2,
-                        float eps, int step, long long n, void* stream);
-/* the same step, also writing the bf16 operand copy of every UPDATED element into lp_bf16 [n] (the
- * flat shadow arena the GEMM operands are views of; skipped segments are left as they are) — saves
- * the separate cast pass over the arena.  lp_bf16 = NULL: as ssl4gie_adamw_arena. */
-int ssl4gie_adamw_arena_lp(float* p, const float* g, float* m, float* v, const long long* seg_start,
-                           const float* seg_lr, const float* seg_wd, int S, float beta1, float beta2,
-                           float eps, int step, long long n, void* lp_bf16, void* stream);
-/* the same step restricted to the arena elements [lo, hi) (multiples of 4; whole segments in
- * practice): lets the update of a transformer block's parameters be enqueued on a side stream as
- * soon as that block's backward is, behind the rest of the backward pass (optim.ArenaAdamW,
- * overlap_backward).  The union of the ranges of one step must cover [0, n) exactly once. */
-int ssl4gie_adamw_arena_range(float* p, const float* g, float* m, float* v, const long long* seg_start,
-                              const float* seg_lr, const float* seg_wd, int S, float beta1, float beta2,
-                              float eps, int step, long long lo, long long hi, void* lp_bf16,
-                              void* stream);
+ *   (1 where a norm is 0), vectors dp = g; mu = momentum mu + dp; p -= lr mu.
+ * sgd_arena: torch.optim.SGD(momentum, weight_decay) with dampening 0 and no Nesterov (main_lincls.py:236-238):
+ *   d = g + wd p; buf = momentum buf + d; p -= lr buf.  A zero buf reproduces torch's first step (buf = d).
+ *   A skipped segment's p and buf (its padding included) stay bit-unchanged; an active segment's zero padding
+ *   stays zero (g, p and buf are all zero there).
+ * lars_arena and sgd_arena take the n elements (n % 4 == 0) behind the pointers they are given (sgd_arena: 16-byte
+ * aligned): a caller may hand them a sub-range of the arena with seg_start rebased to it. */
+size_t ssl4gie_lars_workspace_bytes(int S);
+int ssl4gie_lars_arena(float* p, const float* g, float* mu, const long long* seg_start,
+                       const float* seg_lr, const float* seg_wd, const float* seg_mat, int S,
+                       float momentum, float trust, float* workspace, long long n, void* stream);
+int ssl4gie_sgd_arena(float* p, const float* g, float* buf, const long long* seg_start, const float* seg_lr,
+                      const float* seg_wd, int S, float momentum, long long n, void* stream);
 /* ---- the reference's scaler object over the arena (Models/mae/util/misc.py:251-292,
  * NativeScalerWithGradNormCount: unscale_ -> get_grad_norm_ / clip_grad_norm_ -> scaler.step; driven from
  * Models/mae/engine_pretrain.py:39-69 and engine_finetune.py:66 / main_finetune.py --clip_grad).
@@ -674,26 +670,33 @@ int ssl4gie_grad_norm_arena(const float* g, const long long* seg_start, const fl
                             void* stream);
 int ssl4gie_grad_scale_arena(float* g, const long long* seg_start, const float* seg_mask, int S,
                              const float* ctl, long long n, void* stream);
-/* ssl4gie_adamw_arena_range with the control block (misc.py:267 `self._scaler.step(optimizer)` after a
- * clip): the gradient is ctl[1] * g (g itself is left as it is), and with skip_nonfinite != 0 NOTHING is
- * written while ctl[2] is set — not p, m, v, nor lp_bf16 — GradScaler.step's skip.  torch does not call
- * optimizer.step() for a skipped update, so its bias-correction step does not advance either; the host
- * cannot know without synchronising, so the count of APPLIED updates lives on the device: *applied (one
- * int, caller-owned, 0 for a fresh optimizer) is read by the kernel (step = *applied + 1), and with
- * advance != 0 a one-thread launch behind it adds 1 unless the update was skipped.  Pass advance on the
- * last range of a step only. */
-int ssl4gie_adamw_arena_range_ctl(float* p, const float* g, float* m, float* v, const long long* seg_start,
-                                  const float* seg_lr, const float* seg_wd, int S, float beta1, float beta2,
-                                  float eps, int* applied, long long lo, long long hi, void* lp_bf16,
-                                  const float* ctl, int skip_nonfinite, int advance, void* stream);
-size_t ssl4gie_lars_workspace_bytes(int S);
-int ssl4gie_lars_arena(float* p, const float* g, float* mu, const long long* seg_start,
-                       const float* seg_lr, const float* seg_wd, const float* seg_mat, int S,
-                       float momentum, float trust, float* workspace, long long n, void* stream);
+/* adamw_arena: torch.optim.AdamW's update (main_pretrain.py:179-180, train_depth.py:280) of the arena elements
+ * [lo, hi) (multiples of 4, hi >= lo; whole segments in practice; pointers and seg_start are the whole arena's).
+ * m / v are the flat moment buffers.  lp_bf16 (may be NULL): the bf16 operand copy of every UPDATED element is
+ * written there too (the flat shadow arena the GEMM operands are views of; skipped segments are left as they
+ * are), which saves the separate cast pass.  Ranges let the update of a transformer block's parameters be
+ * enqueued on a side stream as soon as that block's backward is (optim.ArenaAdamW, overlap_backward); the
+ * ranges of one step must cover the arena exactly once.  hi == lo launches no update.
+ *   ctl == NULL, host-counted: `step` (> 0) is the 1-based step count of the bias corrections; applied must
+ *     be NULL and skip_nonfinite and advance 0.
+ *   ctl != NULL, device-counted (misc.py:267 `self._scaler.step(optimizer)` after a clip): the gradient is
+ *     ctl[1] * g (g itself is left as it is), and with skip_nonfinite != 0 NOTHING is written while ctl[2] is
+ *     set — not p, m, v, nor lp_bf16 — GradScaler.step's skip.  torch does not call optimizer.step() for a
+ *     skipped update, so its bias-correction step does not advance either; the host cannot know without
+ *     synchronising, so the count of APPLIED updates lives on the device: *applied (one int, caller-owned, not
+ *     NULL, 0 for a fresh optimizer) is read by the kernel (step = *applied + 1; `step` is ignored), and with
+ *     advance != 0 a one-thread launch behind it adds 1 unless the update was skipped (also when hi == lo).
+ *     Pass advance on the last range of a step only.
+ * Any other combination returns SSL4GIE_EARG before anything is launched. */
+int ssl4gie_adamw_arena(float* p, const float* g, float* m, float* v, const long long* seg_start,
+                        const float* seg_lr, const float* seg_wd, int S, float beta1, float beta2, float eps,
+                        int step, int* applied, long long lo, long long hi, void* lp_bf16, const float* ctl,
+                        int skip_nonfinite, int advance, void* stream);
 
-/* ---------------------------------------------------------------- linear probe: scoring and the head's SGD step
+/* ---------------------------------------------------------------- linear probe: scoring
  * (csrc/probe_ops.hip; joined ABI 12 as additions).  The frozen trunk's forward is the bulk of a probe step
- * (Models/mae/main_linprobe.py, Models/moco_v3/main_lincls.py) and is not touched; these are the device code around it.
+ * (Models/mae/main_linprobe.py, Models/moco_v3/main_lincls.py) and is not touched; the head's SGD step is
+ * ssl4gie_sgd_arena above.
  *
  * topk_update  accuracy(output, target, topk) (main_lincls.py:506-520; timm's accuracy at Models/mae/engine_finetune.py:
  *              19,119-124) and the criterion's value for one batch, added into caller-owned device accumulators so
@@ -714,18 +717,11 @@ int ssl4gie_lars_arena(float* p, const float* g, float* mu, const long long* seg
  *              accepted and a row's loss does not depend on its alignment.  The row losses are added in fp64 in a fixed
  *              order (rows in index order over 256 threads, then a tree), no floating-point atomics: the same inputs
  *              give the same bits from run to run and for any grid.  The counts are integer atomics.
- *              workspace: ssl4gie_topk_workspace_bytes(B) bytes (0 for B <= 0), 4-byte aligned.  C <= 2^30.
- * sgd_arena    torch.optim.SGD(momentum, weight_decay) with dampening 0 and no Nesterov (main_lincls.py:236-238) over the
- *              segment tables above: d = g + wd p; buf = momentum buf + d; p -= lr buf.  A zero buf reproduces torch's
- *              first step (buf = d).  A skipped segment's p and buf (its padding included) stay bit-unchanged; an
- *              active segment's zero padding stays zero (g, p and buf are all zero there).  It takes the n elements (n % 4 == 0) behind the pointers it is
- *              given (16-byte aligned): a caller may hand it a sub-range of the arena with seg_start rebased to it. */
+ *              workspace: ssl4gie_topk_workspace_bytes(B) bytes (0 for B <= 0), 4-byte aligned.  C <= 2^30. */
 size_t ssl4gie_topk_workspace_bytes(int B);
 int ssl4gie_topk_update(const void* logits, int dtype, long long ld, const long long* target, const int* ks, int nk,
                         long long* acc, double* loss_sum, int* rank, float* row_loss, int B, int C, void* workspace,
                         void* stream);
-int ssl4gie_sgd_arena(float* p, const float* g, float* buf, const long long* seg_start, const float* seg_lr,
-                      const float* seg_wd, int S, float momentum, long long n, void* stream);
 
 /* ---------------------------------------------------------------- input pipeline
  * transforms.ToTensor() + transforms.Normalize(mean, std) (Depth_estimation/Data/dataloaders.py:

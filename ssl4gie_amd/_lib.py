@@ -12,7 +12,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libssl4gie_hip.so")
 # the one copy of the ABI revision on the Python side: build(), the tests and load() compare the
 # library's ssl4gie_abi_version() with it (include/ssl4gie_hip.h documents the history)
-ABI_VERSION = 12
+ABI_VERSION = 13
 
 PROF_KINDS = 7  # SSL4GIE_PROF_KINDS: entries of the launch profiler's arrays
 
@@ -149,11 +149,8 @@ PROTOTYPES = {
     "ssl4gie_maxpool3x3s2_bwd": (i32, [vp, vp, vp, i32, i32, i32, i32, i32, vp]),
     "ssl4gie_avgpool_fwd": (i32, [vp, vp, i32, i32, i32, i32, vp]),
     "ssl4gie_avgpool_bwd": (i32, [vp, vp, i32, i32, i32, i32, vp]),
-    "ssl4gie_adamw_arena": (i32, [vp, vp, vp, vp, vp, vp, vp, i32, f32, f32, f32, i32, i64, vp]),
-    "ssl4gie_adamw_arena_lp": (i32, [vp, vp, vp, vp, vp, vp, vp, i32, f32, f32, f32, i32, i64, vp, vp]),
-    "ssl4gie_adamw_arena_range": (i32, [vp, vp, vp, vp, vp, vp, vp, i32, f32, f32, f32, i32, i64, i64, vp, vp]),
-    "ssl4gie_adamw_arena_range_ctl": (i32, [vp, vp, vp, vp, vp, vp, vp, i32, f32, f32, f32, vp, i64, i64, vp, vp,
-                                            i32, i32, vp]),
+    "ssl4gie_adamw_arena": (i32, [vp, vp, vp, vp, vp, vp, vp, i32, f32, f32, f32, i32, vp, i64, i64, vp, vp, i32, i32,
+                                  vp]),
     "ssl4gie_grad_norm_workspace_bytes": (sz, []),
     "ssl4gie_grad_norm_arena": (i32, [vp, vp, vp, i32, f32, f32, vp, vp, i64, vp]),
     "ssl4gie_grad_scale_arena": (i32, [vp, vp, vp, i32, vp, i64, vp]),

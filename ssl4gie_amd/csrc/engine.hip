@@ -20,7 +20,7 @@
 #include "prof.h"
 #include "internal.h"
 
-extern "C" int ssl4gie_abi_version(void) { return 12; }
+extern "C" int ssl4gie_abi_version(void) { return 13; }
 
 namespace { extern int g_wgrad_stream; }
 // 1: block weight gradients on the library's side stream (default), 0: everything on the caller's

@@ -1,7 +1,8 @@
 // Optimizer steps over the parameter arena: AdamW as the reference drives it
 // (torch.optim.AdamW, Models/mae/main_pretrain.py:179-180, train_depth.py:280) and LARS
 // (Models/moco_v3/moco/optimizer.py:18-43) as ONE or THREE launches over the flat fp32 buffers of
-// engine.ParamArena instead of a multi-tensor launch chain per step.
+// engine.ParamArena instead of a multi-tensor launch chain per step, and the linear probe's SGD
+// (Models/moco_v3/main_lincls.py:236-238) as one launch over a sub-range of them.
 //
 // The arena is a sequence of segments (one per parameter, 64-element aligned, padding belongs to the
 // preceding parameter and stays zero); per-segment hyper-parameters come from small device tables:
@@ -18,7 +19,7 @@
 //   ctl[1] clip coefficient min(1, max_norm / (norm + 1e-6)); exactly 1 when max_norm <= 0
 //   ctl[2] found_inf: 1 when any ACTIVE element of g is inf or NaN (decided per element), else 0
 //   ctl[3] reserved (0)
-// which the scale kernel and the _ctl AdamW read on the device: nothing comes back to the host.
+// which the scale kernel and the device-counted AdamW read on the device: nothing comes back to the host.
 #include "reduce.h"
 #include "ssl4gie_hip.h"
 
@@ -41,6 +42,14 @@ DEVI int block_seg(const long long* __restrict__ seg_start, int S, long long i, 
     int s = s0;
     while (s + 1 < S && seg_start[s + 1] <= i) ++s;
     return s;
+}
+// the way into a streaming kernel over the elements [lo, n), 1024 per block: the thread's four elements start at i and
+// lie in segment s (slices are 64-element aligned); false for a thread past n
+DEVI bool elem_seg(const long long* __restrict__ seg_start, int S, long long lo, long long n, long long& i, int& s) {
+    const long long first = lo + (long long)blockIdx.x * blockDim.x * 4;
+    i = first + threadIdx.x * 4;
+    s = block_seg(seg_start, S, i < n ? i : n - 4, first);
+    return i < n;
 }
 }  // namespace
 
@@ -66,10 +75,9 @@ __global__ __launch_bounds__(256) void adamw_arena_kernel(
             bc[1] = 1.f / sqrtf(1.f - powf(b2, t));
         }
     }
-    const long long first = lo + (long long)blockIdx.x * blockDim.x * 4;  // elements [lo, n)
-    const long long i = first + threadIdx.x * 4;
-    const int s = block_seg(seg_start, S, i < n ? i : n - 4, first);  // slices are 64-element aligned
-    if (i >= n) return;
+    long long i;
+    int s;
+    if (!elem_seg(seg_start, S, lo, n, i, s)) return;
     const float lr = seg_lr[s];
     if (lr < 0.f) return;
     if (CTL) { bc1 = bc[0]; rsqrt_bc2 = bc[1]; }
@@ -198,10 +206,9 @@ __global__ __launch_bounds__(256) void grad_scale_kernel(
     int S, const float* __restrict__ ctl, long long n) {
     const float coef = ctl[1];
     if (coef == 1.f) return;  // uniform over the grid
-    const long long first = (long long)blockIdx.x * blockDim.x * 4;
-    const long long i = first + threadIdx.x * 4;
-    const int s = block_seg(seg_start, S, i < n ? i : n - 4, first);
-    if (i >= n) return;
+    long long i;
+    int s;
+    if (!elem_seg(seg_start, S, 0, n, i, s)) return;
     if (seg_mask[s] < 0.f) return;
     st4(g + i, ld4(g + i) * coef);
 }
@@ -256,10 +263,9 @@ __global__ __launch_bounds__(256) void lars_apply_kernel(
     const long long* __restrict__ seg_start, const float* __restrict__ seg_lr,
     const float* __restrict__ seg_wd, const float* __restrict__ seg_mat, const float* __restrict__ q,
     int S, float momentum, long long n) {
-    const long long first = (long long)blockIdx.x * blockDim.x * 4;
-    const long long i = first + threadIdx.x * 4;
-    const int s = block_seg(seg_start, S, i < n ? i : n - 4, first);
-    if (i >= n) return;
+    long long i;
+    int s;
+    if (!elem_seg(seg_start, S, 0, n, i, s)) return;
     const float lr = seg_lr[s];
     if (lr < 0.f) return;
     const bool mat = seg_mat[s] != 0.f;
@@ -275,36 +281,52 @@ __global__ __launch_bounds__(256) void lars_apply_kernel(
     st4(p + i, pp);
     st4(mu + i, mm);
 }
-
-extern "C" int ssl4gie_adamw_arena_range(float* p, const float* g, float* m, float* v,
-                                         const long long* seg_start, const float* seg_lr,
-                                         const float* seg_wd, int S, float beta1, float beta2, float eps,
-                                         int step, long long lo, long long hi, void* lp_bf16,
-                                         void* stream) {
-    REQUIRE(p && g && m && v && seg_start && seg_lr && seg_wd && S > 0 && step > 0 && lo >= 0 && hi >= lo &&
-            lo % 4 == 0 && hi % 4 == 0);
-    if (hi == lo) return 0;
-    const float bc1 = 1.f - powf(beta1, (float)step), bc2 = 1.f - powf(beta2, (float)step);
-    hipLaunchKernelGGL(adamw_arena_kernel<false>, dim3((unsigned)(((hi - lo) / 4 + 255) / 256)), dim3(256), 0,
-                       (hipStream_t)stream, p, g, m, v, seg_start, seg_lr, seg_wd, S, beta1, beta2, eps,
-                       bc1, 1.f / sqrtf(bc2), hi, (bf16_t*)lp_bf16, lo, (const float*)nullptr,
-                       (const int*)nullptr, 0);
-    LAUNCH_CHECK();
-    return 0;
+// torch.optim.SGD(momentum, weight_decay), dampening 0, no Nesterov (Models/moco_v3/main_lincls.py:236-238):
+// d = g + wd p; buf = momentum buf + d; p -= lr buf
+__global__ __launch_bounds__(256) void sgd_arena_kernel(
+    float* __restrict__ p, const float* __restrict__ g, float* __restrict__ buf,
+    const long long* __restrict__ seg_start, const float* __restrict__ seg_lr,
+    const float* __restrict__ seg_wd, int S, float momentum, long long n) {
+    long long i;
+    int s;
+    if (!elem_seg(seg_start, S, 0, n, i, s)) return;
+    const float lr = seg_lr[s];
+    if (lr < 0.f) return;
+    const float wd = seg_wd[s];
+    f32x4 pp = ld4(p + i), bb = ld4(buf + i);
+    const f32x4 gg = ld4(g + i);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const float d = gg[j] + wd * pp[j];
+        bb[j] = momentum * bb[j] + d;
+        pp[j] -= lr * bb[j];
+    }
+    st4(p + i, pp);
+    st4(buf + i, bb);
 }
-extern "C" int ssl4gie_adamw_arena_range_ctl(float* p, const float* g, float* m, float* v,
-                                             const long long* seg_start, const float* seg_lr,
-                                             const float* seg_wd, int S, float beta1, float beta2,
-                                             float eps, int* applied, long long lo, long long hi,
-                                             void* lp_bf16, const float* ctl, int skip_nonfinite,
-                                             int advance, void* stream) {
-    REQUIRE(p && g && m && v && seg_start && seg_lr && seg_wd && S > 0 && applied && ctl && lo >= 0 &&
-            hi >= lo && lo % 4 == 0 && hi % 4 == 0);
-    if (hi > lo) {
-        hipLaunchKernelGGL(adamw_arena_kernel<true>, dim3((unsigned)(((hi - lo) / 4 + 255) / 256)), dim3(256),
-                           0, (hipStream_t)stream, p, g, m, v, seg_start, seg_lr, seg_wd, S, beta1, beta2,
-                           eps, 0.f, 0.f, hi, (bf16_t*)lp_bf16, lo, ctl, (const int*)applied,
-                           skip_nonfinite != 0);
+
+extern "C" int ssl4gie_adamw_arena(float* p, const float* g, float* m, float* v, const long long* seg_start,
+                                   const float* seg_lr, const float* seg_wd, int S, float beta1, float beta2,
+                                   float eps, int step, int* applied, long long lo, long long hi, void* lp_bf16,
+                                   const float* ctl, int skip_nonfinite, int advance, void* stream) {
+    REQUIRE(p && g && m && v && seg_start && seg_lr && seg_wd && S > 0 && lo >= 0 && hi >= lo && lo % 4 == 0 &&
+            hi % 4 == 0);
+    REQUIRE(ctl ? applied != nullptr : step > 0 && !applied && !skip_nonfinite && !advance);
+    const dim3 grid((unsigned)(((hi - lo) / 4 + 255) / 256));
+    bf16_t* lp = (bf16_t*)lp_bf16;
+    if (!ctl) {  // host-counted: the bias corrections come from `step`
+        if (hi == lo) return 0;
+        const float bc1 = 1.f - powf(beta1, (float)step), bc2 = 1.f - powf(beta2, (float)step);
+        hipLaunchKernelGGL(adamw_arena_kernel<false>, grid, dim3(256), 0, (hipStream_t)stream, p, g, m, v,
+                           seg_start, seg_lr, seg_wd, S, beta1, beta2, eps, bc1, 1.f / sqrtf(bc2), hi, lp, lo,
+                           (const float*)nullptr, (const int*)nullptr, 0);
+        LAUNCH_CHECK();
+        return 0;
+    }
+    if (hi > lo) {  // device-counted: the kernel derives them from *applied
+        hipLaunchKernelGGL(adamw_arena_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, p, g, m, v,
+                           seg_start, seg_lr, seg_wd, S, beta1, beta2, eps, 0.f, 0.f, hi, lp, lo, ctl,
+                           (const int*)applied, skip_nonfinite != 0);
         LAUNCH_CHECK();
     }
     if (advance) {
@@ -341,21 +363,6 @@ extern "C" int ssl4gie_grad_scale_arena(float* g, const long long* seg_start, co
     LAUNCH_CHECK();
     return 0;
 }
-extern "C" int ssl4gie_adamw_arena_lp(float* p, const float* g, float* m, float* v,
-                                      const long long* seg_start, const float* seg_lr,
-                                      const float* seg_wd, int S, float beta1, float beta2, float eps,
-                                      int step, long long n, void* lp_bf16, void* stream) {
-    REQUIRE(n >= 0);
-    return ssl4gie_adamw_arena_range(p, g, m, v, seg_start, seg_lr, seg_wd, S, beta1, beta2, eps, step, 0, n,
-                                     lp_bf16, stream);
-}
-extern "C" int ssl4gie_adamw_arena(float* p, const float* g, float* m, float* v,
-                                   const long long* seg_start, const float* seg_lr,
-                                   const float* seg_wd, int S, float beta1, float beta2, float eps,
-                                   int step, long long n, void* stream) {
-    return ssl4gie_adamw_arena_lp(p, g, m, v, seg_start, seg_lr, seg_wd, S, beta1, beta2, eps, step, n,
-                                  nullptr, stream);
-}
 extern "C" size_t ssl4gie_lars_workspace_bytes(int S) {
     return ((size_t)S * LARS_PARTS * 2 + S) * sizeof(float);
 }
@@ -377,6 +384,16 @@ extern "C" int ssl4gie_lars_arena(float* p, const float* g, float* mu, const lon
     LAUNCH_CHECK();
     hipLaunchKernelGGL(lars_apply_kernel, dim3((unsigned)((n / 4 + 255) / 256)), dim3(256), 0, st, p, g, mu,
                        seg_start, seg_lr, seg_wd, seg_mat, q, S, momentum, n);
+    LAUNCH_CHECK();
+    return 0;
+}
+extern "C" int ssl4gie_sgd_arena(float* p, const float* g, float* buf, const long long* seg_start, const float* seg_lr,
+                                 const float* seg_wd, int S, float momentum, long long n, void* stream) {
+    REQUIRE(p && g && buf && seg_start && seg_lr && seg_wd && S > 0 && n >= 0 && n % 4 == 0);
+    REQUIRE(((uintptr_t)p | (uintptr_t)g | (uintptr_t)buf) % 16 == 0);
+    if (n == 0) return 0;
+    hipLaunchKernelGGL(sgd_arena_kernel, dim3((unsigned)((n / 4 + 255) / 256)), dim3(256), 0, (hipStream_t)stream, p, g,
+                       buf, seg_start, seg_lr, seg_wd, S, momentum, n);
     LAUNCH_CHECK();
     return 0;
 }

@@ -1,5 +1,5 @@
-// The device code around a FROZEN trunk in the linear probe (Models/mae/main_linprobe.py, Models/moco_v3/main_lincls.py):
-// scoring and the head's SGD step.  The trunk forward is the bulk of a probe step and is not touched here.
+// The scoring around a FROZEN trunk in the linear probe (Models/mae/main_linprobe.py, Models/moco_v3/main_lincls.py).
+// The trunk forward is the bulk of a probe step and is not touched here; the head's SGD step is in optim_ops.hip.
 //
 // topk_update  the drivers score every batch with accuracy(output, target, topk=(1, 5)) (main_lincls.py:506-520; timm's
 //              accuracy in Models/mae/engine_finetune.py:19,119-124) and the criterion's value, and read each meter
@@ -13,8 +13,6 @@
 //              go through a per-row fp32 workspace and are added in fp64 by ONE workgroup in a fixed order (thread t:
 //              rows t, t + 256, ... in index order, then the 256-entry LDS tree of reduce.h): no floating-point atomics,
 //              the same bits from run to run and for any grid.
-// sgd_arena    torch.optim.SGD(momentum, weight_decay), dampening 0, no Nesterov (main_lincls.py:236-238) over the
-//              segment tables of optim_ops.hip: d = g + wd p; buf = mu buf + d; p -= lr buf.
 #include "reduce.h"
 #include "ssl4gie_hip.h"
 
@@ -144,47 +142,6 @@ __global__ __launch_bounds__(256) void topk_loss_kernel(const float* __restrict_
     block_tree_sum(sh, t);
     if (t == 0) *loss_sum += sh[0][0];
 }
-
-// segment of element i, as optim_ops.hip finds it: one binary search per workgroup, then a forward walk
-DEVI int seg_of(const long long* __restrict__ seg_start, int S, long long i, long long block_first) {
-    __shared__ int s0;
-    if (threadIdx.x == 0) {
-        int lo = 0, hi = S;  // invariant: seg_start[lo] <= block_first < seg_start[hi]
-        while (hi - lo > 1) {
-            const int mid = (lo + hi) >> 1;
-            if (seg_start[mid] <= block_first) lo = mid;
-            else hi = mid;
-        }
-        s0 = lo;
-    }
-    __syncthreads();
-    int s = s0;
-    while (s + 1 < S && seg_start[s + 1] <= i) ++s;
-    return s;
-}
-__global__ __launch_bounds__(256) void sgd_arena_kernel(float* __restrict__ p, const float* __restrict__ g,
-                                                        float* __restrict__ buf, const long long* __restrict__ seg_start,
-                                                        const float* __restrict__ seg_lr,
-                                                        const float* __restrict__ seg_wd, int S, float momentum,
-                                                        long long n) {
-    const long long first = (long long)blockIdx.x * blockDim.x * 4;
-    const long long i = first + threadIdx.x * 4;
-    const int s = seg_of(seg_start, S, i < n ? i : n - 4, first);  // segments are 64-element aligned
-    if (i >= n) return;
-    const float lr = seg_lr[s];
-    if (lr < 0.f) return;
-    const float wd = seg_wd[s];
-    f32x4 pp = ld4(p + i), bb = ld4(buf + i);
-    const f32x4 gg = ld4(g + i);
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        const float d = gg[j] + wd * pp[j];
-        bb[j] = momentum * bb[j] + d;
-        pp[j] -= lr * bb[j];
-    }
-    st4(p + i, pp);
-    st4(buf + i, bb);
-}
 }  // namespace
 
 extern "C" size_t ssl4gie_topk_workspace_bytes(int B) { return B > 0 ? align256((size_t)B * sizeof(float)) : 0; }
@@ -214,17 +171,6 @@ extern "C" int ssl4gie_topk_update(const void* logits, int dtype, long long ld, 
                            nk, a, rank, row_loss, ws, B, C);
     LAUNCH_CHECK();
     hipLaunchKernelGGL(topk_loss_kernel, dim3(1), dim3(256), 0, st, (const float*)ws, loss_sum, B);
-    LAUNCH_CHECK();
-    return 0;
-}
-
-extern "C" int ssl4gie_sgd_arena(float* p, const float* g, float* buf, const long long* seg_start, const float* seg_lr,
-                                 const float* seg_wd, int S, float momentum, long long n, void* stream) {
-    REQUIRE(p && g && buf && seg_start && seg_lr && seg_wd && S > 0 && n >= 0 && n % 4 == 0);
-    REQUIRE(((uintptr_t)p | (uintptr_t)g | (uintptr_t)buf) % 16 == 0);
-    if (n == 0) return 0;
-    hipLaunchKernelGGL(sgd_arena_kernel, dim3((unsigned)((n / 4 + 255) / 256)), dim3(256), 0, (hipStream_t)stream, p, g,
-                       buf, seg_start, seg_lr, seg_wd, S, momentum, n);
     LAUNCH_CHECK();
     return 0;
 }

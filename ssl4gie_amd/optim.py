@@ -118,6 +118,16 @@ def clip_grad_norm_(model_or_optimizer, max_norm):
 
 
 class _ArenaOptimizer:
+    """Base of the arena optimizers.  Each steps over a HULL (i0, i1, lo, hi) of the arena: the segments [i0, i1) and the
+    elements [lo, hi) they span.  State buffers and launches cover the hull only: the kernels get `hi - lo` elements and
+    a segment table rebased to `lo`; a parameter inside the hull that is not the optimizer's is inactive through
+    seg_lr < 0, as a frozen one is.  By default the hull is the whole arena, (0, S, 0, numel).  A `_ranged` class (a
+    linear probe's head: 0.77 M of ViT-B's 86 M elements) takes the hull of its own parameters; its `model` may be None:
+    the arena is then found from the parameters (engine.arena_of) at step(), because a model builds its arena lazily."""
+
+    _ranged = False
+    _state_names = ()
+
     def __init__(self, model, params, defaults):
         self.model = model
         if isinstance(params, (list, tuple)) and params and isinstance(params[0], dict):
@@ -132,18 +142,29 @@ class _ArenaOptimizer:
         self.defaults = dict(defaults)
         self._tables_key = None
         self._hyper = None
+        self._hull_key = self._hull = None
         self._gn = None            # _GradNorm of get_grad_norm_ / clip_grad_norm_ / step(clip_grad=) through self
         self.step_count = 0
+
+    def _own(self):
+        return [p for g in self.param_groups for p in g["params"]]
 
     # ------------------------------------------------------------------ segment tables
     def _arena(self):
         # torch optimizers get this through the global pre-step hook parallel.py registers: close any
         # data-parallel pass still open and wait for the comm stream before gradients are read
+        from .engine import arena_of
         from .parallel import before_optimizer_step
         before_optimizer_step()
-        a = self.model.arena()
-        own = [p for g in self.param_groups for p in g["params"]]
-        assert all(a.owns(p) for p in own), "every optimised parameter must live in the model's arena"
+        own = self._own()
+        # ranged: pointer checks on the own parameters only, no walk over the model's parameters per step
+        a = arena_of(own) if self._ranged else None
+        if a is None:  # (ranged: not built yet, or the parameters moved) the model validates / rebuilds it
+            if self.model is None:
+                raise RuntimeError(f"{type(self).__name__}: its parameters do not live in one live engine arena (run a "
+                                   "forward on the device first: the arena is built lazily)")
+            a = self.model.arena()
+            assert all(a.owns(p) for p in own), "every optimised parameter must live in the model's arena"
         _adopt_grads(a, own)
         return a
 
@@ -152,33 +173,31 @@ class _ArenaOptimizer:
             self._gn = _GradNorm(a.data.device)
         return self._gn
 
-    def _build_tables(self, a):
+    def _build_tables(self, a, keep_active=False):
         """device tables [start | lr | wd | is_matrix] per arena parameter.  The layout (start, mat)
         and the active mask are rebuilt only when the arena or the set of parameters with gradients
         changes; a per-iteration learning-rate schedule (`lr_sched.adjust_learning_rate`) only
         rewrites the small pinned host tables and refreshes the device copies with two non-blocking
-        copies on the compute stream — no host synchronisation per step."""
+        copies on the compute stream — no host synchronisation per step.  keep_active: the ACTIVE mask
+        of the previous step stays (gradients do not exist yet while the backward pass is running)."""
         n = len(a.params)
-        group_of = {}
-        for gi, g in enumerate(self.param_groups):
-            for p in g["params"]:
-                group_of[id(p)] = gi
-        active = tuple(id(p) in group_of and p.requires_grad and p.grad is not None for p in a.params)
         hyper = tuple((g["lr"], g["weight_decay"]) for g in self.param_groups)
-        layout_key = (id(a), active)
-        if layout_key != self._tables_key:
-            dev = a.data.device
-            pin = dev.type == "cuda"
-            start = torch.tensor(list(a.offsets) + [a.numel], dtype=torch.int64)
-            mat = torch.tensor([1.0 if (active[i] and p.ndim > 1) else 0.0 for i, p in enumerate(a.params)])
-            if pin:  # kept alive in _host_layout: the copies below do not wait for the host
-                start, mat = start.pin_memory(), mat.pin_memory()
-            self._host_layout = (start, mat)
-            self._host = (torch.empty(n, pin_memory=pin), torch.empty(n, pin_memory=pin))
-            self._dev = [start.to(dev, non_blocking=pin), torch.empty(n, device=dev), torch.empty(n, device=dev),
-                         mat.to(dev, non_blocking=pin)]
-            self._gidx = [group_of.get(id(p), -1) if active[i] else -1 for i, p in enumerate(a.params)]
-            self._tables_key, self._hyper = layout_key, None
+        if not keep_active:
+            group_of = {id(p): gi for gi, g in enumerate(self.param_groups) for p in g["params"]}
+            active = tuple(id(p) in group_of and p.requires_grad and p.grad is not None for p in a.params)
+            if (id(a), active) != self._tables_key:
+                dev = a.data.device
+                pin = dev.type == "cuda"
+                start = torch.tensor(list(a.offsets) + [a.numel], dtype=torch.int64)
+                mat = torch.tensor([1.0 if (active[i] and p.ndim > 1) else 0.0 for i, p in enumerate(a.params)])
+                if pin:  # kept alive in _host_layout: the copies below do not wait for the host
+                    start, mat = start.pin_memory(), mat.pin_memory()
+                self._host_layout = (start, mat)
+                self._host = (torch.empty(n, pin_memory=pin), torch.empty(n, pin_memory=pin))
+                self._dev = [start.to(dev, non_blocking=pin), torch.empty(n, device=dev), torch.empty(n, device=dev),
+                             mat.to(dev, non_blocking=pin)]
+                self._gidx = [group_of.get(id(p), -1) if active[i] else -1 for i, p in enumerate(a.params)]
+                self._tables_key, self._hyper = (id(a), active), None
         if hyper != self._hyper:
             lr_h, wd_h = self._host
             lrs = [hyper[gi][0] if gi >= 0 else -1.0 for gi in self._gidx]
@@ -190,31 +209,68 @@ class _ArenaOptimizer:
             self._hyper = hyper
         return tuple(self._dev) + (n,)
 
-    # ------------------------------------------------------------------ checkpointing
-    def _state_buffers(self):
-        raise NotImplementedError
+    def _tables(self, a, keep_active=False):
+        """-> (start - lo [S + 1], lr [S], wd [S], mat [S], S, lo, hi) over the hull's S segments: slices of the
+        whole-arena tables (a learning-rate schedule still only rewrites those), cut once per layout"""
+        start, lr, wd, mat, n = self._build_tables(a, keep_active)
+        if self._hull_key != self._tables_key:
+            i0, i1 = 0, n
+            if self._ranged:
+                own = {id(p) for p in self._own()}
+                idx = [i for i, p in enumerate(a.params) if id(p) in own]
+                i0, i1 = min(idx), max(idx) + 1
+            lo = a.offsets[i0]
+            hi = a.offsets[i1] if i1 < n else a.numel
+            rstart = (start[i0:i1 + 1] - lo).contiguous() if lo else start[i0:i1 + 1]
+            self._hull = (rstart, lr[i0:i1], wd[i0:i1], mat[i0:i1], i1 - i0, lo, hi)
+            self._hull_key = self._tables_key
+        return self._hull
 
+    def _state(self, name, a, lo, hi):
+        """the hull-sized fp32 state buffer `name` on the arena's device (zeros when fresh).  A buffer of another
+        size: the whole-arena optimizers start over with zeros (the arena was rebuilt), a ranged one refuses."""
+        v = getattr(self, name)
+        if v is None or (not self._ranged and v.numel() != hi - lo):
+            v = torch.zeros(hi - lo, dtype=torch.float32, device=a.data.device)
+        elif v.numel() != hi - lo:
+            raise ValueError(f"{type(self).__name__}.{name} holds {v.numel()} elements, the hull of its parameters "
+                             f"{hi - lo}: the state was saved for a different arena layout")
+        elif v.device != a.data.device:
+            v = v.to(a.data.device)
+        setattr(self, name, v)
+        return v
+
+    def _finish_step(self, count=True):
+        if count:
+            self.step_count += 1
+        bump_weights_epoch(touched=self._own())
+
+    # ------------------------------------------------------------------ checkpointing
     def state_dict(self):
-        """moments / momentum as flat arena-shaped fp32 tensors + step count + param_groups (without
+        """moments / momentum as flat hull-shaped fp32 tensors + step count + param_groups (without
         the parameter objects) — what `save_model` (`Models/mae/util/misc.py:301-307`) and
         `main_moco.py:310-316` store under "optimizer" for `--resume`"""
         groups = [{k: v for k, v in g.items() if k != "params"} | {"n_params": len(g["params"])}
                   for g in self.param_groups]
+        state = {k: getattr(self, k) for k in self._state_names}
         return {"kind": type(self).__name__, "step_count": self.step_count, "param_groups": groups,
-                "state": {k: (v.detach().clone() if v is not None else None)
-                          for k, v in self._state_buffers().items()}}
+                "state": {k: (v.detach().clone() if v is not None else None) for k, v in state.items()}}
 
     def load_state_dict(self, sd):
+        """the whole-arena optimizers check the buffers' size against the arena here; a ranged one at its next
+        step() (its arena may not exist yet)"""
         assert sd["kind"] == type(self).__name__, (sd["kind"], type(self).__name__)
         assert len(sd["param_groups"]) == len(self.param_groups)
         for g, saved in zip(self.param_groups, sd["param_groups"]):
             assert saved["n_params"] == len(g["params"]), "parameter groups differ from the saved ones"
             g.update({k: v for k, v in saved.items() if k != "n_params"})
-        a = self._arena()
-        for k, v in sd["state"].items():
+        a = None if self._ranged else self._arena()
+        for k in self._state_names:
+            v = sd["state"].get(k)
             if v is not None:
-                assert v.numel() == a.numel, "optimizer state was saved for a different arena layout"
-                setattr(self, k, v.to(a.data.device, torch.float32).clone())
+                assert a is None or v.numel() == a.numel, "optimizer state was saved for a different arena layout"
+                v = v.detach().to(device=None if a is None else a.data.device, dtype=torch.float32).clone()
+            setattr(self, k, v)
         self.step_count = int(sd["step_count"])
         self._hyper = None
 
@@ -257,6 +313,8 @@ class ArenaAdamW(_ArenaOptimizer):
     at checkpoint time only).  Both options need every gradient before the first update: together with
     overlap_backward=True they raise ValueError."""
 
+    _state_names = ("exp_avg", "exp_avg_sq")
+
     def __init__(self, model, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2,
                  overlap_backward=False):
         self._host_steps = 0       # count of applied updates while it lives on the host ...
@@ -268,18 +326,15 @@ class ArenaAdamW(_ArenaOptimizer):
         self._overlap = bool(overlap_backward)
         self._stream = None        # side stream of the in-backward updates
         self._done = []            # [lo, hi) ranges already updated in the current step
-        self._tables = None        # device tables of the current step (built at its first use)
+        self._step_tables = None   # device tables of the current step (built at its first use)
         self._seen = {}            # id(p) -> tracker calls in the current pass
         self._hooked = False
         self._lp = None
         self.last_grad_norm = self.last_found_inf = None
 
-    def _state_buffers(self):
-        return {"exp_avg": self.exp_avg, "exp_avg_sq": self.exp_avg_sq}
-
     # ------------------------------------------------------------------ count of applied updates
     # host-side until the first step(clip_grad= / skip_nonfinite=); then ONE int32 on the device, which
-    # the _ctl kernel reads and advances (a skipped update must not advance the bias corrections)
+    # the device-counted kernel reads and advances (a skipped update must not advance the bias corrections)
     @property
     def step_count(self):
         return self._host_steps if self._dev_steps is None else int(self._dev_steps.item())
@@ -303,14 +358,18 @@ class ArenaAdamW(_ArenaOptimizer):
     def zero_grad(self, set_to_none: bool = True):
         super().zero_grad(set_to_none)
         self._hook()
-        self._done, self._seen, self._tables = [], {}, None
+        self._done, self._seen, self._step_tables = [], {}, None
 
-    def _launch(self, a, lo, hi, st):
-        start, lr, wd, _, S = self._tables
-        _lib.check(_lib.load().ssl4gie_adamw_arena_range(
+    def _launch(self, a, lo, hi, st, ctl=None, skip_nonfinite=False):
+        """the update of the elements [lo, hi): host-counted, or with `ctl` behind the control block and the device-side
+        count, which it then advances"""
+        start, lr, wd, _, S, _, _ = self._step_tables
+        counted = ctl is not None
+        _lib.check(_lib.load().ssl4gie_adamw_arena(
             ptr(a.data), ptr(a.grad), ptr(self.exp_avg), ptr(self.exp_avg_sq), ptr(start), ptr(lr), ptr(wd), S,
-            self.betas[0], self.betas[1], self.eps, self.step_count + 1, lo, hi, ptr(self._lp), st),
-            "adamw_arena_range")
+            self.betas[0], self.betas[1], self.eps, 0 if counted else self._host_steps + 1,
+            ptr(self._dev_steps) if counted else 0, lo, hi, ptr(self._lp), ptr(ctl), int(bool(skip_nonfinite)),
+            int(counted), st), "adamw_arena")
 
     @torch.no_grad()
     def _on_use_done(self, params):
@@ -328,9 +387,9 @@ class ArenaAdamW(_ArenaOptimizer):
         ids = {id(p) for p in params}
         if any(id(q) not in ids for q in inside) or any(lo < h and l < hi for l, h in self._done):
             return  # not a contiguous run of exactly these parameters: left to step()
-        if self._tables is None:
+        if self._step_tables is None:
             self._lp = a.lp_flat_for_update()
-            self._tables = self._build_tables_cached(a)
+            self._step_tables = self._tables(a, keep_active=True)
         if self._stream is None:
             self._stream = torch.cuda.Stream(device=a.data.device)
         ev = torch.cuda.Event()
@@ -344,26 +403,9 @@ class ArenaAdamW(_ArenaOptimizer):
         self._launch(a, lo, hi, self._stream.cuda_stream)
         self._done.append((lo, hi))
 
-    def _build_tables_cached(self, a):
-        """tables with the ACTIVE mask of the previous step (gradients do not exist yet while the
-        backward pass is running); only the lr / wd values are refreshed"""
-        saved = self._tables_key
-        n = len(a.params)
-        group_of = {id(p): gi for gi, g in enumerate(self.param_groups) for p in g["params"]}
-        hyper = tuple((g["lr"], g["weight_decay"]) for g in self.param_groups)
-        if hyper != self._hyper:
-            lr_h, wd_h = self._host
-            lr_h.copy_(torch.tensor([hyper[gi][0] if gi >= 0 else -1.0 for gi in self._gidx]))
-            wd_h.copy_(torch.tensor([hyper[gi][1] if gi >= 0 else 0.0 for gi in self._gidx]))
-            self._dev[1].copy_(lr_h, non_blocking=True)
-            self._dev[2].copy_(wd_h, non_blocking=True)
-            self._hyper = hyper
-        assert self._tables_key == saved and group_of is not None
-        return tuple(self._dev) + (n,)
-
     def _step_ctl(self, a, clip_grad, skip_nonfinite):
         """norm pass (when an option asks for it) + the AdamW kernel behind the control block"""
-        start, lr, wd, _, S = self._tables
+        start, lr, _, _, S, lo, hi = self._step_tables
         dev = a.data.device
         if self._dev_steps is None:
             self._dev_steps = torch.full((1,), self._host_steps, dtype=torch.int32, device=dev)
@@ -379,10 +421,7 @@ class ArenaAdamW(_ArenaOptimizer):
                 self._ctl_plain = torch.zeros(4, device=dev)
                 self._ctl_plain[1] = 1.0
             ctl = self._ctl_plain
-        _lib.check(_lib.load().ssl4gie_adamw_arena_range_ctl(
-            ptr(a.data), ptr(a.grad), ptr(self.exp_avg), ptr(self.exp_avg_sq), ptr(start), ptr(lr), ptr(wd), S,
-            self.betas[0], self.betas[1], self.eps, ptr(self._dev_steps), 0, a.numel, ptr(self._lp), ptr(ctl),
-            int(bool(skip_nonfinite)), 1, stream()), "adamw_arena_range_ctl")
+        self._launch(a, lo, hi, stream(), ctl, skip_nonfinite)
 
     @torch.no_grad()
     def step(self, clip_grad=None, skip_nonfinite=False):
@@ -391,147 +430,102 @@ class ArenaAdamW(_ArenaOptimizer):
             raise ValueError("ArenaAdamW(overlap_backward=True) applies updates while the backward pass is "
                              "still running; clip_grad / skip_nonfinite need the norm of EVERY gradient first")
         a = self._arena()
-        if self.exp_avg is None or self.exp_avg.numel() != a.numel:
-            self.exp_avg = torch.zeros_like(a.data)
-            self.exp_avg_sq = torch.zeros_like(a.data)
         key_before = self._tables_key
-        tables = self._build_tables(a)
+        tables = self._tables(a)
         if self._done and self._tables_key != key_before:
             raise RuntimeError("ArenaAdamW(overlap_backward=True): the set of parameters with gradients "
                                "changed between steps after part of this step was already applied")
-        self._tables = tables
+        self._step_tables = tables
+        lo, hi = tables[5:]
+        for name in self._state_names:
+            self._state(name, a, lo, hi)
         # the kernels also write the bf16 operand copy of what they update into the arena's flat shadow
         # (engine.ParamArena.lp_views): the next forward then only needs the batched transposes
         self._lp = a.lp_flat_for_update() if a.data.is_cuda else None
-        if ctl_path or self._dev_steps is not None:
+        counted = ctl_path or self._dev_steps is not None
+        if counted:
             assert not self._done, "in-backward updates and the device-side step count do not mix"
             self._step_ctl(a, clip_grad, skip_nonfinite)
         else:
             st = stream()
-            pos = 0
-            for lo, hi in sorted(self._done) + [(a.numel, a.numel)]:  # the complement of the ranges done
-                if lo > pos:
-                    self._launch(a, pos, lo, st)
-                pos = max(pos, hi)
+            pos = lo
+            for l, h in sorted(self._done) + [(hi, hi)]:  # the complement of the ranges done
+                if l > pos:
+                    self._launch(a, pos, l, st)
+                pos = max(pos, h)
             if self._done:
                 torch.cuda.current_stream(a.data.device).wait_stream(self._stream)
-            self.step_count += 1
-        self._done, self._seen, self._tables = [], {}, None
-        bump_weights_epoch(touched=[p for g in self.param_groups for p in g["params"]])
+        self._done, self._seen, self._step_tables = [], {}, None
+        self._finish_step(count=not counted)
         if self._lp is not None:
             a.lp_flat_is_current()
 
 
-class ArenaLARS(_ArenaOptimizer):
-    """`ArenaLARS(model, params_or_groups, lr=0, weight_decay=0, momentum=0.9, trust_coefficient=0.001)`"""
+class _LARS(_ArenaOptimizer):
+    """the LARS step over the hull: the three launches of ssl4gie_lars_arena, a hull-sized momentum buffer and
+    workspace.  A subclass says where momentum and trust coefficient are kept."""
 
-    def __init__(self, model, params, lr=0.0, weight_decay=0.0, momentum=0.9, trust_coefficient=0.001):
-        super().__init__(model, params, dict(lr=lr, weight_decay=weight_decay))
-        self.momentum, self.trust = momentum, trust_coefficient
-        self.mu = None
-        self._ws = None
+    _state_names = ("mu",)
+    mu = _ws = None
 
-    def _state_buffers(self):
-        return {"mu": self.mu}
+    def _momentum_trust(self):
+        raise NotImplementedError
 
     @torch.no_grad()
     def step(self):
         a = self._arena()
-        if self.mu is None or self.mu.numel() != a.numel:
-            self.mu = torch.zeros_like(a.data)
-        start, lr, wd, mat, S = self._build_tables(a)
+        start, lr, wd, mat, S, lo, hi = self._tables(a)
+        mu = self._state("mu", a, lo, hi)
         L = _lib.load()
         nbytes = L.ssl4gie_lars_workspace_bytes(S)
-        if self._ws is None or self._ws.numel() < nbytes:
+        if self._ws is None or self._ws.numel() < nbytes or self._ws.device != a.data.device:
             self._ws = torch.empty(nbytes, dtype=torch.uint8, device=a.data.device)
-        self.step_count += 1
-        _lib.check(L.ssl4gie_lars_arena(ptr(a.data), ptr(a.grad), ptr(self.mu), ptr(start), ptr(lr), ptr(wd),
-                                        ptr(mat), S, self.momentum, self.trust, ptr(self._ws), a.numel,
+        momentum, trust = self._momentum_trust()
+        _lib.check(L.ssl4gie_lars_arena(ptr(a.data) + 4 * lo, ptr(a.grad) + 4 * lo, ptr(mu), ptr(start), ptr(lr),
+                                        ptr(wd), ptr(mat), S, float(momentum), float(trust), ptr(self._ws), hi - lo,
                                         stream()), "lars_arena")
-        bump_weights_epoch(touched=[p for g in self.param_groups for p in g["params"]])
+        self._finish_step()
 
 
-class _RangedArenaOptimizer(_ArenaOptimizer):
-    """An arena optimizer whose parameters are a small part of the arena (a linear probe's head: 0.77 M of ViT-B's
-    86 M elements): state and launches cover only the HULL [lo, hi) of its parameters' segments — the kernels get
-    pointers offset by `lo`, `hi - lo` elements and a segment table rebased to the hull; any other parameter inside
-    the hull is inactive through seg_lr < 0, as a frozen one is.  `model` may be None: the arena is then found from the
-    parameters (engine.arena_of) at step(), because a model builds its arena lazily."""
+class ArenaLARS(_LARS):
+    """`ArenaLARS(model, params_or_groups, lr=0, weight_decay=0, momentum=0.9, trust_coefficient=0.001)`: the
+    reference's `Models/moco_v3/moco/optimizer.py:18-43` over the whole arena"""
 
-    _state_names = ()
+    def __init__(self, model, params, lr=0.0, weight_decay=0.0, momentum=0.9, trust_coefficient=0.001):
+        super().__init__(model, params, dict(lr=lr, weight_decay=weight_decay))
+        self.momentum, self.trust = momentum, trust_coefficient
 
-    def __init__(self, model, params, defaults):
-        super().__init__(model, params, defaults)
-        self._range_key = self._range = None
-
-    def _arena(self):
-        from .engine import arena_of
-        from .parallel import before_optimizer_step
-        before_optimizer_step()
-        own = [p for g in self.param_groups for p in g["params"]]
-        a = arena_of(own)   # pointer checks on the own parameters only: no walk over the model's parameters per step
-        if a is None and self.model is not None:
-            return super()._arena()   # not built yet, or the parameters moved: the model validates / rebuilds it
-        if a is None:
-            raise RuntimeError(f"{type(self).__name__}: its parameters do not live in one live engine arena (run a "
-                               "forward on the device first: the arena is built lazily)")
-        _adopt_grads(a, own)
-        return a
-
-    def _ranged_tables(self, a):
-        """-> (start - lo [S + 1], lr [S], wd [S], mat [S], S, lo, hi) over the hull's S segments: slices of the
-        whole-arena tables (a learning-rate schedule still only rewrites those), the rebased starts built once per
-        layout on the device"""
-        start, lr, wd, mat, _ = self._build_tables(a)
-        if self._range_key != self._tables_key:
-            own = {id(p) for g in self.param_groups for p in g["params"]}
-            idx = [i for i, p in enumerate(a.params) if id(p) in own]
-            i0, i1 = min(idx), max(idx) + 1
-            lo = a.offsets[i0]
-            hi = a.offsets[i1] if i1 < len(a.params) else a.numel
-            self._range = (i0, i1, lo, hi, (start[i0:i1 + 1] - lo).contiguous())
-            self._range_key = self._tables_key
-        i0, i1, lo, hi, rstart = self._range
-        return rstart, lr[i0:i1], wd[i0:i1], mat[i0:i1], i1 - i0, lo, hi
-
-    def _state(self, name, a, lo, hi):
-        """the hull-sized fp32 state buffer `name` on the arena's device (zeros when fresh)"""
-        v = getattr(self, name)
-        if v is None:
-            v = torch.zeros(hi - lo, dtype=torch.float32, device=a.data.device)
-        elif v.numel() != hi - lo:
-            raise ValueError(f"{type(self).__name__}.{name} holds {v.numel()} elements, the hull of its parameters "
-                             f"{hi - lo}: the state was saved for a different arena layout")
-        elif v.device != a.data.device:
-            v = v.to(a.data.device)
-        setattr(self, name, v)
-        return v
-
-    def _state_buffers(self):
-        return {k: getattr(self, k) for k in self._state_names}
-
-    def load_state_dict(self, sd):
-        """_ArenaOptimizer's format with hull-sized buffers; their size is checked against the hull at the next
-        step() (the arena may not exist yet)"""
-        assert sd["kind"] == type(self).__name__, (sd["kind"], type(self).__name__)
-        assert len(sd["param_groups"]) == len(self.param_groups)
-        for g, saved in zip(self.param_groups, sd["param_groups"]):
-            assert saved["n_params"] == len(g["params"]), "parameter groups differ from the saved ones"
-            g.update({k: v for k, v in saved.items() if k != "n_params"})
-        for k in self._state_names:
-            v = sd["state"].get(k)
-            setattr(self, k, None if v is None else v.detach().to(torch.float32).clone())
-        self.step_count = int(sd["step_count"])
-        self._hyper = None
+    def _momentum_trust(self):
+        return self.momentum, self.trust
 
 
-class ArenaSGD(_RangedArenaOptimizer):
+class RangedLARS(_LARS):
+    """ArenaLARS's update over the hull of its parameters only: a hull-sized momentum buffer and workspace instead of
+    arena-sized ones; momentum and trust coefficient are parameter-group defaults, as in the reference's signature,
+    which `Models/mae/util/lars.py` gives it."""
+
+    _ranged = True
+
+    def __init__(self, model, params, lr=0.0, weight_decay=0.0, momentum=0.9, trust_coefficient=0.001):
+        super().__init__(model, params, dict(lr=lr, weight_decay=weight_decay, momentum=momentum,
+                                             trust_coefficient=trust_coefficient))
+        if any(g["momentum"] != self.param_groups[0]["momentum"] or
+               g["trust_coefficient"] != self.param_groups[0]["trust_coefficient"] for g in self.param_groups):
+            raise NotImplementedError("LARS: momentum and trust_coefficient must be the same in every group")
+
+    def _momentum_trust(self):
+        g0 = self.param_groups[0]
+        return g0["momentum"], g0["trust_coefficient"]
+
+
+class ArenaSGD(_ArenaOptimizer):
     """`ArenaSGD(model, params_or_groups, lr, momentum=0, weight_decay=0)`: torch.optim.SGD as the linear-probe driver
     builds it (`Models/moco_v3/main_lincls.py:236-238`: momentum 0.9, weight decay 0 over fc's two parameters) in ONE
     launch of ssl4gie_sgd_arena over the hull of its parameters: d = g + wd p; buf = momentum buf + d; p -= lr buf.
     The momentum buffer starts at zero, which reproduces torch's first step (buf = d).  Nesterov momentum and
     dampening are not built."""
 
+    _ranged = True
     _state_names = ("buf",)
 
     def __init__(self, model, params, lr, momentum=0.0, weight_decay=0.0, dampening=0.0, nesterov=False):
@@ -546,42 +540,8 @@ class ArenaSGD(_RangedArenaOptimizer):
     @torch.no_grad()
     def step(self):
         a = self._arena()
-        start, lr, wd, _, S, lo, hi = self._ranged_tables(a)
+        start, lr, wd, _, S, lo, hi = self._tables(a)
         buf = self._state("buf", a, lo, hi)
-        self.step_count += 1
-        _lib.check(_lib.load().ssl4gie_sgd_arena(ptr(a.data[lo:hi]), ptr(a.grad[lo:hi]), ptr(buf), ptr(start), ptr(lr),
-                                                 ptr(wd), S, self.momentum, hi - lo, stream()), "sgd_arena")
-        bump_weights_epoch(touched=[p for g in self.param_groups for p in g["params"]])
-
-
-class RangedLARS(_RangedArenaOptimizer):
-    """ArenaLARS's update (the same three launches of ssl4gie_lars_arena) over the hull of its parameters only: a
-    hull-sized momentum buffer and workspace instead of arena-sized ones.  `Models/mae/util/lars.py` gives it the
-    reference's signature."""
-
-    _state_names = ("mu",)
-
-    def __init__(self, model, params, lr=0.0, weight_decay=0.0, momentum=0.9, trust_coefficient=0.001):
-        super().__init__(model, params, dict(lr=lr, weight_decay=weight_decay, momentum=momentum,
-                                             trust_coefficient=trust_coefficient))
-        if any(g["momentum"] != self.param_groups[0]["momentum"] or
-               g["trust_coefficient"] != self.param_groups[0]["trust_coefficient"] for g in self.param_groups):
-            raise NotImplementedError("LARS: momentum and trust_coefficient must be the same in every group")
-        self.mu = None
-        self._ws = None
-
-    @torch.no_grad()
-    def step(self):
-        a = self._arena()
-        start, lr, wd, mat, S, lo, hi = self._ranged_tables(a)
-        mu = self._state("mu", a, lo, hi)
-        L = _lib.load()
-        nbytes = L.ssl4gie_lars_workspace_bytes(S)
-        if self._ws is None or self._ws.numel() < nbytes or self._ws.device != a.data.device:
-            self._ws = torch.empty(nbytes, dtype=torch.uint8, device=a.data.device)
-        self.step_count += 1
-        g0 = self.param_groups[0]
-        _lib.check(L.ssl4gie_lars_arena(ptr(a.data[lo:hi]), ptr(a.grad[lo:hi]), ptr(mu), ptr(start), ptr(lr), ptr(wd),
-                                        ptr(mat), S, float(g0["momentum"]), float(g0["trust_coefficient"]),
-                                        ptr(self._ws), hi - lo, stream()), "lars_arena")
-        bump_weights_epoch(touched=[p for g in self.param_groups for p in g["params"]])
+        _lib.check(_lib.load().ssl4gie_sgd_arena(ptr(a.data) + 4 * lo, ptr(a.grad) + 4 * lo, ptr(buf), ptr(start),
+                                                 ptr(lr), ptr(wd), S, self.momentum, hi - lo, stream()), "sgd_arena")
+        self._finish_step()

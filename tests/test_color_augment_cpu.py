@@ -111,7 +111,7 @@ def test_header_declares_and_lib_binds_the_colour_stage():
     declared = set(re.findall(r"\b(ssl4gie_[a-z0-9_]+)\s*\(", txt))
     for name in ("ssl4gie_color_augment", "ssl4gie_color_augment_workspace_bytes"):
         assert name in declared and name in _lib.PROTOTYPES
-    assert _lib.ABI_VERSION == 12 and _lib.load().ssl4gie_abi_version() == 12
+    assert _lib.ABI_VERSION == 13 and _lib.load().ssl4gie_abi_version() == 13
 
 
 def test_color_augment_refuses_host_checkable_arguments_before_any_launch():

@@ -99,12 +99,12 @@ def test_header_prototypes_and_abi():
     names = set(re.findall(r"\b(ssl4gie_[a-z0-9_]+)\s*\(", txt))
     assert names == set(_lib.PROTOTYPES), names ^ set(_lib.PROTOTYPES)
     assert NEW_SYMBOLS <= names
-    assert _lib.ABI_VERSION == 12 and "return 12" in open(os.path.join(ROOT, "ssl4gie_amd", "csrc", "engine.hip")).read()
+    assert _lib.ABI_VERSION == 13 and "return 13" in open(os.path.join(ROOT, "ssl4gie_amd", "csrc", "engine.hip")).read()
 
 
 def test_workspace_query_and_cpu_refusals():
     L = _lib.load()
-    assert L.ssl4gie_abi_version() == 12
+    assert L.ssl4gie_abi_version() == 13
     n = L.ssl4gie_dwconv3x3_wgrad_workspace_bytes(_lib.BF16, 2, 14, 14, 2048)
     assert n > 0 and n % (9 * 2048 * 4) == 0
     assert L.ssl4gie_dwconv3x3_wgrad_workspace_bytes(_lib.BF16, 2, 14, 14, 12) == 0   # C % 8

@@ -203,7 +203,7 @@ def test_new_symbols_declared_bound_and_resolvable():
         assert name in _lib.PROTOTYPES and hasattr(lib, name)
         decl = re.search(r"\b" + name + r"\s*\(([^;]*)\)\s*;", code).group(1)
         assert len([a for a in decl.split(",") if a.strip()]) == len(_lib.PROTOTYPES[name][1]), name
-    assert _lib.ABI_VERSION == 12 and lib.ssl4gie_abi_version() == 12
+    assert _lib.ABI_VERSION == 13 and lib.ssl4gie_abi_version() == 13
     assert lib.ssl4gie_det_color_workspace_bytes(0) == 0 and lib.ssl4gie_det_color_workspace_bytes(4) == 4 * 64 * 4
     # the declarations cite the reference lines they replace
     block = txt[txt.index("The detection loaders (Object_detection"):txt.index("size_t ssl4gie_det_color_workspace_bytes")]

@@ -223,9 +223,9 @@ def test_header_declares_and_lib_binds_the_det_map_symbols():
                  "SSL4GIE_DET_MAP_CLASSES 256", "SSL4GIE_DET_MAP_CHUNK 256"):
         assert line in txt, line
     assert (_lib.DET_MAP_MAX_PER_IMAGE, _lib.DET_MAP_CLASSES, _lib.DET_MAP_CHUNK) == (1024, 256, 256)
-    assert _lib.ABI_VERSION == 12
+    assert _lib.ABI_VERSION == 13
     L = _lib.load()
-    assert L.ssl4gie_abi_version() == 12
+    assert L.ssl4gie_abi_version() == 13
     for name in NEW_SYMBOLS:
         assert getattr(L, name) is not None
     srcs = open(os.path.join(ROOT, "ssl4gie_amd", "csrc", "Makefile")).read()

@@ -245,7 +245,7 @@ def test_header_declares_and_lib_binds_the_finetune_stage():
         assert name in declared and name in _lib.PROTOTYPES
     for name, value in (("SSL4GIE_TGT_U8", _lib.TGT_U8), ("SSL4GIE_TGT_U16", _lib.TGT_U16), ("SSL4GIE_TGT_F32", _lib.TGT_F32)):
         assert re.search(rf"#define {name} {value}\b", txt)
-    assert _lib.ABI_VERSION == 12 and _lib.load().ssl4gie_abi_version() == 12
+    assert _lib.ABI_VERSION == 13 and _lib.load().ssl4gie_abi_version() == 13
 
 
 def test_finetune_entry_points_refuse_host_checkable_arguments_before_any_launch():

@@ -1,5 +1,5 @@
-"""GPU parity of the linear-probe device code (csrc/probe_ops.hip and what drives it): ssl4gie_topk_update and
-ssl4gie_sgd_arena against the restatements of tests/probe_checks.py, the ranged optimizers, the BatchNorm head on the
+"""GPU parity of the linear-probe device code (csrc/probe_ops.hip, the SGD step of csrc/optim_ops.hip and what drives
+them): ssl4gie_topk_update and ssl4gie_sgd_arena against the restatements of tests/probe_checks.py, the ranged optimizers, the BatchNorm head on the
 reference's recorded run (G22), the frozen-trunk step end to end, and the unchanged Linear-head path.
 
 Bars: counts and ranks exact; losses max(1e-5, 8 * e32) with e32 the error of torch's own fp32 formulation on the CPU

@@ -173,7 +173,7 @@ def test_header_declares_and_lib_binds_the_view_sampler():
     assert "ssl4gie_view_sample_u8" in declared and "ssl4gie_view_sample_u8" in _lib.PROTOTYPES
     assert re.search(r"#define\s+SSL4GIE_FILTER_BILINEAR\s+0\b", txt) and re.search(r"#define\s+SSL4GIE_FILTER_BICUBIC\s+1\b", txt)
     assert (_lib.FILTER_BILINEAR, _lib.FILTER_BICUBIC) == (0, 1)
-    assert _lib.ABI_VERSION == 12 and _lib.load().ssl4gie_abi_version() == 12
+    assert _lib.ABI_VERSION == 13 and _lib.load().ssl4gie_abi_version() == 13
     # host-checkable arguments are refused before anything is launched (no GPU needed: SSL4GIE_EARG)
     import ctypes as C
     L = _lib.load()

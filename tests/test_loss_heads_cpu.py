@@ -50,9 +50,9 @@ def test_header_declares_and_lib_binds_the_loss_head_symbols():
     for name in NEW_SYMBOLS:
         assert name in declared, name
         assert name in _lib.PROTOTYPES, name
-    assert _lib.ABI_VERSION == 12
+    assert _lib.ABI_VERSION == 13
     L = _lib.load()
-    assert L.ssl4gie_abi_version() == 12
+    assert L.ssl4gie_abi_version() == 13
     # workspace queries need no GPU
     assert L.ssl4gie_infonce_workspace_bytes(256, 2048, 256) > (256 + 2048) * 256 * 4
     assert L.ssl4gie_infonce_workspace_bytes(0, 8, 8) == 0

@@ -167,9 +167,9 @@ def test_header_declares_and_lib_binds_the_metric_symbols():
         assert name in declared, name
         assert name in _lib.PROTOTYPES, name
     assert "SSL4GIE_PRED_I64 2" in txt and _lib.PRED_I64 == 2
-    assert _lib.ABI_VERSION == 12
+    assert _lib.ABI_VERSION == 13
     L = _lib.load()   # resolves every bound symbol in the built library
-    assert L.ssl4gie_abi_version() == 12
+    assert L.ssl4gie_abi_version() == 13
     for name in NEW_SYMBOLS:
         assert getattr(L, name) is not None
     srcs = open(os.path.join(ROOT, "ssl4gie_amd", "csrc", "Makefile")).read()
