@@ -543,7 +543,8 @@ int ssl4gie_subsample2(const void* x, void* y, int dtype, int B, int H, int W, i
  * (C % 8 == 0), fused with the bottleneck's residual add and ReLU: y = act(xhat gamma + beta (+ res)), statistics in
  * fp32 (biased variance for the normalisation, unbiased for running_var, momentum as nn.BatchNorm: running =
  * (1-m) running + m batch).  Backward: g = masked dy, dgamma = sum g xhat, dbeta = sum g,
- * dx = gamma rstd (g - mean(g) - xhat mean(g xhat)), dres (optional) = g.  Five functions span a small product; a
+ * dx = gamma rstd (g - mean(g) - xhat mean(g xhat)), dres (optional) = g.  Five functions span a small product (and
+ * a sixth, ssl4gie_bn_bwd_frozen, is the backward through fixed statistics); a
  * combination outside it (a pointer the form does not use included: pass NULL) is SSL4GIE_EARG.  gamma / beta / res /
  * running_* may be NULL wherever they are used.
  *
@@ -581,6 +582,16 @@ int ssl4gie_subsample2(const void* x, void* y, int dtype, int B, int H, int W, i
  *   ssl4gie_bn_bwd_apply   second half: dx from the GLOBAL sums and inv_count = 1 / global row count.  MASK_NONE, _Y
  *                          or _X; after a MASK_BITS (or any residual + ReLU) reduce, apply on its dres with MASK_NONE.
  *   (convert_sync_batchnorm: Depth_estimation/train_depth.py:225, Models/moco_v3/main_moco.py:196.)
+ *   ssl4gie_bn_bwd_frozen  backward through FIXED statistics: BatchNorm in evaluation mode, and torchvision's
+ *                          FrozenBatchNorm2d of fasterrcnn_resnet50_fpn's trunk (Object_detection/
+ *                          train_detection.py:197-202).  mean / rstd are the running ones, so no term depends on a
+ *                          sum over the batch: g = masked dy, a = rstd gamma (gamma NULL: 1), dx = a g, dres
+ *                          (optional) = g bit for bit, and where given dbeta = sum g, dgamma = sum g xhat (overwritten
+ *                          or accumulated).  Without dgamma / dbeta it is ONE flat pass (MASK_Y: dy, y -> dx (, dres);
+ *                          MASK_BITS: dy and 1/16 of a map -> dx, dres) and workspace is NULL; with them one reduction
+ *                          pass that writes dx and dres as well, then the tail, and workspace is required.  x and
+ *                          mean are read by MASK_X or for dgamma only and are NULL otherwise; beta by MASK_X only.
+ *                          C % 8 == 0 (bf16) / C % 4 == 0 (fp32).
  *
  * `workspace`: ssl4gie_bn_workspace_bytes(rows, C) bytes, as floats [coef 3C][partials parts x 2C][sums 2C][pivot C]
  * with room for the 64 x 2C fold of caller-supplied partials; the backward reuses the regions (`sums`: the mask
@@ -603,6 +614,10 @@ int ssl4gie_bn_bwd_reduce(const void* dy, int mask_kind, const void* mask, const
 int ssl4gie_bn_bwd_apply(const void* dy, int mask_kind, const void* mask, const void* x, const float* gamma,
                          const float* beta, const float* mean, const float* rstd, const float* sums, float inv_count,
                          void* dx, float* workspace, int dtype, long long rows, int C, void* stream);
+int ssl4gie_bn_bwd_frozen(const void* dy, int mask_kind, const void* mask, const void* x, const float* gamma,
+                          const float* beta, const float* mean, const float* rstd, void* dx, void* dres, float* dgamma,
+                          float* dbeta, int accumulate, float* workspace, int dtype, long long rows, int C,
+                          void* stream);
 /* The exchange's arithmetic as ONE launch: gathered [world][2C + 1] = every rank's (mean[C], biased var[C],
  * row count) -> pooled mean / rstd (ranks may hold different row counts), the total row count (device
  * scalar) and, if given, the running statistics (unbiased variance, momentum) — what torch.nn.SyncBatchNorm

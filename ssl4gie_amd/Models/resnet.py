@@ -17,20 +17,55 @@ import torch.nn as nn
 from ..dpt_engine import Conv3x3Fn
 from ..engine import EngineModule, GradJoin, LinearFn
 from ..resnet_engine import (AvgPoolFn, BatchNormFn, BnReluMaxPoolFn, MaxPoolFn, StemConvFn, Subsample2Fn,
-                             _count_batch, _sync_group, bn_relu_maxpool_ok)
+                             _count_batch, _sync_group, bn_relu_maxpool_ok, bn_trains)
+
+
+class FrozenBatchNorm2d(nn.Module):
+    """BatchNorm2d whose statistics AND affine parameters are fixed: torchvision 0.10's class of this name
+    (`torchvision/ops/misc.py`; un-vendored and restated, see the module docstring), the norm layer of
+    `fasterrcnn_resnet50_fpn`'s trunk (reference Object_detection/train_detection.py:197-202).  weight, bias,
+    running_mean and running_var are buffers, there is no `num_batches_tracked`, no momentum and no training mode; the
+    gradient still passes through the per-channel map y = (x - running_mean) rsqrt(running_var + eps) weight + bias.
+    On the engine the arithmetic is resnet_engine.BatchNormFn's (`frozen_statistics` is what it looks for); `forward`
+    is the torch formula on a plain NCHW tensor."""
+    frozen_statistics = True
+
+    def __init__(self, num_features, eps=1e-5):
+        super().__init__()
+        self.num_features, self.eps = num_features, eps
+        self.register_buffer("weight", torch.ones(num_features))
+        self.register_buffer("bias", torch.zeros(num_features))
+        self.register_buffer("running_mean", torch.zeros(num_features))
+        self.register_buffer("running_var", torch.ones(num_features))
+
+    def _load_from_state_dict(self, state_dict, prefix, local_metadata, strict, missing_keys, unexpected_keys,
+                              error_msgs):
+        # an ordinary BatchNorm2d checkpoint loads with strict=True: its batch count has no home here
+        state_dict.pop(prefix + "num_batches_tracked", None)
+        super()._load_from_state_dict(state_dict, prefix, local_metadata, strict, missing_keys, unexpected_keys,
+                                      error_msgs)
+
+    def forward(self, x):
+        scale = (self.weight * torch.rsqrt(self.running_var + self.eps)).reshape(1, -1, 1, 1)
+        shift = self.bias.reshape(1, -1, 1, 1) - self.running_mean.reshape(1, -1, 1, 1) * scale
+        return x * scale + shift
+
+    def extra_repr(self):
+        return f"{self.num_features}, eps={self.eps}"
 
 
 class Bottleneck(nn.Module):
     expansion = 4
 
-    def __init__(self, inplanes, planes, stride=1, downsample=None):
+    def __init__(self, inplanes, planes, stride=1, downsample=None, norm_layer=None):
         super().__init__()
+        norm_layer = norm_layer or nn.BatchNorm2d
         self.conv1 = nn.Conv2d(inplanes, planes, 1, bias=False)
-        self.bn1 = nn.BatchNorm2d(planes)
+        self.bn1 = norm_layer(planes)
         self.conv2 = nn.Conv2d(planes, planes, 3, stride, 1, bias=False)
-        self.bn2 = nn.BatchNorm2d(planes)
+        self.bn2 = norm_layer(planes)
         self.conv3 = nn.Conv2d(planes, planes * 4, 1, bias=False)
-        self.bn3 = nn.BatchNorm2d(planes * 4)
+        self.bn3 = norm_layer(planes * 4)
         self.relu = nn.ReLU(inplace=True)
         self.downsample = downsample
         self.stride = stride
@@ -40,11 +75,16 @@ class ResNet50(EngineModule):
     """the trunk (`forward_maps` -> channels-last layer4 map, or the 4 stage maps; `pooled`) and, when built with
     num_classes, torchvision's `forward` through `fc`"""
 
-    def __init__(self, zero_init_residual=False, num_classes=None):
+    STAGES = ("conv1", "layer1", "layer2", "layer3", "layer4")   # `freeze_stages` counts them from the end
+
+    def __init__(self, zero_init_residual=False, num_classes=None, norm_layer=None):
+        """norm_layer: None (nn.BatchNorm2d) or a class with its constructor, e.g. FrozenBatchNorm2d"""
         super().__init__()
+        self._norm_layer = norm_layer or nn.BatchNorm2d
+        self._freeze_rule = False
         self.inplanes = 64
         self.conv1 = nn.Conv2d(3, 64, 7, 2, 3, bias=False)
-        self.bn1 = nn.BatchNorm2d(64)
+        self.bn1 = self._norm_layer(64)
         self.relu = nn.ReLU(inplace=True)
         self.maxpool = nn.MaxPool2d(3, 2, 1)
         self.layer1 = self._make_layer(64, 3)
@@ -69,12 +109,39 @@ class ResNet50(EngineModule):
         downsample = None
         if stride != 1 or self.inplanes != planes * 4:
             downsample = nn.Sequential(nn.Conv2d(self.inplanes, planes * 4, 1, stride, bias=False),
-                                       nn.BatchNorm2d(planes * 4))
-        layers = [Bottleneck(self.inplanes, planes, stride, downsample)]
+                                       self._norm_layer(planes * 4))
+        layers = [Bottleneck(self.inplanes, planes, stride, downsample, self._norm_layer)]
         self.inplanes = planes * 4
         for _ in range(1, blocks):
-            layers.append(Bottleneck(self.inplanes, planes))
+            layers.append(Bottleneck(self.inplanes, planes, norm_layer=self._norm_layer))
         return nn.Sequential(*layers)
+
+    def freeze_stages(self, trainable_layers):
+        """torchvision's rule of `resnet_fpn_backbone(trainable_layers=...)` (detection/backbone_utils.py; 5 is what
+        the reference passes as trainable_backbone_layers): the last `trainable_layers` of conv1, layer1 .. layer4
+        keep training, every parameter whose name starts with none of them is frozen.  (torchvision also names bn1
+        at 5; under FrozenBatchNorm2d it has no parameters.)  From then on `forward_maps` runs the leading stages
+        without a trainable parameter under torch.no_grad()."""
+        if not isinstance(trainable_layers, int) or not 0 <= trainable_layers <= 5:
+            raise ValueError(f"trainable_layers is {trainable_layers!r}: an integer from 0 to 5")
+        train = self.STAGES[::-1][:trainable_layers]
+        for name, p in self.named_parameters():
+            if not name.startswith(train):
+                p.requires_grad_(False)
+        self._freeze_rule = True
+        return self
+
+    def _frozen_lead(self):
+        """how many of (stem, layer1 .. layer4), from the input on, hold no trainable parameter — counted only
+        after `freeze_stages`: these run under no_grad, so no activation is kept and no backward kernel runs"""
+        if not self._freeze_rule:
+            return 0
+        n = 0
+        for mods in ((self.conv1, self.bn1), (self.layer1,), (self.layer2,), (self.layer3,), (self.layer4,)):
+            if any(p.requires_grad for m in mods for p in m.parameters()):
+                break
+            n += 1
+        return n
 
     # ------------------------------------------------------------------ engine forward
     def _bn(self, x, bn, relu, res=None, stats=None, join=None):
@@ -131,7 +198,7 @@ class ResNet50(EngineModule):
         if torch.is_grad_enabled() or self.dtype_ != torch.bfloat16:
             return False
         from ..resnet_engine import _SYNC_FUSED
-        if not (bn.training or bn.running_mean is None) or (_sync_group(bn)[0] and not _SYNC_FUSED):
+        if not bn_trains(bn) or (_sync_group(bn)[0] and not _SYNC_FUSED):
             return False
         st = conv.stride[0]
         rows = x.shape[0] * ((x.shape[1] - 1) // st + 1) * ((x.shape[2] - 1) // st + 1)
@@ -174,16 +241,19 @@ class ResNet50(EngineModule):
 
     def forward_maps(self, imgs, all_stages=False):
         self._prepare()
-        x, st = StemConvFn.apply(imgs, self.conv1.weight, self.dtype_, self.sink(), self.lp_cache, True)
-        if bn_relu_maxpool_ok(x, self.bn1, st):   # bn1 -> relu -> maxpool in one pass over the convolution output
-            x = BnReluMaxPoolFn.apply(x, self.bn1.weight, self.bn1.bias, self.bn1, self.sink(), st)
-        else:
-            x = self._bn(x, self.bn1, True, stats=st)
-            x = MaxPoolFn.apply(x)
+        lead = self._frozen_lead()   # after freeze_stages: the stages in front of the first trainable one
+        with torch.set_grad_enabled(torch.is_grad_enabled() and lead < 1):
+            x, st = StemConvFn.apply(imgs, self.conv1.weight, self.dtype_, self.sink(), self.lp_cache, True)
+            if bn_relu_maxpool_ok(x, self.bn1, st):   # bn1 -> relu -> maxpool in one pass over the convolution output
+                x = BnReluMaxPoolFn.apply(x, self.bn1.weight, self.bn1.bias, self.bn1, self.sink(), st)
+            else:   # fixed statistics (evaluation mode, FrozenBatchNorm2d) take the separate passes
+                x = self._bn(x, self.bn1, True, stats=st)
+                x = MaxPoolFn.apply(x)
         maps = []
-        for layer in (self.layer1, self.layer2, self.layer3, self.layer4):
-            for blk in layer:
-                x = self._block(x, blk)
+        for i, layer in enumerate((self.layer1, self.layer2, self.layer3, self.layer4)):
+            with torch.set_grad_enabled(torch.is_grad_enabled() and lead < i + 2):
+                for blk in layer:
+                    x = self._block(x, blk)
             maps.append(x)
         return maps if all_stages else x
 
@@ -201,6 +271,7 @@ class ResNet50(EngineModule):
         return LinearFn.apply(x, self.fc.weight, self.fc.bias, self.dtype_, torch.float32, self.sink(), self.lp_cache)
 
 
-def resnet50(num_classes=1000, zero_init_residual=False, **kwargs):
-    """torchvision.models.resnet50 signature subset used by the reference (main_moco.py:185-187)"""
-    return ResNet50(zero_init_residual=zero_init_residual, num_classes=num_classes)
+def resnet50(num_classes=1000, zero_init_residual=False, norm_layer=None, **kwargs):
+    """torchvision.models.resnet50 signature subset used by the reference (main_moco.py:185-187; norm_layer:
+    detection's FrozenBatchNorm2d trunk, Object_detection/train_detection.py:197-202)"""
+    return ResNet50(zero_init_residual=zero_init_residual, num_classes=num_classes, norm_layer=norm_layer)

@@ -10,6 +10,7 @@
 //   bn_apply         y = act((x - mean) rstd gamma + beta (+ residual))     act = ReLU | id
 //   bn_bwd_reduce    partials of sum(dy) and sum(dy * xhat) over the rows (dy already ReLU-masked)
 //   bn_bwd_apply     dx = gamma rstd (g - mean(g) - xhat mean(g xhat)); optional dres = g
+//   bn_bwd_frozen    fixed statistics (evaluation mode, FrozenBatchNorm2d): dx = gamma rstd g in one pass
 //   maxpool3x3s2     forward with argmax byte, backward in gather form
 //   avgpool          global average per image and its gradient
 #include "common.h"
@@ -465,6 +466,162 @@ __global__ void bn_bwd_apply_kernel(const T* __restrict__ dy, const T* __restric
         g[j] = a[j] * gg + b[j] * (xv[j] - m[j]) + d[j];
     }
     *(typename V16<T>::raw*)(dx + idx) = pk<T>(g);
+}
+// ---- frozen statistics (evaluation mode, torchvision's FrozenBatchNorm2d): y = x a + b with a = rstd gamma FIXED, so
+// dx = a g and no term depends on a sum over the batch.  MASK is the mask kind of the C ABI (0 none, 1 the ReLU output,
+// 2 rebuilt as x a + b > 0 by bn_affine, as the forward decided it, 3 the forward's bit map).
+// four of the caller's per-channel floats: one 16-byte load where the pointer allows it (a caller may pass a slice)
+template <bool AL>
+DEVI f32x4 bn_ld_channels(const float* p) {
+    if constexpr (AL) return ld4(p);
+    return f32x4{p[0], p[1], p[2], p[3]};
+}
+// without parameter gradients: a flat map, one 16-byte vector per thread.  dy (+ the ReLU output | 1/16 of a bit map
+// | x) -> dx (+ dres = the masked dy)
+template <typename T, int MASK, bool AL>
+__global__ void bn_bwd_frozen_kernel(const T* __restrict__ dy, const void* __restrict__ mask,
+                                     const T* __restrict__ x, const float* __restrict__ gamma,
+                                     const float* __restrict__ beta, const float* __restrict__ mean,
+                                     const float* __restrict__ rstd, T* __restrict__ dx, T* __restrict__ dres,
+                                     int C, long long total) {
+    constexpr int V = V16<T>::N;
+    typedef typename V16<T>::raw raw_t;
+    const long long idx = ((long long)blockIdx.x * blockDim.x + threadIdx.x) * V;
+    if (idx >= total) return;
+    const int c = (int)(idx % C);
+    const raw_t gv = *(const raw_t*)(dy + idx);
+    float g[V], a[V];
+    [[maybe_unused]] float t[V];  // what the sign is taken of: the ReLU output, or x and then the pre-activation
+    [[maybe_unused]] unsigned mk = 0;
+    if constexpr (MASK == SSL4GIE_BN_MASK_Y) un<T>(*(const raw_t*)((const T*)mask + idx), t);
+    if constexpr (MASK == SSL4GIE_BN_MASK_X) un<T>(*(const raw_t*)(x + idx), t);
+    if constexpr (MASK == SSL4GIE_BN_MASK_BITS) mk = ((const unsigned char*)mask)[idx >> 3];  // V == 8: one byte
+    un<T>(gv, g);
+#pragma unroll
+    for (int j = 0; j < V; j += 4) {
+        const f32x4 one = {1.f, 1.f, 1.f, 1.f}, zero = {0.f, 0.f, 0.f, 0.f};
+        const f32x4 r = bn_ld_channels<AL>(rstd + c + j), gm = gamma ? bn_ld_channels<AL>(gamma + c + j) : one;
+        if constexpr (MASK == SSL4GIE_BN_MASK_X) {
+            const f32x4 mu = bn_ld_channels<AL>(mean + c + j), be = beta ? bn_ld_channels<AL>(beta + c + j) : zero;
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                float mb;
+                bn_affine(gm[i], be[i], mu[i], r[i], a[j + i], mb);
+                t[j + i] = t[j + i] * a[j + i] + mb;
+            }
+        } else {
+#pragma unroll
+            for (int i = 0; i < 4; ++i) a[j + i] = r[i] * gm[i];
+        }
+    }
+    if constexpr (MASK != SSL4GIE_BN_MASK_NONE) {
+#pragma unroll
+        for (int j = 0; j < V; ++j) {
+            const bool keep = MASK == SSL4GIE_BN_MASK_BITS ? ((mk >> j) & 1u) != 0 : t[j] > 0.f;
+            g[j] = keep ? g[j] : 0.f;
+        }
+    }
+    if (dres) *(raw_t*)(dres + idx) = MASK == SSL4GIE_BN_MASK_NONE ? gv : pk<T>(g);
+#pragma unroll
+    for (int j = 0; j < V; ++j) g[j] *= a[j];
+    *(raw_t*)(dx + idx) = pk<T>(g);
+}
+// with parameter gradients: lane mapping, rows in flight and partials of bn_bwd_reduce_kernel (partial[blk][0][c] =
+// sum g, [1][c] = sum g xhat; x NULL: only sum g is wanted and [1] is zero), and dx = a g (+ dres) written in the
+// same pass — bn_bwd_tail_kernel finishes dgamma / dbeta
+template <typename T, int MASK>
+__global__ __launch_bounds__(256) void bn_bwd_frozen_reduce_kernel(
+    const T* __restrict__ dy, const void* __restrict__ mask, const T* __restrict__ x,
+    const float* __restrict__ gamma, const float* __restrict__ beta, const float* __restrict__ mean,
+    const float* __restrict__ rstd, T* __restrict__ dx, T* __restrict__ dres, float* __restrict__ partial,
+    long long rows, int C) {
+    constexpr int V = V16<T>::N;
+    typedef typename V16<T>::raw raw_t;
+    __shared__ float red[3][2][64][V];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const BnLanes m = bn_lanes<V>(C, lane);
+    float s[V], q[V];
+#pragma unroll
+    for (int j = 0; j < V; ++j) s[j] = q[j] = 0.f;
+    if (m.c < C) {
+        const bool hx = x != nullptr;
+        float mu[V], rs[V], a[V];
+        [[maybe_unused]] float mb[V];
+#pragma unroll
+        for (int j = 0; j < V; ++j) {
+            mu[j] = mean ? mean[m.c + j] : 0.f;
+            rs[j] = rstd[m.c + j];
+            float b;
+            bn_affine(gamma ? gamma[m.c + j] : 1.f, beta ? beta[m.c + j] : 0.f, mu[j], rs[j], a[j], b);
+            if constexpr (MASK == SSL4GIE_BN_MASK_X) mb[j] = b;
+        }
+        const T* y = (const T*)mask;
+        [[maybe_unused]] const unsigned char* bits = (const unsigned char*)mask;
+        // tv: the ReLU output (MASK_Y) or, in its first word, this vector's byte of the bit map (MASK_BITS)
+        auto acc = [&](const raw_t& gv, const raw_t& tv, const raw_t& xv, size_t o) {
+            float g[V], xx[V];
+            un<T>(gv, g);
+            un<T>(xv, xx);
+            if constexpr (MASK == SSL4GIE_BN_MASK_X) {
+#pragma unroll
+                for (int j = 0; j < V; ++j) g[j] = xx[j] * a[j] + mb[j] > 0.f ? g[j] : 0.f;
+            } else if constexpr (MASK == SSL4GIE_BN_MASK_BITS) {
+                const unsigned mk = (unsigned)tv[0];
+#pragma unroll
+                for (int j = 0; j < V; ++j) g[j] = ((mk >> j) & 1u) ? g[j] : 0.f;
+            } else if constexpr (MASK == SSL4GIE_BN_MASK_Y) {
+                float yy[V];
+                un<T>(tv, yy);
+#pragma unroll
+                for (int j = 0; j < V; ++j) g[j] = yy[j] > 0.f ? g[j] : 0.f;
+            }
+            if (dres) *(raw_t*)(dres + o) = MASK == SSL4GIE_BN_MASK_NONE ? gv : pk<T>(g);
+            float d[V];
+#pragma unroll
+            for (int j = 0; j < V; ++j) {
+                s[j] += g[j];
+                if (hx) q[j] += g[j] * ((xx[j] - mu[j]) * rs[j]);
+                d[j] = g[j] * a[j];
+            }
+            *(raw_t*)(dx + o) = pk<T>(d);
+        };
+        auto side = [&](const raw_t& gv, size_t o) -> raw_t {
+            raw_t r = gv;
+            if constexpr (MASK == SSL4GIE_BN_MASK_BITS && V == 8) { r = raw_t{}; r[0] = bits[o >> 3]; }
+            if constexpr (MASK == SSL4GIE_BN_MASK_Y) r = *(const raw_t*)(y + o);
+            return r;
+        };
+        const long long step = (long long)gridDim.y * 4 * m.rpw;
+        long long r = ((long long)blockIdx.y * 4 + wave) * m.rpw + m.rsub;
+        constexpr int NR = MASK == SSL4GIE_BN_MASK_Y ? 2 : 4;  // rows in flight per lane: up to ~8 16-B loads outstanding
+        for (; r + (NR - 1) * step < rows; r += NR * step) {
+            size_t o[NR];
+            raw_t gv[NR], xv[NR], tv[NR];
+#pragma unroll
+            for (int i = 0; i < NR; ++i) {
+                o[i] = (size_t)(r + i * step) * C + m.c;
+                gv[i] = *(const raw_t*)(dy + o[i]);
+                xv[i] = hx ? *(const raw_t*)(x + o[i]) : gv[i];
+                tv[i] = side(gv[i], o[i]);
+            }
+#pragma unroll
+            for (int i = 0; i < NR; ++i) acc(gv[i], tv[i], xv[i], o[i]);
+        }
+        for (; r < rows; r += step) {
+            const size_t o0 = (size_t)r * C + m.c;
+            const raw_t g0 = *(const raw_t*)(dy + o0);
+            acc(g0, side(g0, o0), hx ? *(const raw_t*)(x + o0) : g0, o0);
+        }
+    }
+    bn_block_reduce<V>(s, q, red, m.lpr, lane, wave);
+    if (wave == 0 && m.c < C && m.rsub == 0) {
+        float* p = partial + (size_t)blockIdx.y * 2 * C;
+#pragma unroll
+        for (int j = 0; j < V; j += 4) {
+            st4(p + m.c + j, f32x4{s[j], s[j + 1], s[j + 2], s[j + 3]});
+            st4(p + C + m.c + j, f32x4{q[j], q[j + 1], q[j + 2], q[j + 3]});
+        }
+    }
 }
 
 // ------------------------------------------------------------------ MaxPool2d(3, 2, 1)
@@ -1077,6 +1234,82 @@ extern "C" int ssl4gie_bn_bwd_apply(const void* dy, int mask_kind, const void* m
     }
     return bn_launch_bwd_apply(dy, mask, x, ws.coef, dx, mask_kind != SSL4GIE_BN_MASK_NONE, mcoef, ws.pivot, dtype,
                                rows, C, st);
+}
+// backward through FIXED statistics (evaluation mode, FrozenBatchNorm2d): dx = rstd gamma g, dres = g; with dgamma /
+// dbeta one reduction pass that writes dx and dres as well, without them one flat pass that reads x only for MASK_X
+template <typename T, int MASK>
+static void bn_launch_frozen_t(const void* dy, const void* mask, const void* x, const float* gamma, const float* beta,
+                               const float* mean, const float* rstd, void* dx, void* dres, float* partial, int parts,
+                               int dtype, long long rows, int C, hipStream_t st) {
+    if (partial) {
+        hipLaunchKernelGGL((bn_bwd_frozen_reduce_kernel<T, MASK>), dim3(bn_strips(C, dtype), parts), dim3(256), 0, st,
+                           (const T*)dy, mask, (const T*)x, gamma, beta, mean, rstd, (T*)dx, (T*)dres, partial, rows,
+                           C);
+        return;
+    }
+    const long long total = rows * C;
+    const dim3 grid(blocks_of(total / vecn(dtype)));
+    auto launch = [&](auto kernel) {
+        hipLaunchKernelGGL(kernel, grid, dim3(256), 0, st, (const T*)dy, mask, (const T*)x, gamma, beta, mean, rstd,
+                           (T*)dx, (T*)dres, C, total);
+    };
+    if (is16(gamma) && is16(beta) && is16(mean) && is16(rstd)) launch(bn_bwd_frozen_kernel<T, MASK, true>);
+    else launch(bn_bwd_frozen_kernel<T, MASK, false>);
+}
+template <typename T>
+static void bn_launch_frozen(int mask_kind, const void* dy, const void* mask, const void* x, const float* gamma,
+                             const float* beta, const float* mean, const float* rstd, void* dx, void* dres,
+                             float* partial, int parts, int dtype, long long rows, int C, hipStream_t st) {
+#define FROZEN(MASK) \
+    bn_launch_frozen_t<T, MASK>(dy, mask, x, gamma, beta, mean, rstd, dx, dres, partial, parts, dtype, rows, C, st)
+    switch (mask_kind) {
+    case SSL4GIE_BN_MASK_NONE: FROZEN(SSL4GIE_BN_MASK_NONE); break;
+    case SSL4GIE_BN_MASK_Y: FROZEN(SSL4GIE_BN_MASK_Y); break;
+    case SSL4GIE_BN_MASK_X: FROZEN(SSL4GIE_BN_MASK_X); break;
+    case SSL4GIE_BN_MASK_BITS:
+        if constexpr (sizeof(T) == 2) FROZEN(SSL4GIE_BN_MASK_BITS);  // bf16 only (checked by the caller)
+        break;
+    }
+#undef FROZEN
+}
+extern "C" int ssl4gie_bn_bwd_frozen(const void* dy, int mask_kind, const void* mask, const void* x,
+                                     const float* gamma, const float* beta, const float* mean, const float* rstd,
+                                     void* dx, void* dres, float* dgamma, float* dbeta, int accumulate,
+                                     float* workspace, int dtype, long long rows, int C, void* stream) {
+    REQUIRE(dy && rstd && dx && dt_ok(dtype) && rows > 0 && C > 0 && C % vecn(dtype) == 0);
+    const bool params = dgamma || dbeta, need_x = mask_kind == SSL4GIE_BN_MASK_X || dgamma;
+    // a pointer the form does not use is NULL: x and mean without MASK_X and dgamma, the workspace without a reduction
+    REQUIRE(!x == !need_x && !mean == !need_x && !workspace == !params);
+    switch (mask_kind) {
+    case SSL4GIE_BN_MASK_NONE: REQUIRE(!mask && !beta); break;
+    case SSL4GIE_BN_MASK_Y: REQUIRE(mask && !beta); break;
+    case SSL4GIE_BN_MASK_X: REQUIRE(!mask && !dres); break;
+    case SSL4GIE_BN_MASK_BITS: REQUIRE(mask && !beta && dres && dtype == SSL4GIE_BF16); break;
+    default: return ARG_ERR;
+    }
+    hipStream_t st = (hipStream_t)stream;
+    // algorithmic bytes: dy (+ the ReLU output | 1/16 of a map of bits) (+ x) -> dx (+ dres)
+    ProfScope prof(PROF_BN, (double)rows * C * (dtype == SSL4GIE_BF16 ? 2 : 4) *
+                                (2 + (mask_kind == SSL4GIE_BN_MASK_Y ? 1 : 0) +
+                                 (mask_kind == SSL4GIE_BN_MASK_BITS ? 0.0625 : 0) + (x ? 1 : 0) + (dres ? 1 : 0)), st);
+    const int parts = bn_parts(rows, C);
+    float* partial = params ? BnWs(workspace, parts, C).partial : nullptr;
+    if (dtype == SSL4GIE_BF16)
+        bn_launch_frozen<bf16_t>(mask_kind, dy, mask, x, gamma, beta, mean, rstd, dx, dres, partial, parts, dtype, rows,
+                                 C, st);
+    else
+        bn_launch_frozen<float>(mask_kind, dy, mask, x, gamma, beta, mean, rstd, dx, dres, partial, parts, dtype, rows,
+                                C, st);
+    LAUNCH_CHECK();
+    if (!params) return 0;
+    // dbeta = sum g, dgamma = sum g xhat by the training-mode tail (bn_parts <= 1024 <= BN_TAIL_WIDE: no fold).  Its dx
+    // coefficients and copy of mean land in the workspace unread; without x there is no mean to copy and rstd stands in
+    const BnWs ws(workspace, parts, C);
+    hipLaunchKernelGGL(bn_bwd_tail_kernel, dim3((C + 63) / 64), bn_tail_block(parts), 0, st, ws.partial, parts,
+                       mean ? mean : rstd, rstd, gamma, 0.f, ws.coef, dgamma, dbeta, accumulate, C,
+                       (const float*)nullptr, (float*)nullptr, ws.pivot);
+    LAUNCH_CHECK();
+    return 0;
 }
 
 // ---- SyncBatchNorm: pooled statistics out of the gathered per-rank records ----------------------------

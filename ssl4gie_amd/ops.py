@@ -1236,6 +1236,27 @@ def bn_bwd_xmask(dy2d, x2d, gamma, beta, mean, rstd, dgamma, dbeta, accumulate):
     return _bn_bwd(dy2d, _lib.BN_MASK_X, None, x2d, gamma, beta, mean, rstd, False, dgamma, dbeta, accumulate)[0]
 
 
+def bn_bwd_frozen(dy2d, mask_kind, mask, x2d, gamma, beta, mean, rstd, want_dres, dgamma, dbeta, accumulate):
+    """ssl4gie_bn_bwd_frozen: backward through FIXED statistics (evaluation mode, FrozenBatchNorm2d) -> (dx, dres):
+    dx = rstd gamma g with g the masked dy, dres = g; dgamma / dbeta (targets, or None) overwritten or accumulated.
+    x2d and mean are passed for MASK_X or with dgamma only, beta for MASK_X only (None otherwise, as the C ABI asks);
+    without parameter gradients it is one flat pass and there is no workspace"""
+    _dev(dy2d, x2d, gamma, beta, mean, rstd, dgamma, dbeta)
+    _f32(gamma, beta, mean, rstd, dgamma, dbeta)
+    rows, C = dy2d.shape
+    assert x2d is None or (x2d.shape == dy2d.shape and x2d.dtype == dy2d.dtype)
+    if mask_kind == _lib.BN_MASK_Y:
+        assert mask.shape == dy2d.shape and mask.dtype == dy2d.dtype
+    dx = torch.empty_like(dy2d)
+    dres = torch.empty_like(dy2d) if want_dres else None
+    ws = _bn_ws(rows, C, dy2d.device) if (dgamma is not None or dbeta is not None) else None
+    _lib.check(_lib.load().ssl4gie_bn_bwd_frozen(
+        ptr(dy2d), mask_kind, _bn_mask(mask_kind, mask, dy2d), ptr(x2d), ptr(gamma), ptr(beta), ptr(mean), ptr(rstd),
+        ptr(dx), ptr(dres), ptr(dgamma), ptr(dbeta), int(accumulate), ptr(ws), code(dy2d.dtype), rows, C, stream()),
+        "bn_bwd_frozen")
+    return dx, dres
+
+
 def maxpool3x3s2_fwd(x, coef=None, relu=False):
     """coef [2, C] (ops.bn_coef_partials): the pool runs over act(x coef[0] + coef[1]) — BatchNorm (+ ReLU) applied
     on the way in (ssl4gie_bn_maxpool3x3s2_fwd)"""

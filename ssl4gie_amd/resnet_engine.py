@@ -360,6 +360,47 @@ def _bn_backward(dy2, x2, mask, gamma, beta, mean, rstd, want_dres, targets, acc
     return ops.bn_bwd_apply(dy2, m, x2, gd, mean, rstd, gsums, 1.0, kind == "y"), dres
 
 
+def is_frozen_bn(bn):
+    """Models.resnet.FrozenBatchNorm2d (torchvision's class of that name): weight, bias and the statistics are
+    buffers; it has no momentum, no num_batches_tracked and no training mode"""
+    return getattr(bn, "frozen_statistics", False)
+
+
+def bn_trains(bn):
+    """whether the layer normalises with batch statistics (a FrozenBatchNorm2d never does, whatever its `training`
+    flag says)"""
+    return not is_frozen_bn(bn) and (bn.training or bn.running_mean is None)
+
+
+def _frozen_constants(bn, gamma, beta, want_coef):
+    """(rstd, coef [2, C] or None) of a FrozenBatchNorm2d, computed once per module and again only when one of its
+    buffers is rewritten or replaced (load_state_dict, .to()): keyed on the buffers' storage and `_version`"""
+    key = tuple((t.data_ptr(), t._version) for t in (bn.running_mean, bn.running_var, gamma, beta)) + (bn.eps,)
+    cache = bn.__dict__.get("_ssl4gie_frozen")
+    if cache is None or cache[0] != key:
+        cache = [key, torch.rsqrt(bn.running_var + bn.eps), None]
+        bn.__dict__["_ssl4gie_frozen"] = cache
+    if want_coef and cache[2] is None:
+        cache[2] = ops.bn_coef_stats(bn.running_mean, cache[1], gamma, beta)
+    return cache[1], cache[2] if want_coef else None
+
+
+_MASK_KINDS = {"none": 0, "y": 1, "x": 2, "bits": 3}   # SSL4GIE_BN_MASK_*
+
+
+def _bn_backward_frozen(dy2, x2, mask, gamma, beta, mean, rstd, want_dres, targets, acc):
+    """backward through fixed statistics -> (dx, dres): dx = rstd gamma g, dres = g, and dgamma / dbeta into
+    `targets` where the affine parameters train.  x and mean are handed over only where the call reads them (the
+    mask rebuilt from x, or dgamma)"""
+    kind, m = mask
+    tg, tb = targets
+    gd = gamma.detach() if gamma is not None else None
+    reads_x = kind == "x" or tg is not None
+    return ops.bn_bwd_frozen(dy2, _MASK_KINDS[kind], m, x2 if reads_x else None, gd,
+                             beta.detach() if (kind == "x" and beta is not None) else None,
+                             mean if reads_x else None, rstd, want_dres or kind == "bits", tg, tb, acc)
+
+
 class BatchNormFn(torch.autograd.Function):
     """nn.BatchNorm2d / BatchNorm1d / SyncBatchNorm over the rows of a [..., C] tensor, (+ residual)
     (+ ReLU).  With an nn.SyncBatchNorm holder and world_size > 1 the statistics are global: local
@@ -376,7 +417,8 @@ class BatchNormFn(torch.autograd.Function):
         C = shp[-1]
         x2 = x.contiguous().view(-1, C)
         r2 = res.contiguous().view(-1, C) if res is not None else None
-        training = bn.training or bn.running_mean is None
+        frozen = is_frozen_bn(bn)
+        training = bn_trains(bn)
         g = gamma.detach() if gamma is not None else None
         b = beta.detach() if beta is not None else None
         sync, group = _sync_group(bn)
@@ -402,9 +444,21 @@ class BatchNormFn(torch.autograd.Function):
             else:
                 y, _, _ = ops.bn_fwd(x2, g, b, r2, None, None, 0.0, bn.eps, relu, False, mean, rstd)
         else:
+            # fixed statistics: no exchange under SyncBatchNorm either.  Without parameter gradients the backward is
+            # dx = rstd gamma g behind a ReLU mask: x is not kept, and bn3 of a bottleneck hands over its mask as bits
+            want_params = any(ctx.needs_input_grad[1:3])
             mean = bn.running_mean
-            rstd = torch.rsqrt(bn.running_var + bn.eps)  # [C] floats: host-side plumbing
-            y, _, _ = ops.bn_fwd(x2, g, b, r2, None, None, 0.0, bn.eps, relu, False, mean, rstd)
+            want_bits = relu and r2 is not None and x2.dtype == torch.bfloat16 and ctx.needs_input_grad[0] \
+                and not want_params
+            if frozen:
+                rstd, coef = _frozen_constants(bn, g, b, want_bits)
+            else:
+                rstd = torch.rsqrt(bn.running_var + bn.eps)  # [C] floats: host-side plumbing
+                coef = ops.bn_coef_stats(mean, rstd, g, b) if want_bits else None
+            if want_bits:
+                y, bits = ops.bn_apply_bits(x2, coef, r2)
+            else:
+                y, _, _ = ops.bn_fwd(x2, g, b, r2, None, None, 0.0, bn.eps, relu, False, mean, rstd)
         if training and bn.num_batches_tracked is not None:
             _count_batch(bn)
         # the mask-from-x backward rebuilds the ReLU mask from gamma / beta as they are AT BACKWARD TIME: it is only
@@ -412,11 +466,13 @@ class BatchNormFn(torch.autograd.Function):
         # that path never reads the ReLU output, so it is not saved for it either
         if bits is not None:
             kind, m = "bits", bits
-        elif relu and res is None and _XMASK:
+        elif relu and res is None and _XMASK and (training or want_params):
             kind, m = "x", None
         else:
             kind, m = ("y", y) if relu else ("none", None)
         ctx.wepoch = weights_epoch()
+        if not training and not want_params:   # nothing reads x (or mean): the convolution output is not kept alive
+            x2 = mean = None
         ctx.save_for_backward(x2, m, gamma, beta, mean, rstd)
         ctx.cfg = (shp, kind, res is not None, sink, training, sync, group, total)
         return y.view(shp)
@@ -425,9 +481,6 @@ class BatchNormFn(torch.autograd.Function):
     def backward(ctx, dy):
         x2, m, gamma, beta, mean, rstd = ctx.saved_tensors
         shp, kind, has_res, sink, training, sync, group, total = ctx.cfg
-        if not training:
-            raise NotImplementedError("backward through BatchNorm in eval mode (frozen statistics) is "
-                                      "not built: the reference freezes trunks under no_grad")
         targets, acc, rets = sink.plan([gamma, beta])
         if kind == "x" and _bn_params_moved(ctx.wepoch, gamma, beta):
             if sync:
@@ -435,8 +488,12 @@ class BatchNormFn(torch.autograd.Function):
                                    "(set SSL4GIE_BN_XMASK=0)")
             raise RuntimeError("BatchNorm parameters were updated between this forward and its backward: the "
                                "ReLU mask rebuilt from them would disagree with the forward (set SSL4GIE_BN_XMASK=0)")
-        dx, dres = _bn_backward(dy.contiguous().view(-1, shp[-1]), x2, (kind, m), gamma, beta, mean, rstd, has_res,
-                                targets, acc, sync, group, total)
+        dy2 = dy.contiguous().view(-1, shp[-1])
+        if training:
+            dx, dres = _bn_backward(dy2, x2, (kind, m), gamma, beta, mean, rstd, has_res, targets, acc, sync, group,
+                                    total)
+        else:
+            dx, dres = _bn_backward_frozen(dy2, x2, (kind, m), gamma, beta, mean, rstd, has_res, targets, acc)
         gres = dres.view(shp) if has_res else None
         if gres is not None and ctx.join is not None:
             ctx.join.deposit(gres)  # joined in the data-gradient GEMM of the block's first convolution
@@ -505,7 +562,7 @@ class BnReluMaxPoolFn(torch.autograd.Function):
 def bn_relu_maxpool_ok(x, bn, stats):
     """whether BnReluMaxPoolFn applies: training-mode statistics from the convolution's partials (under
     SyncBatchNorm: local partials -> exchange -> coefficients of the global statistics), vector-width channels"""
-    return (_STEM_POOL_FUSED and stats is not None and (bn.training or bn.running_mean is None)
+    return (_STEM_POOL_FUSED and stats is not None and bn_trains(bn)
             and (_SYNC_FUSED or not _sync_group(bn)[0]) and x.shape[-1] % (8 if x.dtype == torch.bfloat16 else 4) == 0)
 
 
